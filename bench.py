@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- image-pairs/sec of full SiamUnet training steps through the HIP engine (BASELINE.json's metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 A step = zero_grad -> forward -> cross-entropy -> backward -> (gradient all-reduce) -> AdamW, on a synthetic
 LEVIR-CD-shaped batch already resident in HBM (stcd_amd/synth.py).  Weak scaling: the per-GPU batch is fixed.
-Rank 0 prints ONE JSON line.  At N=1 the line also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up and K timed steps, and prints the line; its
+roofline entry holds only the whole-step figures computed from the measured step time.  With --full the run then
+also measures
+  host_ms_per_step_idle_queue  the host's own cost of a step, over 5 more steps each started on an idle queue,
+and at N=1 the line also carries
   roofline      the dominant kernel class, timed live with HIP events on the engine's stream
                 (stcd_profile_* in include/stcd_hip.h) over instrumented steps of the same workload,
   cpu_baseline  the oracle (oracle/fcsiam_ref.py: a CPU PyTorch restatement pinned to the reference's golden
-                vectors) timed on this box's host cores over a bounded sample of the same workload.
+                vectors) timed on the host's cores over a bounded sample of the same workload.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: loss, the model's
+output map(s), and the parameters, gradients and BatchNorm statistics the step left behind (dump_outputs()).
 """
 import argparse
 import contextlib
@@ -160,6 +166,11 @@ def parse():
     ap.add_argument("--bucket-dtype", default="auto", choices=["auto", "fp32", "bf16"],
                     help="gradient buckets of the data-parallel all-reduce (N > 1): auto = bf16 payloads with fp32 accumulation for the families with "
                          "large gradients (SNUNet 48 MB, ChangeFormer 164 MB: SURVEY 8e), fp32 for the rest (FC-Siam 5-6 MB: latency-bound either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the idle-queue host cost, the per-kernel roofline and the CPU baseline "
+                         "(--no-roofline / --no-cpu-baseline leave out either)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-pairs", type=int, default=16)     # bounded CPU sample: ~10-30 s of host work in total (16 = the GPU's batch)
@@ -346,6 +357,40 @@ def pmc_traffic(kernel, model):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # --dump-outputs: every file together (64 MB less room for the .npy headers)
+
+
+def dump_outputs(dirname, loss, out, model):
+    """What one training step hands its caller: the loss, the model's output map(s), and the state it leaves in the model (parameters
+    after the optimizer step, their gradients, the BatchNorm running statistics; each flattened in named_parameters / named_buffers
+    order).  Written as float32 <name>.npy.  An array larger than its share of DUMP_BUDGET_BYTES is written as a fixed sample of its
+    flattened elements (sorted indices drawn without replacement from a generator seeded by the name and the size), so two runs with
+    the same arguments write the same elements."""
+    import zlib
+    outs = list(out) if isinstance(out, (list, tuple)) else [out]
+    arrays = {"loss": loss.detach().reshape(())}
+    arrays.update({"output" if len(outs) == 1 else f"output_{i}": o.detach() for i, o in enumerate(outs)})
+    params = list(model.parameters())
+    arrays["params"] = torch.cat([p.detach().float().reshape(-1) for p in params])
+    if all(p.grad is not None for p in params):
+        arrays["grads"] = torch.cat([p.grad.detach().float().reshape(-1) for p in params])
+    bufs = [b.detach().float().reshape(-1) for b in model.buffers() if b.dtype.is_floating_point]
+    if bufs:
+        arrays["bn_stats"] = torch.cat(bufs)
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // 4
+    by_size = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(by_size):        # smallest first: each array takes at most an equal share of what is left
+        n = t.numel()
+        k = min(n, left // (len(by_size) - i))
+        left -= k
+        if k < n:
+            rng = np.random.default_rng(zlib.crc32(name.encode()) + n)
+            idx = torch.from_numpy(np.sort(rng.choice(n, k, replace=False))).to(t.device)
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     from stcd_amd import synth
@@ -409,6 +454,7 @@ def main():
         CH = torch.ones(args.batch, dtype=torch.uint8, device=dev)
         CH[1::4] = 0                                                   # a quarter of the tiles take the no-change branch
         step_no = [0]
+    last = {} if args.dump_outputs else None                           # --dump-outputs: the model output of the latest step
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -416,12 +462,16 @@ def main():
             step_no[0] += 1
             x1, x2, lab_, _, _ = pseudo_change_pairs(TA, TD, TM, CH, seed=step_no[0])
             out = model(x1, x2)
+            if last is not None:
+                last["out"] = out
             out = out[-1] if isinstance(out, (list, tuple)) else out
             loss = cross_entropy(out, lab_) if args.label == 2 else bce_dice_with_logits(out, lab_.float().unsqueeze(1))
             loss.backward()
             opt.step()
             return loss
         out = model(A) if args.model == "unetseg" else model(A, B)
+        if last is not None:
+            last["out"] = out
         out = out[-1] if isinstance(out, (list, tuple)) else out      # SiamUnet_sub: [logits]; SegCD: (mask_t1, mask_t2, change)
         loss = cross_entropy(out, L) if args.label == 2 else bce_dice_with_logits(out, Lf)
         loss.backward()
@@ -431,8 +481,11 @@ def main():
     if args.graph:
         from stcd_amd.train_loop import GraphedTrainStep
         assert world == 1 and not args.pseudo, "--graph: single GPU, resident inputs"
-        lossf = (lambda out, y: cross_entropy(out[-1] if isinstance(out, (list, tuple)) else out, y)) if args.label == 2 else \
-                (lambda out, y: bce_dice_with_logits(out[-1] if isinstance(out, (list, tuple)) else out, y))
+        def lossf(out, y):
+            if last is not None:      # the captured call comes last: its output tensors are the ones every replay rewrites
+                last["out"] = out
+            out = out[-1] if isinstance(out, (list, tuple)) else out
+            return cross_entropy(out, y) if args.label == 2 else bce_dice_with_logits(out, y)
         gstep = GraphedTrainStep(model, opt, lossf, (A,) if args.model == "unetseg" else (A, B), L if args.label == 2 else Lf)
         eager_step = step
 
@@ -468,17 +521,21 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = tt.item()
     last_loss = loss.item()
-    # the host's OWN cost of a step: enqueue time into an idle queue (a synchronize in front of every step).  `host_enqueue_ms_per_step`
-    # above is taken while the GPU is busy: once the hardware queue is full the enqueue blocks, so on a GPU-bound step it approaches
-    # the step time whatever the host costs (ChangeFormer: 19.3 ms of 25.1 with 3.9 ms of real host work per step)
-    idle = []
-    for _ in range(5):
+    if rank == 0 and args.dump_outputs:      # before any further step changes the model
+        dump_outputs(args.dump_outputs, loss, last["out"], model)
+    # --full: the host's OWN cost of a step: enqueue time into an idle queue (a synchronize in front of every step).
+    # `host_enqueue_ms_per_step` above is taken while the GPU is busy: once the hardware queue is full the enqueue blocks, so on a
+    # GPU-bound step it approaches the step time whatever the host costs (ChangeFormer: 19.3 ms of 25.1 with 3.9 ms of real host work)
+    host_idle_ms = None
+    if args.full:
+        idle = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            step()
+            idle.append(time.perf_counter() - th)
         torch.cuda.synchronize()
-        th = time.perf_counter()
-        step()
-        idle.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    host_idle_ms = sorted(idle)[len(idle) // 2] * 1e3
+        host_idle_ms = sorted(idle)[len(idle) // 2] * 1e3
     my_rate = args.batch * args.steps / own_elapsed
     rank_rates = [my_rate]
     if world > 1:      # self-check of the first multi-GPU run: every rank's own pairs/s and the collective backend in use
@@ -495,7 +552,7 @@ def main():
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "host_enqueue_ms_per_step": round(enqueue_s / args.steps * 1e3, 4),     # << ms_per_step: the GPU is the bound, not the host
-        "host_ms_per_step_idle_queue": round(host_idle_ms, 4),                  # the host's own work per step (median of 5 steps, GPU idle)
+        "host_ms_per_step_idle_queue": None if host_idle_ms is None else round(host_idle_ms, 4),   # --full: the host's own work per step (median of 5 steps, GPU idle)
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": args.dtype, "data": "synthetic",
         "config": {"workload": f"{NAMES[args.model]}(3,{args.label}) {args.size}x{args.size} full training step "
@@ -524,7 +581,7 @@ def main():
                  "mfma_frac": round(fl_pp * sc * args.batch / step_s / 1e12 / peak_tf_, 4),
                  "note": "per GPU: algorithmic bytes / flops of one step (SURVEY 8d per-pair figures x pairs per GPU) over the measured step time"}
 
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         eng = model._engine
         nprof = 5
         # every instrumented step is read on its own and each kernel / class takes its MEDIAN over the steps, scaled back to nprof
@@ -603,7 +660,7 @@ def main():
             result["roofline"]["traffic_step_over_algorithmic"] = round(ts / step_roof["alg_bytes"], 3)
     elif rank == 0:
         result["roofline"] = {"step": step_roof}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.model, args.label, args.size, args.cpu_pairs, args.cpu_steps, args.encoder)
     if rank == 0:
         print(json.dumps(result), flush=True)

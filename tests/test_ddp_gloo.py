@@ -27,8 +27,29 @@ class StandInModel(torch.nn.Module):
         self.w.grad = g
 
 
+def _cpu_rank_env(rank, world, port):
+    """torchrun's env for this rank, with every GPU hidden before anything in this fresh process starts the HIP runtime: the ranks
+    take the CPU path on a GPU machine as well (init_distributed would otherwise put rank 1 on cuda:1 of a one-GPU machine)."""
+    os.environ.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",
+                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+
+
+def _join(procs, timeout):
+    """Every rank must exit 0; a rank still alive at the end (e.g. waiting in the rendezvous for a peer that failed) is killed, so
+    that it cannot keep pytest from exiting."""
+    try:
+        for p in procs:
+            p.join(timeout=timeout)
+            assert p.exitcode == 0
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join()
+
+
 def _worker(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _cpu_rank_env(rank, world, port)
     from stcd_amd.ddp import FlatGradReducer, broadcast_parameters, init_distributed
 
     r, lr, w = init_distributed(backend="gloo")
@@ -62,15 +83,13 @@ def test_two_rank_gradient_average_gloo():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    _join(procs, timeout=120)
     res = dict(q.get(timeout=5) for _ in range(2))
     assert res == {0: True, 1: True}
 
 
 def _worker_bf16(rank, world, port, q):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _cpu_rank_env(rank, world, port)
     from stcd_amd.ddp import FlatGradReducer, init_distributed
 
     init_distributed(backend="gloo")
@@ -95,9 +114,7 @@ def test_two_rank_bf16_buckets_accumulate_in_fp32():
     procs = [ctx.Process(target=_worker_bf16, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
+    _join(procs, timeout=120)
     assert dict(q.get(timeout=5) for _ in range(2)) == {0: True, 1: True}
 
 
@@ -150,7 +167,7 @@ class RangedModel(torch.nn.Module):
 
 
 def _ranged_worker(rank, world, port, q, layouts):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    _cpu_rank_env(rank, world, port)
     from stcd_amd.ddp import FlatGradReducer, init_distributed
     init_distributed(backend="gloo")
     ok = True
@@ -179,8 +196,6 @@ def test_two_ranks_over_real_stage_ranges_gloo():
     procs = [ctx.Process(target=_ranged_worker, args=(r, 2, port, q, layouts)) for r in range(2)]
     for p in procs:
         p.start()
-    for p in procs:
-        p.join(timeout=300)
-        assert p.exitcode == 0
+    _join(procs, timeout=300)
     res = dict(q.get(timeout=5) for _ in range(2))
     assert res == {0: True, 1: True}

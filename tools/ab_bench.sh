@@ -9,7 +9,7 @@ for round in 1 2; do
     python3 -c "
 import sys, runpy
 sys.path.insert(0, '$P'); import stcd_amd, stcd_amd._lib
-sys.argv = ['bench.py'] + '$* --no-cpu-baseline'.split()
+sys.argv = ['bench.py'] + '$* --full --no-cpu-baseline'.split()
 runpy.run_path('bench.py', run_name='__main__')" 2>/dev/null | python3 -c "
 import sys, json; d = json.loads(sys.stdin.readline()); print('$d', d['ms_per_step'], d['value'], {n: v for n, v in d['roofline']['kernel_ms_per_step'].items() if 'gemm' in n})" || exit 1
   done

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Copy the judged artefacts of tools/profile_round.sh from gpurun_out/<tag>/ into profiles/ (tracked):
   <tag>_bench.json          the bench.py line (roofline + cpu_baseline)
-  <tag>_kernel_stats.csv    rocprofv3 --kernel-trace --stats summary of `bench.py --no-cpu-baseline`
+  <tag>_kernel_stats.csv    rocprofv3 --kernel-trace --stats summary of `bench.py --full --no-cpu-baseline`
   <tag>_pmc_traffic.txt     per-kernel HBM-side bytes per launch from the separate FETCH_SIZE / WRITE_SIZE passes
                             (FETCH_SIZE, WRITE_SIZE are KiB; FETCH_SIZE doubled per the gfx950 correction of
                             /opt/skills/guides/MI355X_MICROARCH.md, section HBM)
@@ -10,7 +10,7 @@ usage: python tools/collect_profiles.py r01
 import collections, csv, glob, json, os, re, shutil, sys
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
-STEPS = 9            # bench.py --steps 3 --warmup 1 in the --pmc passes of tools/profile_round.sh, + the 5 idle-queue steps every run appends
+STEPS = 9            # bench.py --steps 3 --warmup 1 in the --pmc passes of tools/profile_round.sh, + the 5 idle-queue steps --full appends
 src, dst = f"gpurun_out/{tag}", "profiles"
 os.makedirs(dst, exist_ok=True)
 line = [l for l in open(f"{src}/bench.json") if l.startswith("{")][-1]

@@ -1,4 +1,4 @@
-"""Print the kernel table of a bench.py JSON line (tools aid)."""
+"""Print the kernel table of a `bench.py --full` JSON line (tools aid)."""
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(r["metric"], "|", r["value"], r["unit"], "|", r["ms_per_step"], "ms/step | host", r["host_enqueue_ms_per_step"])
