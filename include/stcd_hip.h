@@ -252,6 +252,22 @@ int stcd_loss_bce_dice(const float* x, const float* target, int64_t numel, int f
  * MSE(pse, |cd - 1|) over the rest, each divided by (count + 1e-8); dpred (nullable) = d loss / d pred, both halves. */
 int stcd_loss_contrastive(const float* pred, const int64_t* cd_label, const int64_t* pse_label, int64_t numel_half, float* loss_out,
                           float* dpred, void* scratch, void* hip_stream);
+/* focal loss (replaces FocalLoss, reference models/losses.py:70-160): x fp32 NCHW [batch, classes, hw], target int64
+ * [batch*hw], alpha fp32 [classes] on the device (NULL: ones).  flags bit 0: x are logits and the softmax is fused (apply_nonlin =
+ * softmax_helper, dx = d loss / d logits); clear: x are probabilities (dx = d loss / d x).  bit 1: sum instead of mean
+ * (size_average=False).  k = one-hot(label) clamped to [smooth/(classes-1), 1-smooth] (no clamp at smooth == 0),
+ * pt = sum k p + smooth, loss = -alpha[label] (1-pt)^gamma log pt.  Label 225 counts as class 0 (:136); any other label outside
+ * [0, classes) makes the loss and that pixel's gradient NaN.  2 <= classes <= 16.  scratch: >= stcd_loss_scratch_bytes(). */
+int stcd_loss_focal(const float* x, const int64_t* target, int batch, int classes, int64_t hw, const float* alpha, float gamma,
+                    float smooth, int flags, float* loss_out, float* dx, void* scratch, void* hip_stream);
+/* mIoU / min-max IoU (replace mIoULoss :170-206 and mmIoULoss :208-242): p = softmax(logits), t = one-hot(label); per (n, c)
+ * iou = sum p t / (sum (p + t - p t) + 1e-8).  mode 0: loss = -mean(weight_c iou) (weight fp32 [classes] on the device, NULL:
+ * ones); mode 1: loss = -min(iou) - mean(iou), the min's gradient split evenly among tied entries.  A label outside [0, classes)
+ * makes the loss NaN.  2 <= classes <= 16.  scratch: >= stcd_loss_iou_scratch_bytes(batch, classes, hw) bytes (0 for a shape
+ * outside the supported range). */
+int64_t stcd_loss_iou_scratch_bytes(int batch, int classes, int64_t hw);
+int stcd_loss_iou(const float* logits, const int64_t* target, int batch, int classes, int64_t hw, const float* weight, int mode,
+                  float* loss_out, float* dlogits, void* scratch, void* hip_stream);
 /* ---- metric: replaces SegmentationMetric.genConfusionMatrix (train_pse_cd.py:361-368) without the
  *      per-step .cpu() sync (train_pse_cd.py:231).  cm[2*label+pred] += count; cm is 4 int64 on the device.
  *      pred = argmax over classes (classes==2) or logit > 0 (classes==1, i.e. sigmoid > 0.5). */

@@ -121,6 +121,9 @@ _PROTOS = {
     "stcd_loss_ce": (_i, [_vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     "stcd_loss_bce_dice": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "stcd_loss_contrastive": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "stcd_loss_focal": (_i, [_vp, _vp, _i, _i, _i64, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "stcd_loss_iou_scratch_bytes": (_i64, [_i, _i, _i64]),
+    "stcd_loss_iou": (_i, [_vp, _vp, _i, _i, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     "stcd_confusion_update": (_i, [_vp, _vp, _i, _i, _i64, _vp, _vp]),
     "stcd_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _d, _d, _d, _i, _vp]),
     "stcd_adam_hyper": (_i, [_i64, _d, _d, _d, _d, _d, C.POINTER(_f)]),

@@ -563,6 +563,11 @@ void launch_loss_bce_dice(const float* logits, const float* target, int64_t n, i
                           float* dlogits, void* scratch, hipStream_t s);
 void launch_loss_contrastive(const float* pred, const int64_t* cd_label, const int64_t* pse_label, int64_t n_half, float* loss,
                              float* dpred, void* scratch, hipStream_t s);
+void launch_loss_focal(const float* x, const int64_t* target, int B, int Cn, int64_t HW, const float* alpha, float gamma, float smooth,
+                       int flags, float* loss, float* dx, void* scratch, hipStream_t s);
+int64_t iou_scratch_bytes(int B, int Cn, int64_t HW);
+void launch_loss_iou(const float* x, const int64_t* target, int B, int Cn, int64_t HW, const float* weight, int mode, float* loss,
+                     float* dx, void* scratch, hipStream_t s);
 void launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float omb1, float beta2, float omb2, float eps,
                  float wd, int decoupled, float step_size, float inv_bc2_sqrt, hipStream_t s);
 void launch_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, int decoupled, hipStream_t s);

@@ -3182,6 +3182,31 @@ int stcd_loss_contrastive(const float* pred, const int64_t* cd_label, const int6
     STCD_HIP(hipGetLastError());
     return 0;
 }
+int64_t stcd_loss_iou_scratch_bytes(int batch, int classes, int64_t hw) {
+    if (batch < 1 || classes < 2 || classes > 16 || hw < 1) return 0;
+    return iou_scratch_bytes(batch, classes, hw);
+}
+int stcd_loss_focal(const float* x, const int64_t* target, int batch, int classes, int64_t hw, const float* alpha, float gamma,
+                    float smooth, int flags, float* loss_out, float* dx, void* scratch, void* hip_stream) {
+    STCD_CHECK(x && target && loss_out && scratch, "null pointer argument");
+    STCD_CHECK(classes >= 2 && classes <= 16, "classes must be in [2, 16]");
+    STCD_CHECK(batch >= 1 && hw >= 1, "bad shape");
+    STCD_CHECK(smooth >= 0.f && smooth <= 1.f, "smooth must be in [0, 1]");
+    STCD_CHECK(flags >= 0 && flags <= 3, "flags: bit 0 = softmax fused, bit 1 = sum instead of mean");
+    launch_loss_focal(x, target, batch, classes, hw, alpha, gamma, smooth, flags, loss_out, dx, scratch, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_loss_iou(const float* logits, const int64_t* target, int batch, int classes, int64_t hw, const float* weight, int mode,
+                  float* loss_out, float* dlogits, void* scratch, void* hip_stream) {
+    STCD_CHECK(logits && target && loss_out && scratch, "null pointer argument");
+    STCD_CHECK(classes >= 2 && classes <= 16, "classes must be in [2, 16]");
+    STCD_CHECK(batch >= 1 && hw >= 1, "bad shape");
+    STCD_CHECK(mode == 0 || mode == 1, "mode must be 0 (mIoU) or 1 (min-max IoU)");
+    launch_loss_iou(logits, target, batch, classes, hw, weight, mode, loss_out, dlogits, scratch, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
 int stcd_confusion_update(const float* logits, const int64_t* target, int batch, int classes, int64_t hw, int64_t* cm,
                           void* hip_stream) {
     STCD_CHECK(logits && target && cm, "null pointer argument");

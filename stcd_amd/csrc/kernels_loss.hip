@@ -4,8 +4,10 @@
 //   cross_entropy(ignore_index=255)          /root/reference/models/losses.py:6-21
 //   cd_loss(sigmoid(x), y) == BCE_DICE       /root/reference/models/losses.py:24-34; train_pse_cd.py:227-228,436-462
 //   SegmentationMetric.genConfusionMatrix    /root/reference/train_pse_cd.py:361-368
+//   FocalLoss, mIoULoss, mmIoULoss           /root/reference/models/losses.py:70-160, 170-242
 // The reference runs each of these as 3-8 tiny ATen kernels plus a host sync for the metric; here each loss is
-// reduce -> finalize -> gradient (three launches, wave-reduced, no host sync) and the metric is one launch.
+// reduce -> finalize -> gradient (three launches, wave-reduced, no host sync; two for the focal loss, whose gradient needs
+// nothing from the reduction) and the metric is one launch.
 #include "common.h"
 
 namespace stcd {
@@ -224,6 +226,272 @@ void launch_loss_contrastive(const float* pred, const int64_t* cd_label, const i
     k_ct_reduce<<<nb, 256, 0, s>>>(pred, cd_label, pse_label, n_half, sc);
     k_ct_finalize<<<1, 256, 0, s>>>(sc, nb, loss);
     if (dpred) k_ct_grad<<<nb, 256, 0, s>>>(pred, cd_label, pse_label, n_half, sc, dpred);
+}
+
+// ------------------------------------------------------------------ focal loss (reference models/losses.py:70-160)
+// Per pixel, with p = softmax(x) over the classes (flags bit 0) or p = x (the caller passes probabilities):
+//   k = one-hot(label) clamped to [smooth/(C-1), 1-smooth] (no clamp when smooth == 0), pt = sum_c k_c p_c + smooth,
+//   loss = -alpha[label] (1-pt)^gamma log(pt); mean over the pixels, or the sum (flags bit 1).
+// Label 225 counts as class 0 (the reference's idx[idx==225]=0); any other label outside [0, C) poisons the loss and that
+// pixel's gradient with NaN and is never dereferenced.  The gradient of a pixel needs nothing from the reduction (the 1/npix of
+// the mean is known on the host), so value partials and gradient come from ONE pass; the finalize sums the partials in a fixed
+// order.  CM: the class count rounded up to a power of two, so the per-pixel class vector stays in registers.
+template <int CM>
+__global__ void __launch_bounds__(256)
+k_fl_reduce_grad(const float* __restrict__ x, const int64_t* __restrict__ target, int Cn, int64_t HW, int64_t npix,
+                 const float* __restrict__ alpha, float gamma, float smooth, int flags, float gscale, LossScratch* sc,
+                 float* __restrict__ dx) {
+    __shared__ double sm[4];
+    double v[1] = {0.0};
+    const float lo = smooth / (float)(Cn - 1), hi = 1.f - smooth;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t t = target[i];
+        const int64_t n = i / HW, q = i - n * HW;
+        const float* xp = x + n * Cn * HW + q;
+        float* dp = dx ? dx + n * Cn * HW + q : nullptr;
+        if (t == 225) t = 0;
+        if (t < 0 || t >= Cn) {
+            v[0] += (double)NAN;
+            if (dp)
+                for (int c = 0; c < Cn; ++c) dp[(int64_t)c * HW] = NAN;
+            continue;
+        }
+        float p[CM], k[CM];
+#pragma unroll
+        for (int c = 0; c < CM; ++c) p[c] = c < Cn ? xp[(int64_t)c * HW] : 0.f;
+        if (flags & 1) {
+            float mx = p[0];
+#pragma unroll
+            for (int c = 1; c < CM; ++c) if (c < Cn) mx = fmaxf(mx, p[c]);
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < CM; ++c) if (c < Cn) { p[c] = expf(p[c] - mx); se += p[c]; }
+#pragma unroll
+            for (int c = 0; c < CM; ++c) p[c] = p[c] / se;
+        }
+        float sk = 0.f;
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+            k[c] = c == t ? 1.f : 0.f;
+            if (smooth != 0.f) k[c] = fminf(fmaxf(k[c], lo), hi);      // torch.clamp(min, max) order
+            if (c < Cn) sk += k[c] * p[c];
+        }
+        const float pt = sk + smooth, om = 1.f - pt, lpt = logf(pt), a = alpha ? alpha[t] : 1.f;
+        const float pw = powf(om, gamma);
+        v[0] += (double)(-a * pw * lpt);
+        if (dp) {
+            // d loss / d pt = a (gamma (1-pt)^(gamma-1) log pt - (1-pt)^gamma / pt); torch's pow backward is 0 at gamma == 0
+            const float dpw = gamma == 0.f ? 0.f : gamma * powf(om, gamma - 1.f);
+            const float g = a * (dpw * lpt - pw / pt) * gscale;
+#pragma unroll
+            for (int c = 0; c < CM; ++c)
+                if (c < Cn) dp[(int64_t)c * HW] = (flags & 1) ? g * p[c] * (k[c] - sk) : g * k[c];   // softmax Jacobian: p (k - p.k)
+        }
+    }
+    block_sum4(v, sm);
+    if (threadIdx.x == 0) sc->part[blockIdx.x][0] = v[0];
+}
+__global__ void k_sum_finalize(LossScratch* sc, int nblocks, double scale, float* loss) {
+    __shared__ double sm[4];
+    double v[1] = {0.0};
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) v[0] += sc->part[b][0];
+    block_sum4(v, sm);
+    if (threadIdx.x == 0) {
+        sc->fin[0] = v[0];
+        *loss = (float)(v[0] * scale);
+    }
+}
+void launch_loss_focal(const float* x, const int64_t* target, int B, int Cn, int64_t HW, const float* alpha, float gamma, float smooth,
+                       int flags, float* loss, float* dx, void* scratch, hipStream_t s) {
+    LossScratch* sc = (LossScratch*)scratch;
+    const int64_t npix = (int64_t)B * HW;
+    const int nb = (int)std::min<int64_t>(LOSS_BLOCKS, (npix + 255) / 256);
+    const double scale = (flags & 2) ? 1.0 : 1.0 / (double)npix;
+    const float gs = (float)scale;
+    if (Cn <= 2) k_fl_reduce_grad<2><<<nb, 256, 0, s>>>(x, target, Cn, HW, npix, alpha, gamma, smooth, flags, gs, sc, dx);
+    else if (Cn <= 4) k_fl_reduce_grad<4><<<nb, 256, 0, s>>>(x, target, Cn, HW, npix, alpha, gamma, smooth, flags, gs, sc, dx);
+    else if (Cn <= 8) k_fl_reduce_grad<8><<<nb, 256, 0, s>>>(x, target, Cn, HW, npix, alpha, gamma, smooth, flags, gs, sc, dx);
+    else k_fl_reduce_grad<16><<<nb, 256, 0, s>>>(x, target, Cn, HW, npix, alpha, gamma, smooth, flags, gs, sc, dx);
+    k_sum_finalize<<<1, 256, 0, s>>>(sc, nb, scale, loss);
+}
+
+// ------------------------------------------------------------------ mIoU / min-max IoU (reference models/losses.py:170-242)
+// p = softmax(logits), t = one-hot(label); per (n, c): I = sum p t, U = sum (p + t - p t) (= 1 where t == c, p elsewhere);
+// iou = I / (U + 1e-8).  mIoU: loss = -mean_{n,c}(w_c iou); min-max: loss = -min_{n,c}(iou) - mean_{n,c}(iou), the min's gradient
+// split evenly among tied entries (torch's full-reduction min() backward).  Pass 1 writes double partials per (n, chunk of HW) with
+// the chunking a function of HW alone: identical samples give bit-identical sums, so a tie between samples is exact.  The finalize
+// (one block) sums each (n, c) over its chunks in index order and writes dL/dI and dL/dU per (n, c); pass 3 recomputes p and
+// writes dlogits = p (g - p.g) with g_c = dL/dI (c == label) or dL/dU (c != label).  A label outside [0, C): NaN.
+struct IouLayout {
+    int64_t per, chunks;           // pixels per chunk (a multiple of 1024), chunks per sample (<= 128)
+    size_t part_off, stat_off, coef_off, bytes;
+};
+static IouLayout iou_layout(int B, int Cn, int64_t HW) {
+    IouLayout L;
+    L.per = 1024 * std::max<int64_t>(1, (HW + 1024 * 128 - 1) / (1024 * 128));
+    L.chunks = (HW + L.per - 1) / L.per;
+    L.part_off = 0;                                                              // double [B][chunks][2][Cn]
+    L.stat_off = L.part_off + (size_t)B * L.chunks * 2 * Cn * sizeof(double);    // double [B*Cn][3]: I, U, iou
+    L.coef_off = L.stat_off + (size_t)B * Cn * 3 * sizeof(double);              // float [B*Cn][2]: dL/dI, dL/dU
+    L.bytes = L.coef_off + (size_t)B * Cn * 2 * sizeof(float) + 16;
+    return L;
+}
+int64_t iou_scratch_bytes(int B, int Cn, int64_t HW) { return (int64_t)iou_layout(B, Cn, HW).bytes; }
+
+template <int CM>
+__device__ __forceinline__ void iou_softmax(const float* __restrict__ xp, int Cn, int64_t HW, float (&p)[CM]) {
+#pragma unroll
+    for (int c = 0; c < CM; ++c) p[c] = c < Cn ? xp[(int64_t)c * HW] : 0.f;
+    float mx = p[0];
+#pragma unroll
+    for (int c = 1; c < CM; ++c) if (c < Cn) mx = fmaxf(mx, p[c]);
+    float se = 0.f;
+#pragma unroll
+    for (int c = 0; c < CM; ++c) if (c < Cn) { p[c] = expf(p[c] - mx); se += p[c]; }
+#pragma unroll
+    for (int c = 0; c < CM; ++c) p[c] = p[c] / se;
+}
+
+template <int CM>
+__global__ void __launch_bounds__(256)
+k_iou_reduce(const float* __restrict__ x, const int64_t* __restrict__ target, int Cn, int64_t HW, int64_t per, double* __restrict__ part) {
+    __shared__ double sm[4 * 2 * CM];
+    const int n = blockIdx.y, ch = blockIdx.x;
+    double v[2 * CM];
+#pragma unroll
+    for (int k = 0; k < 2 * CM; ++k) v[k] = 0.0;
+    const float* xn = x + (int64_t)n * Cn * HW;
+    const int64_t* tn = target + (int64_t)n * HW;
+    const int64_t q1 = std::min<int64_t>(HW, (int64_t)(ch + 1) * per);
+    for (int64_t q = (int64_t)ch * per + threadIdx.x; q < q1; q += blockDim.x) {
+        const int64_t t = tn[q];
+        if (t < 0 || t >= Cn) {
+            v[0] += (double)NAN;
+            continue;
+        }
+        float p[CM];
+        iou_softmax<CM>(xn + q, Cn, HW, p);
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+            if (c == t) { v[c] += (double)p[c]; v[CM + c] += 1.0; }
+            else v[CM + c] += (double)p[c];
+        }
+    }
+    block_sum4(v, sm);
+    if (threadIdx.x == 0) {
+        double* o = part + ((int64_t)n * gridDim.x + ch) * 2 * Cn;
+        for (int c = 0; c < Cn; ++c) { o[c] = v[c]; o[Cn + c] = v[CM + c]; }
+    }
+}
+__global__ void __launch_bounds__(256)
+k_iou_finalize(const double* __restrict__ part, int B, int Cn, int chunks, const float* __restrict__ weight, int mode,
+               double* __restrict__ stat, float* __restrict__ coef, float* __restrict__ loss) {
+    __shared__ double sm[8];
+    __shared__ double s_min, s_cnt;
+    const int nc = B * Cn, lane = threadIdx.x & 63;
+    // one wave per (n, c): lane l sums chunks l, l+64, ..., then a fixed butterfly -- the same order for every (n, c)
+    for (int j = threadIdx.x >> 6; j < nc; j += blockDim.x >> 6) {
+        const int n = j / Cn, c = j - n * Cn;
+        double I = 0.0, U = 0.0;
+        for (int ch = lane; ch < chunks; ch += 64) {
+            const double* o = part + ((int64_t)n * chunks + ch) * 2 * Cn;
+            I += o[c]; U += o[Cn + c];
+        }
+        I = wave_sum_d(I); U = wave_sum_d(U);
+        if (lane == 0) { stat[3 * j] = I; stat[3 * j + 1] = U; stat[3 * j + 2] = I / (U + 1e-8); }
+    }
+    __syncthreads();                            // stat is read below by other threads of the block
+    double v[2] = {0.0, 0.0};                   // sum w iou (mIoU) or sum iou (min-max); count of tied minima (second pass)
+    double mn = INFINITY;
+    for (int j = threadIdx.x; j < nc; j += blockDim.x) {
+        const double iou = stat[3 * j + 2];
+        v[0] += (mode == 0 && weight) ? (double)weight[j % Cn] * iou : iou;
+        mn = fmin(mn, iou);
+    }
+    // min over the block (fmin is order-free); a NaN entry already poisons the mean, hence the loss
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
+    if ((threadIdx.x & 63) == 0) sm[4 + (threadIdx.x >> 6)] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = sm[4];
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = fmin(m, sm[4 + w]);
+        s_min = m;
+    }
+    __syncthreads();
+    const double gmin = s_min;
+    for (int j = threadIdx.x; j < nc; j += blockDim.x) v[1] += stat[3 * j + 2] == gmin ? 1.0 : 0.0;
+    __syncthreads();                            // sm is reused by the sums below
+    block_sum4(v, sm);
+    if (threadIdx.x == 0) {
+        s_cnt = v[1];
+        const double mean = v[0] / (double)nc;
+        *loss = (float)(mode == 0 ? -mean : -gmin - mean);
+    }
+    __syncthreads();
+    const double cnt = s_cnt;
+    for (int j = threadIdx.x; j < nc; j += blockDim.x) {
+        const int c = j % Cn;
+        const double I = stat[3 * j], den = stat[3 * j + 1] + 1e-8, iou = stat[3 * j + 2];
+        double d = mode == 0 ? -(weight ? (double)weight[c] : 1.0) / (double)nc
+                             : -1.0 / (double)nc - (iou == gmin ? 1.0 / cnt : 0.0);
+        coef[2 * j] = (float)(d / den);                 // dL/dI
+        coef[2 * j + 1] = (float)(-d * I / (den * den)); // dL/dU
+    }
+}
+template <int CM>
+__global__ void __launch_bounds__(256)
+k_iou_grad(const float* __restrict__ x, const int64_t* __restrict__ target, int Cn, int64_t HW, int64_t per, const float* __restrict__ coef,
+           float* __restrict__ dx) {
+    const int n = blockIdx.y, ch = blockIdx.x;
+    float gi[CM], gu[CM];
+#pragma unroll
+    for (int c = 0; c < CM; ++c) {
+        gi[c] = c < Cn ? coef[2 * (n * Cn + c)] : 0.f;
+        gu[c] = c < Cn ? coef[2 * (n * Cn + c) + 1] : 0.f;
+    }
+    const float* xn = x + (int64_t)n * Cn * HW;
+    float* dn = dx + (int64_t)n * Cn * HW;
+    const int64_t* tn = target + (int64_t)n * HW;
+    const int64_t q1 = std::min<int64_t>(HW, (int64_t)(ch + 1) * per);
+    for (int64_t q = (int64_t)ch * per + threadIdx.x; q < q1; q += blockDim.x) {
+        const int64_t t = tn[q];
+        if (t < 0 || t >= Cn) {
+            for (int c = 0; c < Cn; ++c) dn[(int64_t)c * HW + q] = NAN;
+            continue;
+        }
+        float p[CM], g[CM];
+        iou_softmax<CM>(xn + q, Cn, HW, p);
+        float pg = 0.f;
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+            g[c] = c == t ? gi[c] : gu[c];
+            pg += p[c] * g[c];
+        }
+#pragma unroll
+        for (int c = 0; c < CM; ++c)
+            if (c < Cn) dn[(int64_t)c * HW + q] = p[c] * (g[c] - pg);
+    }
+}
+template <int CM>
+static void launch_iou_cm(const float* x, const int64_t* target, int B, int Cn, int64_t HW, const float* weight, int mode, float* loss,
+                          float* dx, char* scratch, const IouLayout& L, hipStream_t s) {
+    double* part = (double*)(scratch + L.part_off);
+    double* stat = (double*)(scratch + L.stat_off);
+    float* coef = (float*)(scratch + L.coef_off);
+    const dim3 grid((unsigned)L.chunks, (unsigned)B);
+    k_iou_reduce<CM><<<grid, 256, 0, s>>>(x, target, Cn, HW, L.per, part);
+    k_iou_finalize<<<1, 256, 0, s>>>(part, B, Cn, (int)L.chunks, weight, mode, stat, coef, loss);
+    if (dx) k_iou_grad<CM><<<grid, 256, 0, s>>>(x, target, Cn, HW, L.per, coef, dx);
+}
+void launch_loss_iou(const float* x, const int64_t* target, int B, int Cn, int64_t HW, const float* weight, int mode, float* loss,
+                     float* dx, void* scratch, hipStream_t s) {
+    const IouLayout L = iou_layout(B, Cn, HW);
+    char* sc = (char*)scratch;
+    if (Cn <= 2) launch_iou_cm<2>(x, target, B, Cn, HW, weight, mode, loss, dx, sc, L, s);
+    else if (Cn <= 4) launch_iou_cm<4>(x, target, B, Cn, HW, weight, mode, loss, dx, sc, L, s);
+    else if (Cn <= 8) launch_iou_cm<8>(x, target, B, Cn, HW, weight, mode, loss, dx, sc, L, s);
+    else launch_iou_cm<16>(x, target, B, Cn, HW, weight, mode, loss, dx, sc, L, s);
 }
 
 // ------------------------------------------------------------------ 2x2 confusion matrix: cm[2*label+pred] += count

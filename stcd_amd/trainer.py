@@ -132,8 +132,20 @@ class CDTrainer:
             self._pxl_loss = F.binary_cross_entropy
         elif args.loss == "cd_loss":
             self._pxl_loss = losses.cd_loss
-        elif args.loss in ("fl", "miou", "mmiou"):
-            raise NotImplementedError("loss '%s' is outside the accelerated hot path of this build" % args.loss)
+        elif args.loss == "fl":
+            self.logger.write("\n Calculating alpha in Focal-Loss (FL) ...\n")
+            alpha = losses.get_alpha(dataloaders["train"])        # class occurrences
+            self.logger.write(f"alpha-0 (no-change)={alpha[0]}, alpha-1 (change)={alpha[1]}\n")
+            self._pxl_loss = losses.FocalLoss(apply_nonlin=losses.softmax_helper, alpha=alpha, gamma=2, smooth=1e-5)
+        elif args.loss == "miou":
+            self.logger.write("\n Calculating class occurrences in training set...\n")
+            alpha = np.asarray(losses.get_alpha(dataloaders["train"]))
+            alpha = alpha / np.sum(alpha)
+            weights = 1 - torch.from_numpy(alpha).to(self.device)
+            self.logger.write(f"Weights = {weights}\n")
+            self._pxl_loss = losses.mIoULoss(weight=weights, size_average=True, n_classes=args.n_class)
+        elif args.loss == "mmiou":
+            self._pxl_loss = losses.mmIoULoss(n_classes=args.n_class)
         else:
             raise NotImplementedError(args.loss)
         self.VAL_ACC = np.array([], np.float32)
