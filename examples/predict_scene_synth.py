@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""Whole-scene inference on the HIP engine: two co-registered uint8 scenes in, one change mask and its scores out.
+
+The reference crops its scenes into 256-pixel tiles offline (/root/reference/split.py:17-46) and its test-time evaluator
+(models/evaluator.py) does not run; ``stcd_amd.scene.predict_scene`` tiles, normalises, predicts and stitches on the device.
+The scene is synthetic (stcd_amd.synth); with ``--load_path`` the weights of a trained ``SiamUnet_diff`` are used, otherwise the
+scores are those of a randomly initialised network and only show the plumbing.
+
+    python examples/predict_scene_synth.py --size 1024 --tile 256 --stride 128 --window hann
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch
+
+from stcd_amd import synth
+from stcd_amd.modules import SiamUnet_diff
+from stcd_amd.scene import plan_tiles, predict_scene
+
+parser = argparse.ArgumentParser()
+parser.add_argument("--size", type=int, default=1024, help="scene edge in pixels (LEVIR-CD scenes are 1024 x 1024)")
+parser.add_argument("--tile", type=int, default=256)
+parser.add_argument("--stride", type=int, default=128, help="<= tile; tile = no overlap")
+parser.add_argument("--batch", type=int, default=16)
+parser.add_argument("--window", type=str, default="hann", choices=("flat", "hann"))
+parser.add_argument("--load_path", type=str, default="", help="state_dict of a trained SiamUnet_diff(3, 2)")
+parser.add_argument("--seed", type=int, default=7)
+
+
+def main(argv=None):
+    args = parser.parse_args(argv)
+    assert torch.cuda.is_available(), "the engine needs a GPU (no CPU fallback)"
+    dev = torch.device("cuda:0")
+    a, b, label = synth.make_pairs_u8(1, args.size, args.size, args.seed)          # uint8 [1,H,W,3] x 2, uint8 [1,H,W] in {0,1}
+    scene_a, scene_b, label = (torch.from_numpy(v[0]).to(dev) for v in (a, b, label))
+
+    torch.manual_seed(args.seed)
+    model = SiamUnet_diff(3, 2)
+    if args.load_path:
+        model.load_state_dict(torch.load(args.load_path, map_location="cpu"))
+    model.to(dev)
+
+    plan = plan_tiles(args.size, args.size, args.tile, args.stride)
+    t0 = time.perf_counter()
+    res = predict_scene(model, scene_a, scene_b, tile=args.tile, stride=args.stride, batch=args.batch, window=args.window,
+                        label=label, return_prob=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    s = res.scores
+    print(f"{args.size} x {args.size} scene, {plan.tiles_y} x {plan.tiles_x} tiles of {plan.tile} at stride {plan.stride} ({args.window}): "
+          f"{dt * 1e3:.1f} ms including the first-call set-up")
+    print(f"change pixels predicted {int(res.mask.sum())} / labelled {int((label >= 1).sum())}; mean change probability {float(res.prob.mean()):.4f}")
+    print(f"confusion matrix [label, pred]: {res.cm.tolist()}")
+    print(f"OA {s['oa']:.4f}  precision {s['precision'][1]:.4f}  recall {s['recall'][1]:.4f}  F1 {s['f1'][1]:.4f}  IoU {s['iou'][1]:.4f}")
+    return res
+
+
+if __name__ == "__main__":
+    main()

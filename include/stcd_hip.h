@@ -313,6 +313,40 @@ int64_t stcd_augment_scratch_bytes(int n_images, int height, int width);
 int stcd_augment(const float* x, const float* params, int n_images, int height, int width, const float* mean3, const float* std3,
                  float* out, void* scratch, int64_t scratch_bytes, void* hip_stream);
 
+/* ---- whole-scene inference: tile two co-registered uint8 scenes, run the network on the tiles, put the logits back together.
+ *      Three entries that share one regular tile grid: scene height x width, tile edge T, stride S (1 <= S <= T),
+ *      tiles_y = max(0, ceil((height - T) / S)) + 1, likewise tiles_x; tile k has ky = k / tiles_x, kx = k % tiles_x and origin
+ *      (ky * S, kx * S).  A tile may reach past the bottom / right edge and a scene may be smaller than one tile.  Every entry
+ *      works on the tiles [first_tile, first_tile + n_tiles) (n_tiles == 0: nothing is launched); tiles_x / tiles_y must be the
+ *      values above.  All indices are 64-bit inside: classes * height * width may pass 2^31. */
+/* Replaces the offline 256-pixel crops of split.py:17-46 and the host ToTensor + Normalize of data/dataset.py:499-500.
+ * scene_a, scene_b: uint8 [height,width,3] (HWC, device) -> x1, x2: fp32 [n_tiles,3,T,T] normalised, ready for the forward.
+ * A tile pixel outside the scene reads the scene by mirror reflection without repeating the edge sample
+ * (m = 2*(L-1); i = ((i % m) + m) % m; i = i >= L ? m - i : i; L == 1 -> 0): the reference pads nothing, this is the library's
+ * own rule.  Value arithmetic is stcd_pseudo_pair's: (u * (1.f/255.f) - mean[c]) * (1.f/std[c]) (host mean3 / std3). */
+int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                      int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, void* hip_stream);
+/* The overlap blend; the reference has none (it scores crops one by one), so this is the library's own specification.
+ * logits: fp32 [n_tiles,classes,T,T] (classes 1 or 2) of tiles [first_tile, first_tile + n_tiles) are added into acc fp32
+ * [classes,height,width] and wsum fp32 [height,width], both zeroed by the caller before the first call.  window: nullable
+ * fp32 [T] (NULL = all ones); pixel weight w = window[ty] * window[tx]; tile pixels outside the scene are dropped.
+ * A gather over scene pixels, without float atomics: each pixel adds its covering tiles of this call in ASCENDING tile index,
+ * acc = fmaf(w, logit, acc), wsum += w.  Hence the same inputs give the same bits on every run, and acc / wsum do not depend
+ * on how the tiles were split into calls as long as the calls come in ascending first_tile. */
+int stcd_scene_stitch(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                      int first_tile, int n_tiles, const float* window, float* acc, float* wsum, void* hip_stream);
+/* Replaces the arg-max / threshold of models/trainer.py:197-203 and, with a label, SegmentationMetric.genConfusionMatrix
+ * (train_pse_cd.py:361-368) on the whole scene.  mask: uint8 [height,width].  classes == 2: acc[1] > acc[0] (a tie is class 0,
+ * as torch.argmax takes the first maximum).  classes == 1: acc[0] > threshold * wsum, i.e. the blended raw output above
+ * `threshold`: 0 is "sigmoid > 0.5" (stcd_confusion_update, train_pse_cd.py); 0.5 is CDTrainer's n_class == 1 rule on the raw
+ * output (trainer.py:200-203) EXCEPT that the reference compares with >= and this entry with >: a value exactly on the
+ * threshold is class 0 here.  The mask needs no division; every pixel must have wsum > 0 (true after all tiles were stitched
+ * with a positive window).  prob: nullable fp32 [height,width], softmax class 1 (classes == 2) or sigmoid (classes == 1) of
+ * acc / wsum.  label: nullable uint8 [height,width] (>= 1 is change, 255 is ignored) together with cm: int64 [4] on the
+ * device, cm[2*label+pred] += count as stcd_confusion_update does; both or neither. */
+int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold,
+                        const uint8_t* label, uint8_t* mask, float* prob, int64_t* cm, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

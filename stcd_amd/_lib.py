@@ -131,6 +131,9 @@ _PROTOS = {
     "stcd_pseudo_pair": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp]),
     "stcd_augment_scratch_bytes": (_i64, [_i, _i, _i]),
     "stcd_augment": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _i64, _vp]),
+    "stcd_scene_gather": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _vp]),
+    "stcd_scene_stitch": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "stcd_scene_finalize": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_scratch_bytes": (_i64, [C.POINTER(ConvGeom)]),

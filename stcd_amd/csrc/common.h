@@ -579,6 +579,13 @@ void launch_augment(const float* x, const float* params, int N, int H, int W, co
 int64_t augment_scratch_bytes(int N, int H, int W);
 void launch_confusion(const float* logits, const int64_t* target, int B, int Cn, int64_t HW, int64_t* cm,
                       hipStream_t s);
+// whole-scene inference (kernels_scene.hip): the callers have validated the tile grid and the tile range
+void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                         const float* mean, const float* std_, float* x1, float* x2, hipStream_t s);
+void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
+                         const float* window, float* acc, float* wsum, hipStream_t s);
+void launch_scene_finalize(const float* acc, const float* wsum, int classes, int H, int W, float threshold, const uint8_t* label,
+                           uint8_t* mask, float* prob, int64_t* cm, hipStream_t s);
 
 // ---- ChangeFormer (transformer) kernels, kernels_tf.hip.  Tokens are NHWC pixels: a [n, N = h*w, C] sequence IS the
 //      [n, h, w, C] map.  Every Dropout / DropPath site draws its mask from a counter hash of (site seed, element index in the

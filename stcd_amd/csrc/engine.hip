@@ -3275,6 +3275,50 @@ int stcd_augment(const float* x, const float* params, int n_images, int height, 
     return 0;
 }
 
+// tiles per axis of the regular grid: max(0, ceil((L - T) / S)) + 1
+static int scene_tiles(int L, int T, int S) { return (L > T ? (int)(((int64_t)L - T + S - 1) / S) : 0) + 1; }
+static int check_scene_grid(int height, int width, int tile, int stride, int tiles_x, int tiles_y, int first_tile, int n_tiles) {
+    STCD_CHECK(height >= 1 && width >= 1 && tile >= 1, "bad shape");
+    STCD_CHECK(stride >= 1 && stride <= tile, "stride must be in [1, tile]");
+    STCD_CHECK(tiles_x == scene_tiles(width, tile, stride), "tiles_x is not max(0, ceil((width - tile) / stride)) + 1");
+    STCD_CHECK(tiles_y == scene_tiles(height, tile, stride), "tiles_y is not max(0, ceil((height - tile) / stride)) + 1");
+    STCD_CHECK((int64_t)tiles_x * tiles_y < ((int64_t)1 << 31), "more than 2^31 tiles");
+    STCD_CHECK(first_tile >= 0 && n_tiles >= 0 && (int64_t)first_tile + n_tiles <= (int64_t)tiles_x * tiles_y,
+               "tile range outside [0, tiles_x * tiles_y)");
+    return 0;
+}
+int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                      int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, void* hip_stream) {
+    STCD_CHECK(scene_a && scene_b && mean3 && std3 && x1 && x2, "null pointer argument");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
+        return 1;
+    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
+    launch_scene_gather(scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2,
+                        (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_scene_stitch(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                      int first_tile, int n_tiles, const float* window, float* acc, float* wsum, void* hip_stream) {
+    STCD_CHECK(logits && acc && wsum, "null pointer argument");
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
+    launch_scene_stitch(logits, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
+                        (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold, const uint8_t* label,
+                        uint8_t* mask, float* prob, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(acc && wsum && mask, "null pointer argument");
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    STCD_CHECK(height >= 1 && width >= 1, "bad shape");
+    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
+    launch_scene_finalize(acc, wsum, classes, height, width, threshold, label, mask, prob, cm, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_geom(const stcd_conv_geom* g) {
     STCD_CHECK(g != nullptr, "geometry is null");
     STCD_CHECK(g->ntaps >= 1 && g->ntaps <= 9, "ntaps must be in [1,9]");
