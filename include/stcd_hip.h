@@ -347,6 +347,26 @@ int stcd_scene_stitch(const float* logits, int classes, int height, int width, i
 int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold,
                         const uint8_t* label, uint8_t* mask, float* prob, int64_t* cm, void* hip_stream);
 
+/* ---- the self-training round: K checkpoints of one network score the same pairs.  Replaces, per pair and checkpoint, the sigmoid,
+ *      the compare, the .int(), the .cpu() and the host bincount of train_stcd.py:111-125 (reliability split) and :155-177
+ *      (pseudo-label writer) by one launch that reads every logit once and writes one byte per pixel.
+ * logits: HOST array of n_models device pointers (1 <= n_models <= STCD_SELFTRAIN_MAX_MODELS; the kernel takes them by value),
+ * each fp32 [batch,classes,hw]: the raw change output of one checkpoint for the same `batch` pairs; classes 1 or 2.
+ * Prediction of model k at a pixel: classes == 1: x > threshold (0 is the reference's "sigmoid > 0.5", the rule of
+ * stcd_confusion_update and stcd_scene_finalize; a value exactly on the threshold is class 0); classes == 2: x[1] > x[0] (a tie
+ * is class 0, as torch.argmax takes the first maximum).  NaN compares false: class 0.
+ * mask: uint8 [batch,hw], the LAST model's prediction: mask_value (1..255) where change, else 0.
+ * agree: int64 [batch][n_models-1][4] on the device, agree[b][i][2*last + pred_i] += count over the pixels of pair b: the matrix the
+ * reference forms with metric.addBatch(preds[i], preds[-1]) (:120; the later checkpoint plays the label).  NULL iff n_models == 1.
+ * label / cm: both or neither; label uint8 [batch,hw] (>= 1 is change, 255 is ignored), cm int64 [4] on the device,
+ * cm[2*label + pred_last] += count as stcd_confusion_update does.
+ * Counts are integers, reduced per wave and block before one 64-bit atomic per block and cell: every output is a pure function of
+ * the inputs.  16-byte loads when hw % 4 == 0 and the pointers allow it, a scalar path otherwise; 64-bit indices inside
+ * (batch * classes * hw may pass 2^31).  batch == 0 or hw == 0 launches nothing.  Arguments are checked before any HIP call. */
+#define STCD_SELFTRAIN_MAX_MODELS 8
+int stcd_selftrain_score(const float* const* logits, int n_models, int batch, int classes, int64_t hw, float threshold,
+                         const uint8_t* label, int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

@@ -586,6 +586,11 @@ void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, 
                          const float* window, float* acc, float* wsum, hipStream_t s);
 void launch_scene_finalize(const float* acc, const float* wsum, int classes, int H, int W, float threshold, const uint8_t* label,
                            uint8_t* mask, float* prob, int64_t* cm, hipStream_t s);
+// the self-training round (kernels_selftrain.hip): the caller has validated every argument; the device pointers of the checkpoints'
+// logits travel by value as a kernel argument
+struct SelftrainPtrs { const float* p[STCD_SELFTRAIN_MAX_MODELS]; };
+void launch_selftrain_score(const SelftrainPtrs& lg, int n_models, int batch, int classes, int64_t hw, float threshold, const uint8_t* label,
+                            int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, hipStream_t s);
 
 // ---- ChangeFormer (transformer) kernels, kernels_tf.hip.  Tokens are NHWC pixels: a [n, N = h*w, C] sequence IS the
 //      [n, h, w, C] map.  Every Dropout / DropPath site draws its mask from a counter hash of (site seed, element index in the

@@ -3319,6 +3319,26 @@ int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int he
     return 0;
 }
 
+int stcd_selftrain_score(const float* const* logits, int n_models, int batch, int classes, int64_t hw, float threshold, const uint8_t* label,
+                         int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(logits && mask, "null pointer argument");
+    STCD_CHECK(n_models >= 1 && n_models <= STCD_SELFTRAIN_MAX_MODELS, "n_models must be in [1, 8]");
+    SelftrainPtrs lg{};
+    for (int k = 0; k < n_models; ++k) {
+        STCD_CHECK(logits[k] != nullptr, "a logits pointer is null");
+        lg.p[k] = logits[k];
+    }
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    STCD_CHECK(batch >= 0 && hw >= 0, "bad shape");
+    STCD_CHECK(mask_value >= 1 && mask_value <= 255, "mask_value must be in [1, 255]");
+    STCD_CHECK((agree == nullptr) == (n_models == 1), "agree is NULL if and only if n_models == 1");
+    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
+    if (batch == 0 || hw == 0) return 0;
+    launch_selftrain_score(lg, n_models, batch, classes, hw, threshold, label, mask_value, mask, agree, cm, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_geom(const stcd_conv_geom* g) {
     STCD_CHECK(g != nullptr, "geometry is null");
     STCD_CHECK(g->ntaps >= 1 && g->ntaps <= 9, "ntaps must be in [1,9]");

@@ -1,0 +1,314 @@
+"""The self-training round between two trainings: reliability split and pseudo-labels, on the device.
+
+In the reference this is /root/reference/train_stcd.py:96-204.  K saved checkpoints predict every training pair; the IoU of the
+change class between each earlier checkpoint's mask and the last checkpoint's mask is averaged into a per-pair reliability; the
+upper half of the sorted pairs goes to ``list/reliable_ids.txt``, the rest to ``list/unreliable_ids.txt`` (:96-135).  Then the
+model predicts every pair of such a list, the mask times 255 is saved under ``pseudo_label/`` and the scores of the change class
+against the true labels are printed (:137-204).  The reference does both with batch size 1 and, per pair and checkpoint, a
+sigmoid, a compare, an ``.int()``, a ``.cpu()`` and a host ``bincount``; here one launch of ``stcd_selftrain_score`` per batch
+(include/stcd_hip.h) takes the raw outputs of all checkpoints and leaves the mask and integer counts on the device, and the
+drivers copy back once per ``flush`` batches.
+
+``reliability``, ``split_reliable`` and ``write_lists`` are host-only and need no GPU.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import os
+from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import StcdError
+from .metrics import scores_from_cm
+from .scene import _change_logits
+
+MAX_MODELS = 8
+
+
+class BatchScore(NamedTuple):
+    mask: torch.Tensor                  # uint8 [B,H,W] on the device: the LAST model's prediction, mask_value where change
+    agree: Optional[torch.Tensor]       # int64 [B,K-1,2,2] on the device, agree[b, i, last, pred_i]; None for one model
+    cm: Optional[torch.Tensor]          # int64 [4] on the device, cm[2 * label + pred_last] (label given)
+
+
+class Selection(NamedTuple):
+    reliable: List[str]
+    unreliable: List[str]
+    names: List[str]                    # every pair, in processing order
+    reliability: np.ndarray             # float64 [N], aligned with names
+    agree: np.ndarray                   # int64 [N,K-1,2,2]
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _model_list(models) -> list:
+    models = [models] if isinstance(models, torch.nn.Module) else list(models)
+    if not 1 <= len(models) <= MAX_MODELS:
+        raise StcdError(f"between 1 and {MAX_MODELS} models, got {len(models)}")
+    for m in models:
+        if not isinstance(m, torch.nn.Module):
+            raise StcdError(f"a model must be a torch module, got {type(m).__name__}")
+    return models
+
+
+def _device_of(models) -> torch.device:
+    dev = None
+    for m in models:
+        prm = next(iter(m.parameters()), None)
+        if prm is None or not prm.is_cuda:
+            raise StcdError("the self-training round runs on the GPU: move every model there first (no CPU fallback)")
+        if dev is not None and prm.device != dev:
+            raise StcdError(f"the models sit on different devices: {dev} and {prm.device}")
+        dev = prm.device
+    return dev
+
+
+@contextlib.contextmanager
+def _evaluating(models):
+    """eval(), no_grad and frozen_weights for every model; the previous modes come back on exit, also on error."""
+    from .modules import frozen_weights
+    was = [m.training for m in models]
+    try:
+        with contextlib.ExitStack() as stack:
+            stack.enter_context(torch.no_grad())
+            for m in models:
+                m.eval()
+                stack.enter_context(frozen_weights(m))
+            yield
+    finally:
+        for m, w in zip(models, was):
+            m.train(w)
+
+
+def score_batch(models, x1: torch.Tensor, x2: torch.Tensor, label: Optional[torch.Tensor] = None, threshold: float = 0.0,
+                mask_value: int = 1, cm: Optional[torch.Tensor] = None) -> BatchScore:
+    """Every model of ``models`` (1..8 modules on one GPU: engine families, ``SegCD``, ``ChangeFormerV6`` or any torch module that
+    maps two ``[B,3,H,W]`` fp32 batches to ``[B,1|2,H,W]`` logits, or to a list / tuple whose last element is that) predicts the
+    batch in ``eval()`` mode under ``torch.no_grad()`` and ``frozen_weights``; the previous modes are restored on exit.  One launch
+    then turns the K raw outputs into the last model's mask, the agreement of every earlier model with it and, with a ``label``
+    (uint8 ``[B,H,W]``, >= 1 is change, 255 is ignored), the confusion matrix of the last model.  One-class models predict change
+    where the raw output is above ``threshold`` (0 is the reference's ``sigmoid > 0.5``), two-class models where class 1 wins.
+    A ``cm`` passed in (int64 ``[4]`` on the device) is accumulated into.  Everything stays on the device; nothing synchronises."""
+    models = _model_list(models)
+    dev = _device_of(models)
+    for name, x in (("x1", x1), ("x2", x2)):
+        if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4:
+            raise StcdError(f"{name} must be an fp32 [B,C,H,W] tensor")
+        if x.device != dev:
+            raise StcdError(f"{name} is on {x.device}, the models on {dev}")
+    if x1.shape != x2.shape or x1.shape[0] < 1:
+        raise StcdError(f"x1 and x2 must share one shape with B >= 1: {tuple(x1.shape)} and {tuple(x2.shape)}")
+    B, H, W = int(x1.shape[0]), int(x1.shape[2]), int(x1.shape[3])
+    if label is not None:
+        if not torch.is_tensor(label) or label.dtype != torch.uint8 or tuple(label.shape) != (B, H, W):
+            raise StcdError(f"label must be uint8 [{B},{H},{W}]")
+        if label.device != dev:
+            raise StcdError(f"label is on {label.device}, the models on {dev}")
+    if cm is not None:
+        if label is None:
+            raise StcdError("cm needs a label")
+        if not torch.is_tensor(cm) or cm.dtype != torch.int64 or cm.numel() != 4 or cm.device != dev or not cm.is_contiguous():
+            raise StcdError(f"cm must be a contiguous int64 tensor of 4 elements on {dev}")
+    if not 1 <= int(mask_value) <= 255:
+        raise StcdError(f"mask_value must be in [1, 255], got {mask_value}")
+    # everything is checked: from here on the device works
+    K = len(models)
+    with torch.cuda.device(dev), _evaluating(models):
+        outs = []
+        for m in models:
+            lg = _change_logits(m(x1, x2))
+            if not torch.is_tensor(lg) or lg.dim() != 4 or lg.shape[0] != B or lg.shape[1] not in (1, 2) or tuple(lg.shape[2:]) != (H, W):
+                got = tuple(lg.shape) if torch.is_tensor(lg) else type(lg).__name__
+                raise StcdError(f"a model returned {got} for {B} pairs of {H} x {W}: expected [{B},1|2,{H},{W}]")
+            if outs and lg.shape[1] != outs[0].shape[1]:
+                raise StcdError("the models differ in their number of classes")
+            outs.append(lg.float().contiguous())
+        classes = int(outs[0].shape[1])
+        lab = None if label is None else label.contiguous()
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        agree = torch.zeros((B, K - 1, 2, 2), dtype=torch.int64, device=dev) if K > 1 else None
+        if lab is not None and cm is None:
+            cm = torch.zeros(4, dtype=torch.int64, device=dev)
+        ptrs = (C.c_void_p * K)(*[o.data_ptr() for o in outs])
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().stcd_selftrain_score(ptrs, K, B, classes, H * W, C.c_float(threshold), _ptr(lab), int(mask_value), _ptr(mask),
+                                                   _ptr(agree), _ptr(cm), stream))
+    return BatchScore(mask, agree, cm)
+
+
+# ------------------------------------------------------------------------------------------------ host side: reliability and split
+def _agree_array(agree) -> np.ndarray:
+    a = np.asarray(agree)
+    if a.ndim == 3 and a.shape[-1] == 4:
+        a = a.reshape(a.shape[0], a.shape[1], 2, 2)
+    if a.ndim != 4 or a.shape[2:] != (2, 2) or not np.issubdtype(a.dtype, np.integer):
+        raise StcdError(f"agree must be an integer array [N,K-1,2,2], got {a.dtype} {a.shape}")
+    if a.shape[1] < 1:
+        raise StcdError("reliability needs at least two models (one earlier checkpoint to compare with the last)")
+    return a.astype(np.int64)
+
+
+def reliability(agree, cumulative: bool = False) -> np.ndarray:
+    """float64 ``[N]`` from ``agree`` int64 ``[N,K-1,2,2]`` (``agree[n, i, last, pred_i]``), numpy only.
+
+    ``cumulative=False``: per pair the mean over the K-1 earlier models of ``IoU_1 = a11 / (a11 + a10 + a01)`` of that pair's own
+    matrix; an empty union (neither mask holds change) is full agreement, 1.0.  This is the rule of ST++ that the reference's loop
+    evidently means, and the library's own specification where the two part.
+
+    ``cumulative=True``: the reference's literal arithmetic.  Its metric object is created once before the loop and never reset
+    (train_stcd.py:106; ``addBatch`` only adds), so the IoU it appends at :122 is that of the matrix accumulated over every earlier
+    pair and checkpoint in processing order: prefix sums of ``agree``.  0 / 0 is NaN, as there."""
+    a = _agree_array(agree)
+    N, E = a.shape[:2]
+    if cumulative:
+        a = np.cumsum(a.reshape(N * E, 2, 2), axis=0).reshape(N, E, 2, 2)
+    inter = a[:, :, 1, 1].astype(np.float64)
+    union = (a[:, :, 1, 1] + a[:, :, 1, 0] + a[:, :, 0, 1]).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = inter / union
+    if not cumulative:
+        iou = np.where(union == 0, 1.0, iou)
+    total = iou[:, 0].copy()
+    for i in range(1, E):                                       # the reference's sum(mIOU): left to right
+        total = total + iou[:, i]
+    return total / E
+
+
+def split_reliable(names: Sequence[str], rel) -> Tuple[List[str], List[str]]:
+    """Descending reliability, ties in input order (Python's stable ``sort(reverse=True)``, train_stcd.py:127), NaN last in input
+    order (own rule: the reference's order is undefined there); the first ``len // 2`` are reliable (:130-134)."""
+    names = list(names)
+    rel = np.asarray(rel, dtype=np.float64).ravel()
+    if rel.shape[0] != len(names):
+        raise StcdError(f"{len(names)} names for {rel.shape[0]} reliabilities")
+    finite = [i for i in range(len(names)) if not np.isnan(rel[i])]
+    finite.sort(key=lambda i: rel[i], reverse=True)
+    order = finite + [i for i in range(len(names)) if np.isnan(rel[i])]
+    ranked = [names[i] for i in order]
+    half = len(ranked) // 2
+    return ranked[:half], ranked[half:]
+
+
+def write_lists(list_dir: str, reliable: Sequence[str], unreliable: Sequence[str]) -> None:
+    """``reliable_ids.txt`` and ``unreliable_ids.txt`` under ``list_dir``, one name and a newline per line (train_stcd.py:128-135)."""
+    os.makedirs(list_dir, exist_ok=True)
+    for fname, ids in (("reliable_ids.txt", reliable), ("unreliable_ids.txt", unreliable)):
+        with open(os.path.join(list_dir, fname), "w") as f:
+            for name in ids:
+                f.write(name + "\n")
+
+
+# ------------------------------------------------------------------------------------------------ drivers
+def _check_names(names, batch: int, seen: set) -> List[str]:
+    names = [names] if isinstance(names, str) else list(names)
+    if len(names) != batch:
+        raise StcdError(f"{len(names)} names for a batch of {batch} pairs")
+    for n in names:
+        if not isinstance(n, str) or not n:
+            raise StcdError(f"a pair's name must be a non-empty string, got {n!r}")
+        if n in seen:
+            raise StcdError(f"the name {n!r} comes twice")
+        seen.add(n)
+    return names
+
+
+def _batch_size(x1) -> int:
+    if not torch.is_tensor(x1) or x1.dim() != 4:
+        raise StcdError("x1 must be an fp32 [B,C,H,W] tensor")
+    return int(x1.shape[0])
+
+
+def _to_host(parts: List[torch.Tensor]) -> List[np.ndarray]:
+    """One copy for tensors of one shape (the usual case), one each otherwise; the only place a driver waits for the device."""
+    if not parts:
+        return []
+    if all(p.shape[1:] == parts[0].shape[1:] for p in parts):
+        return [torch.cat(parts).cpu().numpy()]
+    return [p.cpu().numpy() for p in parts]
+
+
+def select_reliable(models, batches: Iterable, list_dir: Optional[str] = None, cumulative: bool = False, threshold: float = 0.0,
+                    flush: int = 64) -> Selection:
+    """The reliability split of train_stcd.py:96-135 over ``batches``, an iterable of ``(x1, x2, label_or_None, names)`` of any batch
+    size (the label is not used).  Every batch is enqueued without a host sync; the agreement counts wait in device buffers and come
+    back once per ``flush`` batches.  With ``list_dir`` the two lists are written there."""
+    models = _model_list(models)
+    if len(models) < 2:
+        raise StcdError("the reliability split compares earlier checkpoints with the last: at least two models")
+    if int(flush) < 1:
+        raise StcdError(f"flush must be >= 1, got {flush}")
+    names: List[str] = []
+    seen: set = set()
+    pending: List[torch.Tensor] = []
+    done: List[np.ndarray] = []
+    with _evaluating(models):
+        for x1, x2, _label, batch_names in batches:
+            names += _check_names(batch_names, _batch_size(x1), seen)
+            pending.append(score_batch(models, x1, x2, threshold=threshold).agree)
+            if len(pending) >= flush:
+                done += _to_host(pending)
+                pending = []
+        done += _to_host(pending)
+    K = len(models)
+    agree = np.concatenate(done).reshape(-1, K - 1, 2, 2) if done else np.zeros((0, K - 1, 2, 2), np.int64)
+    rel = reliability(agree, cumulative) if len(names) else np.zeros(0, np.float64)
+    reliable, unreliable = split_reliable(names, rel)
+    if list_dir is not None:
+        write_lists(list_dir, reliable, unreliable)
+    return Selection(reliable, unreliable, names, rel, agree)
+
+
+def generate_pseudo_labels(model, batches: Iterable, out_dir: Optional[str], threshold: float = 0.0, write: bool = True,
+                           flush: int = 64) -> Optional[dict]:
+    """The pseudo-label writer of train_stcd.py:137-204 over ``batches`` (as ``select_reliable``): ``model`` predicts every pair, the
+    mask times 255 is saved as a mode-``L`` PNG under the pair's own name in ``out_dir`` (``write=False``: scores only), and when
+    the batches carry labels the ``scores_from_cm`` of the confusion matrix over all pairs are returned (else None).  The masks
+    wait on the device and come back once per ``flush`` batches; the confusion matrix comes back once, at the end."""
+    models = _model_list([model])
+    if int(flush) < 1:
+        raise StcdError(f"flush must be >= 1, got {flush}")
+    if write:
+        if out_dir is None:
+            raise StcdError("out_dir is needed to write the masks")
+        from PIL import Image
+        os.makedirs(out_dir, exist_ok=True)
+    seen: set = set()
+    pending: List[torch.Tensor] = []
+    pending_names: List[str] = []
+    cm = None
+    labelled: Optional[bool] = None
+
+    def drain():
+        nonlocal pending, pending_names
+        at = 0
+        for block in _to_host(pending):
+            for m in block:                                     # uint8 [H,W]: Pillow's mode L
+                Image.fromarray(m).save(os.path.join(out_dir, pending_names[at]), format="PNG")
+                at += 1
+        pending, pending_names = [], []
+
+    with _evaluating(models):
+        for x1, x2, label, batch_names in batches:
+            batch_names = _check_names(batch_names, _batch_size(x1), seen)
+            if labelled is None:
+                labelled = label is not None
+            elif labelled != (label is not None):
+                raise StcdError("either every batch carries a label or none does")
+            res = score_batch(models, x1, x2, label=label, threshold=threshold, mask_value=255, cm=cm)
+            cm = res.cm
+            if write:
+                pending.append(res.mask)
+                pending_names += batch_names
+                if len(pending) >= flush:
+                    drain()
+        if write:
+            drain()
+    if cm is None:
+        return None
+    return scores_from_cm(cm.cpu().numpy().reshape(2, 2))
