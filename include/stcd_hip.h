@@ -54,6 +54,17 @@ extern "C" {
  * FC-Siam encoder / decoder with a cross_conc block on every skip (:11-33: the two dates' channels interleaved into a grouped 3x3
  * conv (C groups of 2 -> 1), BatchNorm, ReLU, a 3x3 conv C -> C, BatchNorm, ReLU); forward returns [logits]. */
 #define STCD_ARCH_XCONC 10
+/* Siam_NestedUNet_Conc, "SNUNet-CD without attention" (models/SNUNet.py:155-243; no define_G name in the reference): the trunk
+ * and state_dict layout of SNUNet_ECAM without ca / ca1, then final1..final4 (Conv2d(32, label_ch, 1) on x0_1..x0_4) and
+ * conv_final (Conv2d(4 * label_ch, label_ch, 1)) over their concat.  H and W must be divisible by 16.  The head runs as one
+ * composed 1x1 conv 128 -> label_ch over cat(x0_1..x0_4), streamed once per direction by kernels of its own that read / write the
+ * fp32 NCHW maps directly (no packed output gradient, no output_1..4 in memory); both ids take that path. */
+#define STCD_ARCH_SNUNET_CONC 11 /* forward returns the fused map: logits [batch, label_ch, H, W] */
+/* the same network with deep supervision (models/SNUNet.py:155-243 computes output1..4 and drops them; models/trainer.py:300-309
+ * trains on a list): `logits` / `grad_logits` hold FIVE maps, map-major, [5*batch, label_ch, H, W] = output1, output2, output3,
+ * output4, output (the [3*batch, ...] convention of STCD_ARCH_SEGCD); the last map equals STCD_ARCH_SNUNET_CONC's output bit for
+ * bit.  label_ch <= 2. */
+#define STCD_ARCH_SNUNET_CONC_DS 12
 /* smp.UnetSeg (decoders/unet/model.py:109-171), the single-image ResNet UNet train_sup.py:303 trains: the same encoder /
  * decoder / head on ONE image batch (x2 of stcd_forward is ignored; BatchNorm over the whole batch; logits [batch, label_ch,
  * H, W]).  STCD_ARCH_UNETSEG + k, k = 0..4: resnet50, resnet18, resnet34, resnet101, resnet152 (the order of the ids above). */

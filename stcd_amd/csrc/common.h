@@ -522,6 +522,16 @@ void launch_ecam_backward(int dt, const void* X, int ld, const void* dZ, int ldd
                           const float* w1a, const float* w2a, const float* w1b, const float* w2b, float* gw1a, float* gw2a,
                           float* gw1b, float* gw2b, const float* pool, const int64_t* argm, const float* att, const float* hid,
                           float* sums, float* dpool, float* part, hipStream_t s);
+// head of Siam_NestedUNet_Conc (SNUNet.py:195-199, 238-242) as one composed 1x1 conv over E = cat(x0_1..x0_4); kernels_snhead.hip.
+// Parameter / gradient pointers in the reference's layouts: w[i] = final{i+1}.weight [L,32], b[i] its bias [L], wf = conv_final.weight
+// [L,4L], bf its bias [L].  ds: the fp32 NCHW maps hold [5B, L, H, W] (output1..4, then the fused map) instead of [B, L, H, W].
+struct SnHeadParams { const float* w[4]; const float* b[4]; const float* wf; const float* bf; int L, ds; };
+struct SnHeadGrads { float* w[4]; float* b[4]; float* wf; float* bf; };
+int64_t snhead_scratch_floats(int B, int64_t HW, int L, int ds);      // partial sums of the backward (H * W a multiple of 64)
+void launch_snhead_forward(int dt, const void* E, int ld, const SnHeadParams& p, float* out, int B, int64_t HW, hipStream_t s);
+// dE (written once) = W_all^T . G; the ten parameter gradients are OVERWRITTEN (fixed-order sums, no atomics)
+void launch_snhead_backward(int dt, const void* E, int ld, const SnHeadParams& p, const SnHeadGrads& g, const float* G, void* dE,
+                            int ldd, float* scratch, int B, int64_t HW, hipStream_t s);
 // dA (+)= route(dP) to the first maximum of each 2x2 window of A
 void launch_pool_bwd(int dt, const void* A, int lda, int64_t a_goff, const void* dP, int ldp, void* dA, int ldda,
                      int64_t da_goff, int groups, int npg, int H, int W, int C, int accumulate, hipStream_t s);

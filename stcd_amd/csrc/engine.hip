@@ -212,6 +212,8 @@ struct stcd_engine_impl {
     int64_t sn_pool = -1, sn_argm = -1, sn_att = -1, sn_hid = -1, sn_sums = -1, sn_dpool = -1, sn_part = -1;
     int64_t sn_dout_begin = -1, sn_dout_end = -1;
     ConvOp sn_final_fwd, sn_final_dgr; WgradOp sn_final_wg;
+    // Siam_NestedUNet_Conc (SNUNet.py:155-243): final1..4 / conv_final offsets in the flat params (weight, bias), head scratch
+    int64_t snc_w[5] = {0, 0, 0, 0, 0}, snc_b[5] = {0, 0, 0, 0, 0}, snc_scratch = -1;
     // ---- SegCD (ResNet-50 UNet) plan
     std::vector<GLayer> g_layers;                            // every conv + BatchNorm (+ residual) (+ ReLU) layer, forward order
     std::vector<GStep> g_fwd;                                // forward program (the backward walks it in reverse)
@@ -432,6 +434,10 @@ static const DecSpec DEC[4] = {
 static inline int fc_dates(const stcd_engine& e) { return e.arch == STCD_ARCH_FCEF ? 1 : 2; }
 static inline bool fc_concat_skips(const stcd_engine& e) { return e.arch == STCD_ARCH_CONC || e.arch == STCD_ARCH_FCEF; }
 static inline bool fc_cross(const stcd_engine& e) { return e.arch == STCD_ARCH_XCONC; }
+// Siam_NestedUNet_Conc shares the trunk (tables, plan, block order); only the tail differs (kernels_snhead.hip)
+static inline bool is_snconc(int arch) { return arch == STCD_ARCH_SNUNET_CONC || arch == STCD_ARCH_SNUNET_CONC_DS; }
+static inline bool is_snunet(int arch) { return arch == STCD_ARCH_SNUNET || is_snconc(arch); }
+static inline int sn_out_maps(int arch) { return arch == STCD_ARCH_SNUNET_CONC_DS ? 5 : 1; }
 // skip layers of diff / sub whose activations are never stored: the forward writes only the pooled map and the fused skip,
 // the backward (k_skip_bwd_pair) recomputes them from Y
 static inline bool skip_recomputed(const stcd_engine& e, const Cbrd& L) {
@@ -568,7 +574,7 @@ static WgradMfmaPlan pick_wgrad_plan(const stcd_engine& e, const stcd_conv_geom&
         WgradMfmaPlan p = wgrad_dma_plan(g, kpad, wld);
         if (p.ok) return p;
     }
-    return wgrad_mfma_plan(g, kpad, wld, e.arch == STCD_ARCH_SNUNET || (e.cf && g.ntaps == 9));
+    return wgrad_mfma_plan(g, kpad, wld, is_snunet(e.arch) || (e.cf && g.ntaps == 9));
 }
 
 static void build_pack_jobs(stcd_engine& e, Bump& ws) {
@@ -1750,7 +1756,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
     return 0;
 }
 
-// ================================================================================================ SNUNet-ECAM
+// ================================================================================================ SNUNet-ECAM, Siam_NestedUNet_Conc
 static const int SN_F[5] = {32, 64, 128, 256, 512};
 
 static int add_block_params(stcd_engine& e, const std::string& name, int cin, int c, int calls, bool need_dgrad1, NBlock* b) {
@@ -1788,12 +1794,24 @@ static void build_snunet_tables(stcd_engine& e) {
     blk("conv1_3", f[1] * 4 + f[2], f[1], 1, true); up("Up1_3", f[1]);
     blk("conv0_4", f[0] * 5 + f[1], f[0], 1, true);
     const int c4 = f[0] * 4, c1 = f[0];
+    e.enc_param_end = 0;      // one backward stage: every gradient is final when stage 0 returns
+    if (is_snconc(e.arch)) {      // registration order of Siam_NestedUNet_Conc.__init__ (SNUNet.py:195-199)
+        const int L = e.label;
+        for (int i = 0; i < 4; ++i) {
+            const std::string n = std::string("final") + char('1' + i);
+            add_param(e, n + ".weight", {L, c1, 1, 1}, &e.snc_w[i]);
+            add_param(e, n + ".bias", {L}, &e.snc_b[i]);
+        }
+        add_param(e, "conv_final.weight", {L, 4 * L, 1, 1}, &e.snc_w[4]);
+        add_param(e, "conv_final.bias", {L}, &e.snc_b[4]);
+        e.sn_final = -1;
+        return;
+    }
     add_param(e, "ca.fc1.weight", {c4 / 16, c4, 1, 1}, &e.sn_w[0]);
     add_param(e, "ca.fc2.weight", {c4, c4 / 16, 1, 1}, &e.sn_w[1]);
     add_param(e, "ca1.fc1.weight", {c1 / 4, c1, 1, 1}, &e.sn_w[2]);
     add_param(e, "ca1.fc2.weight", {c1, c1 / 4, 1, 1}, &e.sn_w[3]);
     e.sn_final = add_conv(e, "conv_final", K_CONV1, c4, e.label, true);
-    e.enc_param_end = 0;      // one backward stage: every gradient is final when stage 0 returns
 }
 
 static int sn_block_index(const stcd_engine& e, const std::string& name) {
@@ -1825,10 +1843,12 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     auto plain = [&](int N, int h, int w, int C) { TRef t; t.off = ws.take((int64_t)N * h * w * C * T); t.ld = C; return t; };
     auto B_ = [&](const char* n) -> NBlock& { return e.sn_blocks[sn_block_index(e, n)]; };
 
+    const bool conc = is_snconc(e.arch);       // no ECAM: no gated copy of E, no packed output gradient (kernels_snhead.hip)
     e.X0 = plain(2 * B, H, W, 8);
-    e.G = plain(B, H, W, 8);
+    if (!conc) e.G = plain(B, H, W, 8);
     const int c4 = f[0] * 4;
-    e.snE = plain(B, H, W, c4); e.snZ = plain(B, H, W, c4); e.sndZ = plain(B, H, W, c4);
+    e.snE = plain(B, H, W, c4);
+    if (!conc) { e.snZ = plain(B, H, W, c4); e.sndZ = plain(B, H, W, c4); }
 
     // ---- activation buffers of every block.  dOut buffers are allocated back to back: one memset per backward.
     e.sn_dout_begin = ws.cur;
@@ -1865,7 +1885,7 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         b.bacc1 = ws.take(bn_acc_bytes(b.groups, b.C)); b.bacc2 = ws.take(bn_acc_bytes(b.groups, b.C));
     }
     for (auto& u : e.sn_ups) u.bias_acc = ws.take(bn_acc_bytes(1, u.C));
-    e.final_bias_acc = ws.take(bn_acc_bytes(1, 8));
+    if (!conc) e.final_bias_acc = ws.take(bn_acc_bytes(1, 8));
     e.zero_end = ws.cur;
     // ---- inputs
     for (auto& b : e.sn_blocks) {
@@ -1955,10 +1975,14 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
 
     e.scratch8 = ws.take(256);
     e.masks = ws.take(256);
-    e.sn_pool = ws.take((int64_t)B * 4 * c4 * 4); e.sn_argm = ws.take((int64_t)B * 2 * c4 * 8);
-    e.sn_att = ws.take((int64_t)B * 2 * c4 * 4); e.sn_hid = ws.take((int64_t)B * 2 * 2 * 16 * 4);
-    e.sn_sums = ws.take((int64_t)B * 2 * c4 * 4); e.sn_dpool = ws.take((int64_t)B * 4 * c4 * 4);
-    e.sn_part = ws.take(ecam_part_floats(B, c4) * 4);
+    if (conc) {
+        e.snc_scratch = ws.take(snhead_scratch_floats(B, (int64_t)H * W, e.label, sn_out_maps(e.arch) > 1) * 4);
+    } else {
+        e.sn_pool = ws.take((int64_t)B * 4 * c4 * 4); e.sn_argm = ws.take((int64_t)B * 2 * c4 * 8);
+        e.sn_att = ws.take((int64_t)B * 2 * c4 * 4); e.sn_hid = ws.take((int64_t)B * 2 * 2 * 16 * 4);
+        e.sn_sums = ws.take((int64_t)B * 2 * c4 * 4); e.sn_dpool = ws.take((int64_t)B * 4 * c4 * 4);
+        e.sn_part = ws.take(ecam_part_floats(B, c4) * 4);
+    }
     for (auto& c : e.convs) {
         c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
         if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
@@ -2024,7 +2048,7 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         for (int t = 0; t < 4; ++t) { gd.dy[t] = (int8_t)(t >> 1); gd.dx[t] = (int8_t)(t & 1); }
         bind_conv(u.dgr, gd, u.conv, true, 0, u.C, u.C);
     }
-    {
+    if (!conc) {
         const ConvW& cv = e.convs[e.sn_final];
         bind_conv(e.sn_final_fwd, geom1(B, H, W, c4, e.snZ.ld, e.label, e.label), e.sn_final, false, 0, c4, e.label);
         bind_wgrad(e.sn_final_wg, geom1(B, H, W, c4, e.snZ.ld, e.label, 8), e.sn_final, 0, c4, e.label, e.snZ.off, e.G.off);
@@ -2048,8 +2072,10 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         }
     }
     {
-        BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.sn_final].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
-        e.bias_jobs.push_back(jb);
+        if (!conc) {
+            BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.sn_final].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
+            e.bias_jobs.push_back(jb);
+        }
         e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
     }
     build_pack_jobs(e, ws);
@@ -2174,6 +2200,14 @@ static void sn_up_backward(const Ctx& c, const SnUp& u) {
     (void)T;
 }
 
+static SnHeadParams sn_head_params(const stcd_engine& e, const float* params) {
+    SnHeadParams p;
+    for (int i = 0; i < 4; ++i) { p.w[i] = params + e.snc_w[i]; p.b[i] = params + e.snc_b[i]; }
+    p.wf = params + e.snc_w[4]; p.bf = params + e.snc_b[4];
+    p.L = e.label; p.ds = sn_out_maps(e.arch) > 1;
+    return p;
+}
+
 static int forward_snunet(stcd_engine& e, const float* x1, const float* x2, const float* params, float* bn_running, int training,
                           float* logits, void* workspace, hipStream_t s) {
     Ctx c{e, (char*)workspace, params, nullptr, s};
@@ -2184,6 +2218,13 @@ static int forward_snunet(stcd_engine& e, const float* x1, const float* x2, cons
         const NBlock& b = e.sn_blocks[bi];
         if (b.up >= 0) sn_up_forward(c, e.sn_ups[b.up]);
         sn_block_forward(c, b, bn_running, training != 0);
+    }
+    if (is_snconc(e.arch)) {
+        ProfScope ps(c, PC_CONV, 2.0 * e.B * e.H * e.W * 128.0 * sn_out_maps(e.arch) * e.label,
+                     (double)e.B * e.H * e.W * (128.0 * dsize(e.dt) + 4.0 * sn_out_maps(e.arch) * e.label), "k_snhead_fwd");
+        launch_snhead_forward(e.dt, c.at(e.snE.off), e.snE.ld, sn_head_params(e, params), logits, e.B, (int64_t)e.H * e.W, s);
+        STCD_HIP(hipGetLastError());
+        return 0;
     }
     const int c4 = SN_F[0] * 4;
     launch_ecam_forward(e.dt, c.at(e.snE.off), e.snE.ld, c.at(e.snZ.off), e.snZ.ld, e.B, (int64_t)e.H * e.W, c4, params + e.sn_w[0],
@@ -2213,13 +2254,23 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
     // (no bulk zeroing of the dOut buffers: each is fully written -- max-pool / ECAM gradient, or the gathered sum)
     for (auto& b : e.sn_blocks)          // pooled gradients of the A half of conv3_0 never get written (x4_0A does not exist)
         if (b.pool && b.name == "conv3_0") STCD_HIP(hipMemsetAsync(c.at(b.dP.off), 0, (int64_t)B * (b.H / 2) * (b.W / 2) * b.C * T, s));
-    launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
-    exec_wgrad(c, e.sn_final_wg, c.at(e.snZ.off), c.at(e.G.off));
-    exec_conv(c, e.sn_final_dgr, c.at(e.G.off), nullptr, c.at(e.sndZ.off), false);
-    launch_ecam_backward(dt, c.at(e.snE.off), e.snE.ld, c.at(e.sndZ.off), e.sndZ.ld, c.at(e.sndE.off), e.sndE.ld, B, (int64_t)e.H * e.W, c4,
-                         params + e.sn_w[0], params + e.sn_w[1], params + e.sn_w[2], params + e.sn_w[3], grads + e.sn_w[0],
-                         grads + e.sn_w[1], grads + e.sn_w[2], grads + e.sn_w[3], c.at<float>(e.sn_pool), c.at<int64_t>(e.sn_argm),
-                         c.at<float>(e.sn_att), c.at<float>(e.sn_hid), c.at<float>(e.sn_sums), c.at<float>(e.sn_dpool), c.at<float>(e.sn_part), s);
+    if (is_snconc(e.arch)) {
+        const double px = (double)B * e.H * e.W, no = (double)sn_out_maps(e.arch) * e.label;
+        ProfScope ps(c, PC_CONV, 4.0 * px * 128.0 * no, px * (256.0 * (double)T + 4.0 * no), "k_snhead_bwd|k_snhead_reduce|k_snhead_chain");
+        SnHeadGrads hg;
+        for (int i = 0; i < 4; ++i) { hg.w[i] = grads + e.snc_w[i]; hg.b[i] = grads + e.snc_b[i]; }
+        hg.wf = grads + e.snc_w[4]; hg.bf = grads + e.snc_b[4];
+        launch_snhead_backward(dt, c.at(e.snE.off), e.snE.ld, sn_head_params(e, params), hg, grad_logits, c.at(e.sndE.off), e.sndE.ld,
+                               c.at<float>(e.snc_scratch), B, (int64_t)e.H * e.W, s);
+    } else {
+        launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
+        exec_wgrad(c, e.sn_final_wg, c.at(e.snZ.off), c.at(e.G.off));
+        exec_conv(c, e.sn_final_dgr, c.at(e.G.off), nullptr, c.at(e.sndZ.off), false);
+        launch_ecam_backward(dt, c.at(e.snE.off), e.snE.ld, c.at(e.sndZ.off), e.sndZ.ld, c.at(e.sndE.off), e.sndE.ld, B, (int64_t)e.H * e.W, c4,
+                             params + e.sn_w[0], params + e.sn_w[1], params + e.sn_w[2], params + e.sn_w[3], grads + e.sn_w[0],
+                             grads + e.sn_w[1], grads + e.sn_w[2], grads + e.sn_w[3], c.at<float>(e.sn_pool), c.at<int64_t>(e.sn_argm),
+                             c.at<float>(e.sn_att), c.at<float>(e.sn_hid), c.at<float>(e.sn_sums), c.at<float>(e.sn_dpool), c.at<float>(e.sn_part), s);
+    }
     for (int oi = (int)e.sn_order.size() - 1; oi >= 0; --oi) {
         const NBlock& b = e.sn_blocks[e.sn_order[oi]];
         if (b.pool) {    // gradient coming back through the 2x2 max-pool of this encoder output
@@ -2953,7 +3004,7 @@ int stcd_cf_set_drop_rates(stcd_engine* e, float drop_rate, float attn_drop, flo
 int64_t stcd_output_floats(const stcd_engine* e) {
     if (!e || !e->configured) return 0;
     if (e->cf) return e->cf->out_floats;
-    const int maps = (is_segcd(e->arch) && !is_unetseg(e->arch)) ? 3 : 1;
+    const int maps = (is_segcd(e->arch) && !is_unetseg(e->arch)) ? 3 : sn_out_maps(e->arch);
     return (int64_t)maps * e->B * e->label * e->H * e->W;
 }
 int stcd_cf_output_info(const stcd_engine* e, int i, int64_t* offset, int* height, int* width) {
@@ -2971,15 +3022,16 @@ int stcd_create(int arch, int in_ch, int label_ch, int dtype, stcd_engine** out)
         cfg.in_ch = in_ch; cfg.out_ch = label_ch;
         return stcd_create_changeformer(&cfg, dtype, out);
     }
-    STCD_CHECK((arch >= STCD_ARCH_DIFF && arch <= STCD_ARCH_SEGCD_R152) || arch == STCD_ARCH_FCEF || arch == STCD_ARCH_XCONC || is_unetseg(arch) || is_ffctlcd(arch), "unknown arch");
+    STCD_CHECK((arch >= STCD_ARCH_DIFF && arch <= STCD_ARCH_SEGCD_R152) || arch == STCD_ARCH_FCEF || arch == STCD_ARCH_XCONC || is_snconc(arch) || is_unetseg(arch) || is_ffctlcd(arch), "unknown arch");
     STCD_CHECK(arch != STCD_ARCH_FCEF || in_ch <= 4, "FC-EF concatenates the two dates along the channels: in_ch must be <= 4");
     STCD_CHECK(in_ch >= 1 && in_ch <= 8, "in_ch must be in [1,8]");
     STCD_CHECK(label_ch >= 1 && label_ch <= 8, "label_ch must be in [1,8]");
     STCD_CHECK(dtype == STCD_DTYPE_F32 || dtype == STCD_DTYPE_BF16, "unknown dtype");
+    STCD_CHECK(arch != STCD_ARCH_SNUNET_CONC_DS || label_ch <= 2, "Siam_NestedUNet_Conc with deep supervision: label_ch must be <= 2 (five maps of label_ch rows each in one pass of the head kernels)");
     std::unique_ptr<stcd_engine> e(new stcd_engine());
     e->arch = arch; e->in_ch = in_ch; e->label = label_ch; e->dt = dtype;
     engine_env_switches(e.get());
-    if (arch == STCD_ARCH_SNUNET) build_snunet_tables(*e);
+    if (is_snunet(arch)) build_snunet_tables(*e);
     else if (is_segcd(arch)) build_segcd_tables(*e);
     else build_fcsiam_tables(*e);
     *out = e.release();
@@ -3020,7 +3072,7 @@ int stcd_configure(stcd_engine* e, int batch, int height, int width) {
     if (is_cf(e->arch)) {
         STCD_CHECK(height % 32 == 0 && width % 32 == 0, "ChangeFormer needs height and width divisible by 32 (stride-4 patch embedding, sr_ratio 8)");
         if (configure_cf(*e, batch, height, width)) return 1;
-    } else if (e->arch == STCD_ARCH_SNUNET) {
+    } else if (is_snunet(e->arch)) {
         STCD_CHECK(height % 16 == 0 && width % 16 == 0, "SNUNet needs height and width divisible by 16 (the reference's cat of up-sampled maps fails otherwise)");
         if (configure_snunet(*e, batch, height, width)) return 1;
     } else if (is_segcd(e->arch)) {
@@ -3069,7 +3121,7 @@ int stcd_forward(stcd_engine* e, const float* x1, const float* x2, const float* 
     e->fwd_training = false;
     int rc = is_cf(e->arch)
                  ? forward_cf(*e, x1, x2, params, bn_running, dropout_masks, dropout_seed, training, logits, workspace, (hipStream_t)hip_stream)
-             : e->arch == STCD_ARCH_SNUNET
+             : is_snunet(e->arch)
                  ? forward_snunet(*e, x1, x2, params, bn_running, training, logits, workspace, (hipStream_t)hip_stream)
                  : is_segcd(e->arch)
                        ? forward_segcd(*e, x1, x2, params, bn_running, training, logits, workspace, (hipStream_t)hip_stream)
@@ -3086,7 +3138,7 @@ int stcd_backward(stcd_engine* e, const float* grad_logits, const float* params,
     STCD_CHECK(grad_logits && params && grads && workspace, "null pointer argument");
     STCD_CHECK(stage >= -1 && stage <= 1, "stage must be -1, 0 or 1");
     if (is_cf(e->arch)) return backward_cf(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
-    if (e->arch == STCD_ARCH_SNUNET) return backward_snunet(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
+    if (is_snunet(e->arch)) return backward_snunet(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
     if (is_segcd(e->arch)) return backward_segcd(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
     return backward_fcsiam(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
 }

@@ -470,6 +470,49 @@ class _ChannelAttentionHolder(nn.Module):
         self.fc2 = nn.Conv2d(in_channels // ratio, in_channels, 1, bias=False)
 
 
+def _snunet_trunk(m, in_ch):
+    """Registers the nested-UNet trunk on `m` in the reference's order (SNUNet.py:73-103 = :163-193) and returns the widths."""
+    n1 = 32
+    f = [n1, n1 * 2, n1 * 4, n1 * 8, n1 * 16]
+    m.pool = nn.MaxPool2d(kernel_size=2, stride=2)
+    m.conv0_0 = _NestedBlockHolder(in_ch, f[0], f[0])
+    m.conv1_0 = _NestedBlockHolder(f[0], f[1], f[1])
+    m.Up1_0 = _UpHolder(f[1])
+    m.conv2_0 = _NestedBlockHolder(f[1], f[2], f[2])
+    m.Up2_0 = _UpHolder(f[2])
+    m.conv3_0 = _NestedBlockHolder(f[2], f[3], f[3])
+    m.Up3_0 = _UpHolder(f[3])
+    m.conv4_0 = _NestedBlockHolder(f[3], f[4], f[4])
+    m.Up4_0 = _UpHolder(f[4])
+    m.conv0_1 = _NestedBlockHolder(f[0] * 2 + f[1], f[0], f[0])
+    m.conv1_1 = _NestedBlockHolder(f[1] * 2 + f[2], f[1], f[1])
+    m.Up1_1 = _UpHolder(f[1])
+    m.conv2_1 = _NestedBlockHolder(f[2] * 2 + f[3], f[2], f[2])
+    m.Up2_1 = _UpHolder(f[2])
+    m.conv3_1 = _NestedBlockHolder(f[3] * 2 + f[4], f[3], f[3])
+    m.Up3_1 = _UpHolder(f[3])
+    m.conv0_2 = _NestedBlockHolder(f[0] * 3 + f[1], f[0], f[0])
+    m.conv1_2 = _NestedBlockHolder(f[1] * 3 + f[2], f[1], f[1])
+    m.Up1_2 = _UpHolder(f[1])
+    m.conv2_2 = _NestedBlockHolder(f[2] * 3 + f[3], f[2], f[2])
+    m.Up2_2 = _UpHolder(f[2])
+    m.conv0_3 = _NestedBlockHolder(f[0] * 4 + f[1], f[0], f[0])
+    m.conv1_3 = _NestedBlockHolder(f[1] * 4 + f[2], f[1], f[1])
+    m.Up1_3 = _UpHolder(f[1])
+    m.conv0_4 = _NestedBlockHolder(f[0] * 5 + f[1], f[0], f[0])
+    return f
+
+
+def _snunet_init(m):
+    """Default initialisation of both SNUNet classes (SNUNet.py:108-113, :201-206)."""
+    for mod in m.modules():
+        if isinstance(mod, nn.Conv2d):
+            nn.init.kaiming_normal_(mod.weight, mode="fan_out", nonlinearity="relu")
+        elif isinstance(mod, (nn.BatchNorm2d, nn.GroupNorm)):
+            nn.init.constant_(mod.weight, 1)
+            nn.init.constant_(mod.bias, 0)
+
+
 class SNUNet_ECAM(HipChangeDetector):
     """SNUNet-CD with ECAM (SNUNet.py:63-152): SNUNet_ECAM(in_ch=3, out_ch=1).forward(xA, xB) -> logits tensor.
     Same parameter names / registration order / default initialisation (kaiming fan_out for Conv2d, BN 1/0,
@@ -479,47 +522,57 @@ class SNUNet_ECAM(HipChangeDetector):
 
     def __init__(self, in_ch=3, out_ch=1, dtype: Optional[str] = None):
         super().__init__(in_ch, out_ch, dtype)
-        n1 = 32
-        f = [n1, n1 * 2, n1 * 4, n1 * 8, n1 * 16]
-        self.pool = nn.MaxPool2d(kernel_size=2, stride=2)
-        self.conv0_0 = _NestedBlockHolder(in_ch, f[0], f[0])
-        self.conv1_0 = _NestedBlockHolder(f[0], f[1], f[1])
-        self.Up1_0 = _UpHolder(f[1])
-        self.conv2_0 = _NestedBlockHolder(f[1], f[2], f[2])
-        self.Up2_0 = _UpHolder(f[2])
-        self.conv3_0 = _NestedBlockHolder(f[2], f[3], f[3])
-        self.Up3_0 = _UpHolder(f[3])
-        self.conv4_0 = _NestedBlockHolder(f[3], f[4], f[4])
-        self.Up4_0 = _UpHolder(f[4])
-        self.conv0_1 = _NestedBlockHolder(f[0] * 2 + f[1], f[0], f[0])
-        self.conv1_1 = _NestedBlockHolder(f[1] * 2 + f[2], f[1], f[1])
-        self.Up1_1 = _UpHolder(f[1])
-        self.conv2_1 = _NestedBlockHolder(f[2] * 2 + f[3], f[2], f[2])
-        self.Up2_1 = _UpHolder(f[2])
-        self.conv3_1 = _NestedBlockHolder(f[3] * 2 + f[4], f[3], f[3])
-        self.Up3_1 = _UpHolder(f[3])
-        self.conv0_2 = _NestedBlockHolder(f[0] * 3 + f[1], f[0], f[0])
-        self.conv1_2 = _NestedBlockHolder(f[1] * 3 + f[2], f[1], f[1])
-        self.Up1_2 = _UpHolder(f[1])
-        self.conv2_2 = _NestedBlockHolder(f[2] * 3 + f[3], f[2], f[2])
-        self.Up2_2 = _UpHolder(f[2])
-        self.conv0_3 = _NestedBlockHolder(f[0] * 4 + f[1], f[0], f[0])
-        self.conv1_3 = _NestedBlockHolder(f[1] * 4 + f[2], f[1], f[1])
-        self.Up1_3 = _UpHolder(f[1])
-        self.conv0_4 = _NestedBlockHolder(f[0] * 5 + f[1], f[0], f[0])
+        f = _snunet_trunk(self, in_ch)
         self.ca = _ChannelAttentionHolder(f[0] * 4, ratio=16)
         self.ca1 = _ChannelAttentionHolder(f[0], ratio=16 // 4)
         self.conv_final = nn.Conv2d(f[0] * 4, out_ch, kernel_size=1)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
+        _snunet_init(self)
         self._check_layout()
 
     def __deepcopy__(self, memo):
         new = type(self)(self._engine.in_ch, self._engine.label_ch, self._engine.dtype)
+        new.load_state_dict({k: v.detach().clone() for k, v in self.state_dict().items()})
+        new.train(self.training)
+        if self._flat_params is not None:
+            new.to(self._flat_params.device)
+        return new
+
+
+class Siam_NestedUNet_Conc(HipChangeDetector):
+    """SNUNet-CD without attention (SNUNet.py:155-243): Siam_NestedUNet_Conc(in_ch=3, out_ch=1).forward(xA, xB) -> the fused
+    logits tensor, as the reference class.  Same parameter names / registration order / default initialisation (SNUNet.py:201-206)
+    as the reference, so state_dicts interchange both ways.
+
+    ``deep_supervision=True`` (an addition: the reference computes output1..4 and drops them, SNUNet.py:238-243) returns the list
+    ``[output1, output2, output3, output4, output]``, fused map last, so ``G_pred[-1]`` and CDTrainer's ``multi_scale_train`` loss
+    work unchanged; gradients flow into all five maps, and a map the loss does not touch carries a zero gradient."""
+
+    ARCH = "snunet_conc"
+
+    def __init__(self, in_ch=3, out_ch=1, dtype: Optional[str] = None, deep_supervision: bool = False):
+        self.deep_supervision = bool(deep_supervision)
+        if self.deep_supervision:
+            self.ARCH = "snunet_conc_ds"
+            self.OUT_MAPS = 5
+        super().__init__(in_ch, out_ch, dtype)
+        f = _snunet_trunk(self, in_ch)
+        self.final1 = nn.Conv2d(f[0], out_ch, kernel_size=1)
+        self.final2 = nn.Conv2d(f[0], out_ch, kernel_size=1)
+        self.final3 = nn.Conv2d(f[0], out_ch, kernel_size=1)
+        self.final4 = nn.Conv2d(f[0], out_ch, kernel_size=1)
+        self.conv_final = nn.Conv2d(out_ch * 4, out_ch, kernel_size=1)
+        _snunet_init(self)
+        self._check_layout()
+
+    def _wrap_output(self, out, B):
+        if not self.deep_supervision:
+            return out
+        if isinstance(out, tuple):          # training: the autograd node already returns the five maps
+            return list(out)
+        return [out[k * B:(k + 1) * B] for k in range(5)]
+
+    def __deepcopy__(self, memo):
+        new = type(self)(self._engine.in_ch, self._engine.label_ch, self._engine.dtype, self.deep_supervision)
         new.load_state_dict({k: v.detach().clone() for k, v in self.state_dict().items()})
         new.train(self.training)
         if self._flat_params is not None:

@@ -17,6 +17,7 @@ _ON_PATH = {
     "SiamUnet_sub": lambda n: SiamUnet_sub(input_nbr=3, label_nbr=n),     # :146-147
     "SiamUnet_cross_conc": lambda n: SiamUnet_cross_conc(input_nbr=3, label_nbr=n),   # :152-153
 }
+_ON_PATH_ARGS = {}      # builders that also read the run's arguments
 _OFF_PATH = ("DTCDSCN", "IFNet", "base_resnet18", "base_transformer_pos_s4",
              "base_transformer_pos_s4_dd8", "base_transformer_pos_s4_dd8_dedim8", "ChangeFormerV1", "ChangeFormerV2",
              "ChangeFormerV3", "ChangeFormerV4", "ChangeFormerV5", "ChangeGNNV1", "ChangeGNNV2",
@@ -29,6 +30,10 @@ def _register_snunet():
     except ImportError:
         return
     _ON_PATH["SNUNet"] = lambda n: SNUNet_ECAM(in_ch=3, out_ch=n)        # networks.py:168-169
+    from .modules import Siam_NestedUNet_Conc
+    # an addition: the reference's define_G has no name for Siam_NestedUNet_Conc (SNUNet.py:155-243); "SNUNet" is untouched
+    _ON_PATH_ARGS["SNUNet_conc"] = lambda n, args: Siam_NestedUNet_Conc(
+        in_ch=3, out_ch=n, deep_supervision=getattr(args, "multi_scale_train", "False") == "True")
 
 
 _register_snunet()
@@ -88,12 +93,17 @@ def init_net(net, init_type="normal", init_gain=0.02, gpu_ids=[]):
 
 
 def define_G(args, init_type="normal", init_gain=0.02, gpu_ids=[]):
+    """The reference's names for the networks on the path, plus one addition: ``"SNUNet_conc"`` builds ``Siam_NestedUNet_Conc``
+    (SNUNet.py:155-243, which the reference's define_G never registers); with ``args.multi_scale_train == "True"`` it returns the
+    five maps [output1..4, output] for CDTrainer's multi-scale loss.  ``"SNUNet"`` still builds ``SNUNet_ECAM``."""
     name = args.net_G
     if name == "ChangeFormerV6":                           # networks.py:195-196: ChangeFormerV6(embed_dim=args.embed_dim), two classes
         from .changeformer import ChangeFormerV6
         net = ChangeFormerV6(embed_dim=getattr(args, "embed_dim", 256))
     elif name in _ON_PATH:
         net = _ON_PATH[name](args.n_class)
+    elif name in _ON_PATH_ARGS:                            # "SNUNet_conc": Siam_NestedUNet_Conc, a name of this project (the reference
+        net = _ON_PATH_ARGS[name](args.n_class, args)      # registers none); multi_scale_train == "True" builds its deep-supervision form
     elif name in _OFF_PATH:
         raise NotImplementedError("Generator model name [%s] is outside the accelerated hot path of this build" % name)
     else:

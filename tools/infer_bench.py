@@ -1,5 +1,5 @@
 """Inference throughput (eval-mode forward, bf16, weights frozen so the filters are packed once): pairs/s for one family.
-python tools/infer_bench.py --model diff|conc|snunet|segcd [--batch 16] [--size 256]"""
+python tools/infer_bench.py --model diff|conc|snunet|snunet_conc|segcd [--batch 16] [--size 256]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,7 +13,7 @@ if a.model == "segcd":
     m = SegCD().to(dev).eval()
 else:
     from stcd_amd import modules
-    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM}[a.model](3, 2).to(dev).eval()
+    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model](3, 2).to(dev).eval()
 x1, x2, _ = synth.make_batch(a.batch, a.size, a.size, seed=5)
 A, B = torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev)
 for frozen in (False, True):

@@ -1,5 +1,5 @@
 """Per-kernel table of one training step through the engine's own HIP-event instrumentation (stcd_profile_*): launches,
-ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|segcd|diff|conc [--batch 16]"""
+ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|snunet_conc|segcd|diff|conc [--batch 16]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,7 +18,7 @@ if a.model == "segcd":
     label = 1
 else:
     from stcd_amd import modules
-    cls = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "sub": modules.SiamUnet_sub, "snunet": modules.SNUNet_ECAM}[a.model]
+    cls = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "sub": modules.SiamUnet_sub, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model]
     m = cls(3, 2).to(dev).train()
     label = 2
 x1, x2, lab = synth.make_batch(a.batch, a.size, a.size, seed=1)

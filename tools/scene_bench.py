@@ -1,5 +1,5 @@
 """Whole-scene inference throughput: predict_scene (tile, forward, stitch on the device) against a host tiler and the bare forward.
-python tools/scene_bench.py --model diff|conc|snunet|segcd [--size 4096] [--tile 256] [--stride 256|128] [--batch 16] [--reps 20]
+python tools/scene_bench.py --model diff|conc|snunet|snunet_conc|segcd [--size 4096] [--tile 256] [--stride 256|128] [--batch 16] [--reps 20]
 
 Three rates, each in megapixels/s of scene and tile-pairs/s:
   device : stcd_amd.scene.predict_scene (bf16 eval forward, frozen weights), flat window, no label; mean of --reps calls in one timed window
@@ -24,7 +24,7 @@ if a.model == "segcd":
     m = SegCD().to(dev).eval()
 else:
     from stcd_amd import modules
-    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM}[a.model](3, 2).to(dev).eval()
+    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model](3, 2).to(dev).eval()
 H = W = a.size
 T, S = a.tile, a.stride
 plan = plan_tiles(H, W, T, S)

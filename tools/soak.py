@@ -14,7 +14,7 @@ if a.model == "segcd":
     m, label = SegCD().to(dev).train(), 1
 else:
     from stcd_amd import modules
-    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM}[a.model](3, 2).to(dev).train(); label = 2
+    m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model](3, 2).to(dev).train(); label = 2
 opt = FlatAdamW(m, lr=1e-3, weight_decay=0.01)
 x1, x2, lab = synth.make_batch(64, 128, 128, seed=5)
 A, B, L = torch.from_numpy(x1).to(dev), torch.from_numpy(x2).to(dev), torch.from_numpy(lab).to(dev)
