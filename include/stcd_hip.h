@@ -74,6 +74,15 @@ extern "C" {
  * own BatchNorm batch statistics, in that order --, change = min(head(dec(|f1 - f2|)), |mask_t1 - mask_t2|).  Same outputs as
  * STCD_ARCH_SEGCD ([3*batch, label_ch, H, W] = mask_t1, mask_t2, change).  STCD_ARCH_FFCTLCD + k, k as above. */
 #define STCD_ARCH_FFCTLCD 32
+/* "base_resnet18" -> ResNet, the CNN baseline of the BIT family (models/networks.py:223-304; define_G name, :172-173): a BasicBlock
+ * ResNet trunk that stays at 1/8 resolution (layer3 / layer4 run at stride 1, dilation 1: models/resnet.py:47-48) shared by both
+ * dates with per-date BatchNorm statistics, nearest x2, conv_pred (3x3, bias, -> 32), |x1 - x2|, bilinear x4 (align_corners =
+ * False), classifier (conv3x3 32 -> 32, BatchNorm over the batch, ReLU, conv3x3 32 -> label_ch with bias); logits [batch,
+ * label_ch, H, W].  STCD_ARCH_BASE_RESNET + k: k = 0 resnet18 / resnet_stages_num 5, 1 resnet18 / 4 (the trunk stops after
+ * layer3), 2 resnet34 / 5, 3 resnet34 / 4.  Every tensor of the class's state_dict is a parameter of the engine, also the ones
+ * no output depends on (resnet.fc.*, resnet.layer4.* at 4 stages): their gradient is exactly zero.  H and W must be divisible
+ * by 32; in_ch must be 3. */
+#define STCD_ARCH_BASE_RESNET 48
 
 /* ChangeFormerV6 (/root/reference/models/ChangeFormer.py:1669-1701; define_G name "ChangeFormerV6", models/networks.py:195-196;
  * BASELINE.json configs[4]): hierarchical transformer encoder shared by both dates + MLP / conv-difference decoder.  Its forward
@@ -219,6 +228,7 @@ int stcd_grad_stage_range(const stcd_engine* e, int stage, int64_t* begin, int64
  *      parity test can check every layer of a deep network IN PLACE (layer output against a convolution of the layer's own
  *      stored input, weight gradient against the stored input and output gradient ...) at per-op tolerance, independent of how
  *      rounding differences grow through the depth.  Filled for the STCD_ARCH_SEGCD* families ("<conv name>.in|.Y|.A|.dY|.dIn|.res")
+ *      (STCD_ARCH_BASE_RESNET also: "conv_pred.in|.Y|.dY|.dIn", no BatchNorm; "upsamplex4.in|.Y|.dY|.dIn", the bilinear step)
  *      and the FC-Siam families ("<conv name>.in|.Y|.A.g0|.A.g1|.dY"; the activation per date); 0 tensors for SNUNet.  NHWC: element (n, y, x, ch) at offset_bytes + (((n*h + y)*w + x)*ld + ch) * elem_size.
  *      stcd_set_debug bit 0 (before stcd_configure): every layer writes its input gradient to a buffer of its own (the
  *      producer gathers it) instead of in place into the producer's gradient tensor, so ".dIn" survives the backward. */

@@ -25,6 +25,7 @@ ARCH_SNUNET_CONC = 11      # Siam_NestedUNet_Conc (SNUNet-CD without attention):
 ARCH_SNUNET_CONC_DS = 12   # ... with deep supervision: [output1..4, output]
 ARCH_UNETSEG = 16          # + 0..4: resnet50, resnet18, resnet34, resnet101, resnet152
 ARCH_FFCTLCD = 32          # + 0..4, same order
+ARCH_BASE_RESNET = 48      # + 0..3: ResNet (base_resnet18, the BIT family's CNN baseline): (resnet18, resnet34) x (5, 4 stages)
 ARCH_CHANGEFORMER = 64     # ChangeFormerV6
 DTYPE_F32, DTYPE_BF16 = 0, 1
 ARCH_IDS = {"diff": ARCH_DIFF, "conc": ARCH_CONC, "sub": ARCH_SUB, "fcef": ARCH_FCEF, "xconc": ARCH_XCONC, "snunet": ARCH_SNUNET, "snunet_conc": ARCH_SNUNET_CONC, "snunet_conc_ds": ARCH_SNUNET_CONC_DS, "segcd": ARCH_SEGCD,
@@ -34,6 +35,8 @@ ARCH_IDS = {"diff": ARCH_DIFF, "conc": ARCH_CONC, "sub": ARCH_SUB, "fcef": ARCH_
             "unetseg_resnet101": ARCH_UNETSEG + 3, "unetseg_resnet152": ARCH_UNETSEG + 4,
             "ffctlcd_resnet50": ARCH_FFCTLCD, "ffctlcd_resnet18": ARCH_FFCTLCD + 1, "ffctlcd_resnet34": ARCH_FFCTLCD + 2,
             "ffctlcd_resnet101": ARCH_FFCTLCD + 3, "ffctlcd_resnet152": ARCH_FFCTLCD + 4,
+            "base_resnet18_s5": ARCH_BASE_RESNET, "base_resnet18_s4": ARCH_BASE_RESNET + 1,
+            "base_resnet34_s5": ARCH_BASE_RESNET + 2, "base_resnet34_s4": ARCH_BASE_RESNET + 3,
             "changeformer": ARCH_CHANGEFORMER}
 DTYPE_IDS = {"fp32": DTYPE_F32, "f32": DTYPE_F32, "bf16": DTYPE_BF16}
 

@@ -167,9 +167,11 @@ struct GLayer {
     int64_t stat = -1, coef = -1, facc = -1, bacc = -1;
     int g_first = 0;                      // BatchNorm group the reference normalises first (running-statistic update order)
 };
-enum GStepKind { GS_LAYER = 0, GS_MAXPOOL = 1, GS_UPSAMPLE = 2, GS_ABSDIFF = 3 };
+enum GStepKind { GS_LAYER = 0, GS_MAXPOOL = 1, GS_UPSAMPLE = 2, GS_ABSDIFF = 3, GS_BCONV = 4, GS_ABSPAIR = 5, GS_BILINEAR = 6 };
 // GS_ABSDIFF (FFCTLCD): images [2B, 3B) of `src` (C channels of a [3B, h, w, ld] tensor) = |date 0 - date 1|; backward: the
 // gradient of that third group (dsrc) becomes a [2B, h, w, C] contribution buffer (ddst) the producer of the two dates gathers
+// base_resnet tail (dsrc / ddst: gradients of src / dst): GS_BCONV = conv_pred, a biased 3x3 conv without BatchNorm over the 2B images
+// of src; GS_ABSPAIR: dst [B] = |date 0 - date 1| of src [2B]; GS_BILINEAR: dst [N, 4h, 4w] = bilinear x4 of src (align_corners = False)
 struct GStep { int kind = GS_LAYER; int layer = -1; TRef src, dst, dsrc, ddst; int N = 0, h = 0, w = 0, C = 0; };
 
 // ---- SNUNet-ECAM plan (SNUNet.py:63-152)
@@ -231,6 +233,12 @@ struct stcd_engine_impl {
     int64_t g_stem_part = -1;                                 // k_stem_wgrad's per-chunk partial filters (fp32 / non-MFMA path: fixed-order finish)
     int64_t g_raw3 = -1, g_draw3 = -1;
     ConvOp g_head_fwd, g_head_dgr; WgradOp g_head_wg;
+    // ---- base_resnet (the BIT family's CNN baseline): SegCD's BasicBlock trunk at stride (1,2,1,1) + the tail above
+    bool bres = false; int seg_nstage = 4;                   // residual stages the forward runs (3: resnet_stages_num == 4)
+    int g_head_c = 16;                                       // input channels of the head conv
+    int g_cls = -1, g_pred_conv = -1;                        // classifier.0 + classifier.1 (one BatchNorm group); conv_pred
+    ConvOp g_pred_fwd, g_pred_dgr; WgradOp g_pred_wg;
+    int64_t g_pred_bias_acc = -1;
     int arch = 0, in_ch = 3, label = 2, dt = F32;
     int64_t min_bn_count = 0;                                // fewest values per channel any BatchNorm layer of the current plan sees
     float drop_p = 0.2f;
@@ -2311,7 +2319,11 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
 static const int RS_PLANES[4] = {64, 128, 256, 512};
 static bool is_unetseg(int arch) { return arch >= STCD_ARCH_UNETSEG && arch <= STCD_ARCH_UNETSEG + 4; }
 static bool is_ffctlcd(int arch) { return arch >= STCD_ARCH_FFCTLCD && arch <= STCD_ARCH_FFCTLCD + 4; }
-static bool is_segcd(int arch) { return (arch >= STCD_ARCH_SEGCD && arch <= STCD_ARCH_SEGCD_R152) || is_unetseg(arch) || is_ffctlcd(arch); }
+static bool is_bres(int arch) { return arch >= STCD_ARCH_BASE_RESNET && arch <= STCD_ARCH_BASE_RESNET + 3; }
+static bool is_segcd(int arch) { return (arch >= STCD_ARCH_SEGCD && arch <= STCD_ARCH_SEGCD_R152) || is_unetseg(arch) || is_ffctlcd(arch) || is_bres(arch); }
+// stride of block b of residual stage li: (1,2,2,2); base_resnet (replace_stride_with_dilation=[False,True,True] on BasicBlock, which
+// keeps dilation 1: models/resnet.py:47-48) stays at 1/8 resolution: (1,2,1,1)
+static int seg_stride(const stcd_engine& e, int li, int b) { return (b == 0 && (e.bres ? li == 1 : li > 0)) ? 2 : 1; }
 
 static const int SEG_DEC[5] = {256, 128, 64, 32, 16};
 
@@ -2332,6 +2344,13 @@ static void segcd_encoder_cfg(stcd_engine& e) {
     e.seg_x = 4;
     e.seg_dates = is_unetseg(e.arch) ? 1 : 2;
     e.seg_ffc = is_ffctlcd(e.arch);
+    e.bres = is_bres(e.arch); e.seg_nstage = 4; e.g_head_c = 16;
+    if (e.bres) {      // STCD_ARCH_BASE_RESNET + k: (resnet18, resnet34) x (5, 4 stages)
+        const int k = e.arch - STCD_ARCH_BASE_RESNET;
+        e.seg_x = 1; e.seg_nstage = (k & 1) ? 3 : 4; e.g_head_c = 32;
+        for (int i = 0; i < 4; ++i) e.seg_layers[i] = (k >> 1) ? L34[i] : L18[i];
+        return;
+    }
     switch (is_unetseg(e.arch) ? e.arch - STCD_ARCH_UNETSEG + STCD_ARCH_SEGCD
             : is_ffctlcd(e.arch) ? e.arch - STCD_ARCH_FFCTLCD + STCD_ARCH_SEGCD : e.arch) {      // same encoder order in every id range
         case STCD_ARCH_SEGCD_R18: e.seg_x = 1; l = L18; break;
@@ -2347,14 +2366,28 @@ static void build_segcd_tables(stcd_engine& e) {
     segcd_encoder_cfg(e);
     const int X = e.seg_x;
     e.g_layers.clear(); e.g_blocks.clear(); e.g_dec.clear();
-    e.g_stem = add_glayer(e, "encoder.conv1", "encoder.bn1", K_STEM7, e.in_ch, 64, true, false);
+    const std::string enc = e.bres ? "resnet." : "encoder.";
+    e.g_stem = add_glayer(e, enc + "conv1", enc + "bn1", K_STEM7, e.in_ch, 64, true, false);
     int inpl = 64;
     for (int li = 0; li < 4; ++li)
         for (int b = 0; b < e.seg_layers[li]; ++b) {
-            const int w = RS_PLANES[li], stride = (b == 0 && li > 0) ? 2 : 1;
-            const std::string pre = "encoder.layer" + std::to_string(li + 1) + "." + std::to_string(b);
+            const int w = RS_PLANES[li], stride = seg_stride(e, li, b);
+            const std::string pre = enc + "layer" + std::to_string(li + 1) + "." + std::to_string(b);
             // ResNet._make_layer (models/resnet.py:165-187): a down-sample where the stride or the width changes
             const bool down = b == 0 && (stride != 1 || inpl != w * X);
+            if (li >= e.seg_nstage) {      // base_resnet with 4 stages: layer4 stays in the state_dict and is never run -- parameters
+                int64_t off;               // only (no layer, no BatchNorm buffer of the engine), their gradient stays zero
+                add_param(e, pre + ".conv1.weight", {w, inpl, 3, 3}, &off);
+                add_param(e, pre + ".bn1.weight", {w}, &off); add_param(e, pre + ".bn1.bias", {w}, &off);
+                add_param(e, pre + ".conv2.weight", {w, w, 3, 3}, &off);
+                add_param(e, pre + ".bn2.weight", {w}, &off); add_param(e, pre + ".bn2.bias", {w}, &off);
+                if (down) {
+                    add_param(e, pre + ".downsample.0.weight", {w, inpl, 1, 1}, &off);
+                    add_param(e, pre + ".downsample.1.weight", {w}, &off); add_param(e, pre + ".downsample.1.bias", {w}, &off);
+                }
+                inpl = w;
+                continue;
+            }
             std::array<int, 4> blk;
             if (X == 4) {      // Bottleneck (models/resnet.py:78-124): 1x1, 3x3 (carries the stride), 1x1
                 blk[0] = add_glayer(e, pre + ".conv1", pre + ".bn1", K_CONV1, inpl, w, true, true);
@@ -2369,6 +2402,17 @@ static void build_segcd_tables(stcd_engine& e) {
             e.g_blocks.push_back(blk);
             inpl = X * w;
         }
+    if (e.bres) {      // registration order of ResNet.__init__ (models/networks.py:231-262): resnet (with its unused fc), classifier, conv_pred
+        int64_t off;
+        add_param(e, "resnet.fc.weight", {1000, 512}, &off);
+        add_param(e, "resnet.fc.bias", {1000}, &off);
+        // TwoLayerConv2d (models/help_funcs.py): conv3x3 without bias, BatchNorm2d, ReLU, conv3x3 with bias; called once per forward
+        e.g_cls = add_glayer(e, "classifier.0", "classifier.1", K_CONV3, 32, 32, true, true, 1);
+        e.g_head_conv = add_conv(e, "classifier.3", K_CONV3, 32, e.label, true, true);
+        e.g_pred_conv = add_conv(e, "conv_pred", K_CONV3, RS_PLANES[e.seg_nstage - 1], 32, true, true);
+        e.enc_param_end = 0;
+        return;
+    }
     const int ENC_OUT[5] = {512 * X, 256 * X, 128 * X, 64 * X, 64};
     int cin = ENC_OUT[0];
     for (int i = 0; i < 5; ++i) {
@@ -2419,10 +2463,10 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     TRef cur = e.gP0; int curC = 64, h = H / 4, w = W / 4, prev_out = -1;      // prev_out: layer whose A is `cur` (-1: the max-pool)
     std::vector<int> stage_out;                                               // L3 of the last block of layer1..4
     size_t bi = 0;
-    for (int li = 0; li < 4; ++li)
+    for (int li = 0; li < e.seg_nstage; ++li)
         for (int b = 0; b < e.seg_layers[li]; ++b, ++bi) {
             const std::array<int, 4>& blk = e.g_blocks[bi];
-            const int stride = (b == 0 && li > 0) ? 2 : 1;
+            const int stride = seg_stride(e, li, b);
             const int ho = h / stride, wo = w / stride;
             GLayer& L1 = e.g_layers[blk[0]]; GLayer& L3 = e.g_layers[blk[2]];
             GLayer* L2 = blk[1] >= 0 ? &e.g_layers[blk[1]] : nullptr;
@@ -2458,6 +2502,26 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             cur = L3.A; curC = L3.C; h = ho; w = wo; prev_out = blk[2];
             if (b == e.seg_layers[li] - 1) stage_out.push_back(blk[2]);
         }
+    if (e.bres) {
+        // ---- base_resnet tail (models/networks.py:267-304): per date nearest x2 + conv_pred, |x1 - x2|, bilinear x4, classifier
+        GLayer& X = e.g_layers[stage_out.back()];
+        X.grad_base = true;                                                                 // the up-sampling gradient alone
+        const int Ct = X.C, h4 = 2 * X.Ho, w4 = 2 * X.Wo;
+        GStep up; up.kind = GS_UPSAMPLE; up.src = X.A; up.dsrc = X.dA; up.dst = plain(N, h4, w4, Ct); up.ddst = plain(N, h4, w4, Ct);
+        up.N = N; up.h = X.Ho; up.w = X.Wo; up.C = Ct; e.g_fwd.push_back(up);
+        GStep cp; cp.kind = GS_BCONV; cp.src = up.dst; cp.dsrc = up.ddst; cp.dst = plain(N, h4, w4, 32); cp.ddst = plain(N, h4, w4, 32);
+        cp.N = N; cp.h = h4; cp.w = w4; cp.C = Ct; e.g_fwd.push_back(cp);
+        GStep ab; ab.kind = GS_ABSPAIR; ab.src = cp.dst; ab.dsrc = cp.ddst; ab.dst = plain(B, h4, w4, 32); ab.ddst = plain(B, h4, w4, 32);
+        ab.N = B; ab.h = h4; ab.w = w4; ab.C = 32; e.g_fwd.push_back(ab);
+        GStep bl; bl.kind = GS_BILINEAR; bl.src = ab.dst; bl.dsrc = ab.ddst; bl.dst = plain(B, H, W, 32); bl.ddst = plain(B, H, W, 32);
+        bl.N = B; bl.h = h4; bl.w = w4; bl.C = 32; e.g_fwd.push_back(bl);
+        GLayer& CL = e.g_layers[e.g_cls];
+        shape(CL, bl.dst, 32, H, W, 1, 1);
+        CL.dIn = bl.ddst; CL.grad_base = true;                                              // dA: the head's data gradient
+        { GStep st; st.layer = e.g_cls; e.g_fwd.push_back(st); }
+        e.gX3 = CL.A; e.gdX3 = CL.dA;
+        e.G = plain(B, H, W, 8);
+    } else {
     // ---- decoder: x = f5; block i: nearest x2 into cat_i[:, :Cx], skip (written by its encoder producer) in cat_i[:, Cx:]
     const int skip_layer[4] = {stage_out[2], stage_out[1], stage_out[0], e.g_stem};          // f4, f3, f2, f1
     int xl = stage_out[3];                                                                  // layer producing x
@@ -2518,12 +2582,14 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         e.g_raw3 = ws.take((int64_t)3 * B * e.label * H * W * 4); e.g_draw3 = ws.take((int64_t)3 * B * e.label * H * W * 4);
     }
     e.G = plain(nhead, H, W, 8);
+    }
     for (auto& L : e.g_layers)
         if ((int)L.extra_dst.size() > MAX_VIEWS || (int)L.grad_src.size() > MAX_VIEWS) { set_error("internal: too many views"); return 1; }
     // ---- zero arena: accumulators, tickets-free (consumer-side tables), bias accumulator of the head
     e.zero_begin = ws.cur;
     for (auto& L : e.g_layers) { L.facc = ws.take(bn_acc_bytes(std::max(2, L.groups), L.C)); L.bacc = ws.take(bn_acc_bytes(std::max(2, L.groups), L.C)); }
     e.final_bias_acc = ws.take(bn_acc_bytes(1, 8));
+    if (e.bres) e.g_pred_bias_acc = ws.take(bn_acc_bytes(1, 32));
     e.zero_end = ws.cur;
     e.scratch8 = ws.take(256);
     e.masks = ws.take(256);
@@ -2688,10 +2754,17 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     }
     {
         const ConvW& cv = e.convs[e.g_head_conv];
-        const int nhead = D == 2 ? 3 * B : B;
-        bind_conv(e.g_head_fwd, geom3(nhead, H, W, 16, 16, e.label, e.label), e.g_head_conv, false, 0, 16, e.label);
-        bind_wgrad(e.g_head_wg, geom3(nhead, H, W, 16, 16, e.label, 8), e.g_head_conv, e.gX3.off, e.G.off);
-        bind_conv(e.g_head_dgr, geom3(nhead, H, W, cv.dgrad.kpad, 8, 16, 16), e.g_head_conv, true, 0, e.label, 16);
+        const int nhead = (D == 2 && !e.bres) ? 3 * B : B, hc = e.g_head_c;
+        bind_conv(e.g_head_fwd, geom3(nhead, H, W, hc, hc, e.label, e.label), e.g_head_conv, false, 0, hc, e.label);
+        bind_wgrad(e.g_head_wg, geom3(nhead, H, W, hc, hc, e.label, 8), e.g_head_conv, e.gX3.off, e.G.off);
+        bind_conv(e.g_head_dgr, geom3(nhead, H, W, cv.dgrad.kpad, 8, hc, hc), e.g_head_conv, true, 0, e.label, hc);
+    }
+    for (const GStep& st : e.g_fwd) {
+        if (st.kind != GS_BCONV) continue;
+        const ConvW& cv = e.convs[e.g_pred_conv];
+        bind_conv(e.g_pred_fwd, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.dst.ld), e.g_pred_conv, false, 0, st.C, 32);
+        bind_wgrad(e.g_pred_wg, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.ddst.ld), e.g_pred_conv, st.src.off, st.ddst.off);
+        bind_conv(e.g_pred_dgr, geom3(st.N, st.h, st.w, cv.dgrad.kpad, st.ddst.ld, st.C, st.dsrc.ld), e.g_pred_conv, true, 0, 32, st.C);
     }
     e.ws_tensors.clear();
     for (const auto& L : e.g_layers) {
@@ -2710,11 +2783,29 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         if (L.has_dIn) rec("dIn", L.dIn, L.N, L.Hi, L.Wi, L.K);
         rec("res", L.res, L.N, L.Ho, L.Wo, L.C);
     }
+    for (const GStep& st : e.g_fwd) {      // the base_resnet steps that are no layer
+        if (st.kind != GS_BCONV && st.kind != GS_BILINEAR) continue;
+        const bool cp = st.kind == GS_BCONV;
+        const int ho = cp ? st.h : 4 * st.h, wo = cp ? st.w : 4 * st.w;
+        auto rec = [&](const char* name, const TRef& t, int h, int w, int c) {
+            stcd_ws_tensor r;
+            memset(&r, 0, sizeof(r));
+            snprintf(r.name, sizeof(r.name), "%s.%s", cp ? "conv_pred" : "upsamplex4", name);
+            r.offset_bytes = t.off; r.n = st.N; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
+            e.ws_tensors.push_back(r);
+        };
+        rec("in", st.src, st.h, st.w, st.C); rec("Y", st.dst, ho, wo, 32);
+        rec("dY", st.ddst, ho, wo, 32); rec("dIn", st.dsrc, st.h, st.w, st.C);
+    }
     e.slab = ws.take(e.slab_floats * 4);
     e.bias_jobs.clear();
     {
         BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.g_head_conv].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
         e.bias_jobs.push_back(jb);
+        if (e.bres && e.dt == BF16) {      // conv_pred's bias gradient: summed in the integer accumulator (launch_bias_grad), converted at the end
+            BiasJob jp{}; jp.acc_off = e.g_pred_bias_acc; jp.out_off = e.convs[e.g_pred_conv].b_off; jp.C = 32; jp.valid = 32; jp.scale = BN_BS;
+            e.bias_jobs.push_back(jp);
+        }
         e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
     }
     build_pack_jobs(e, ws);
@@ -2825,9 +2916,22 @@ static int forward_segcd(stcd_engine& e, const float* x1, const float* x2, const
             const int64_t hw = (int64_t)st.h * st.w;
             launch_fuse(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * hw * st.src.ld,
                         c.at<char>(st.src.off) + (int64_t)2 * st.N * hw * st.src.ld * T, st.src.ld, st.N, hw, st.C, s);
-        } else launch_upsample2(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, st.C, s);
+        } else if (st.kind == GS_BCONV)
+            exec_conv(c, e.g_pred_fwd, c.at(st.src.off), params + e.convs[e.g_pred_conv].b_off, c.at(st.dst.off), false);
+        else if (st.kind == GS_ABSPAIR) {
+            ProfScope ps(c, PC_POOL_FUSE, 0.0, 3.0 * st.N * st.h * st.w * st.C * (double)T, "k_fuse");
+            launch_fuse(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * st.h * st.w * st.src.ld, c.at(st.dst.off), st.dst.ld, st.N,
+                        (int64_t)st.h * st.w, st.C, s);
+        } else if (st.kind == GS_BILINEAR) {
+            ProfScope ps(c, PC_POOL_FUSE, 0.0, 17.0 * st.N * st.h * st.w * st.C * (double)T, "k_bilinear");
+            launch_bilinear(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, 4 * st.h, 4 * st.w, st.C, 0, s);
+        } else if (e.bres) {
+            ProfScope ps(c, PC_POOL_FUSE, 0.0, 5.0 * st.N * st.h * st.w * st.C * (double)T, "k_upsample2");
+            launch_upsample2(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, st.C, s);
+        }
+        else launch_upsample2(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, st.C, s);
     }
-    if (e.seg_dates == 1) {      // UnetSeg: masks = head(decoder output)
+    if (e.seg_dates == 1 || e.bres) {      // UnetSeg: masks = head(decoder output); base_resnet: logits = classifier.3(classifier's ReLU)
         exec_conv(c, e.g_head_fwd, c.at(e.gX3.off), params + e.convs[e.g_head_conv].b_off, logits, true);
         STCD_HIP(hipGetLastError());
         return 0;
@@ -2849,7 +2953,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
     const int64_t T = (int64_t)dsize(dt), HW = (int64_t)e.H * e.W;
     STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
     if (!mfma_on(e)) STCD_HIP(hipMemsetAsync(c.at(e.dwe_begin), 0, e.dwe_end - e.dwe_begin, s));
-    if (e.seg_dates == 1) {
+    if (e.seg_dates == 1 || e.bres) {
         launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
         exec_wgrad(c, e.g_head_wg, c.at(e.gX3.off), c.at(e.G.off));
         exec_conv(c, e.g_head_dgr, c.at(e.G.off), nullptr, c.at(e.gdX3.off), false);
@@ -2872,6 +2976,21 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
             launch_fuse_bwd(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * hw * st.src.ld,
                             c.at<char>(st.dsrc.off) + (int64_t)2 * st.N * hw * st.dsrc.ld * T, st.dsrc.ld,
                             c.at(st.ddst.off), st.ddst.ld, (int64_t)st.N * hw * st.ddst.ld, st.N, hw, st.C, s);
+        }
+        else if (st.kind == GS_BILINEAR) {
+            ProfScope ps(c, PC_POOL_FUSE, 0.0, 17.0 * st.N * st.h * st.w * st.C * (double)T, "k_bilinear_bwd");
+            launch_bilinear_bwd(dt, c.at(st.ddst.off), st.ddst.ld, c.at(st.dsrc.off), st.dsrc.ld, st.N, st.h, st.w, 4 * st.h, 4 * st.w, st.C, 0, s);
+        } else if (st.kind == GS_ABSPAIR) {      // d(x1), d(x2) = +/- sign(x1 - x2) * d|x1 - x2|; sign(0) = 0 as torch.abs
+            const int64_t hw = (int64_t)st.h * st.w;
+            ProfScope ps(c, PC_POOL_FUSE, 0.0, 5.0 * st.N * hw * st.C * (double)T, "k_fuse_bwd");
+            launch_fuse_bwd(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * hw * st.src.ld, c.at(st.ddst.off), st.ddst.ld,
+                            c.at(st.dsrc.off), st.dsrc.ld, (int64_t)st.N * hw * st.dsrc.ld, st.N, hw, st.C, s);
+        } else if (st.kind == GS_BCONV) {
+            { ProfScope ps(c, PC_POOL_FUSE, 0.0, (double)st.N * st.h * st.w * 32 * (double)T, "k_bias_grad");
+            launch_bias_grad(dt, c.at(st.ddst.off), st.ddst.ld, (int64_t)st.N * st.h * st.w, 32, grads + e.convs[e.g_pred_conv].b_off, s,
+                             dt == BF16 ? c.at<long long>(e.g_pred_bias_acc) : nullptr); }
+            exec_wgrad(c, e.g_pred_wg, c.at(st.src.off), c.at(st.ddst.off));
+            exec_conv(c, e.g_pred_dgr, c.at(st.ddst.off), nullptr, c.at(st.dsrc.off), false);
         }
         else {      // max-pool: d(P0) = conv1 contribution (written in place) + identity-branch contribution of layer1.0 (its
                     // down-sample's data gradient for Bottleneck encoders, the gated residual gradient itself for BasicBlock ones)
@@ -3004,7 +3123,7 @@ int stcd_cf_set_drop_rates(stcd_engine* e, float drop_rate, float attn_drop, flo
 int64_t stcd_output_floats(const stcd_engine* e) {
     if (!e || !e->configured) return 0;
     if (e->cf) return e->cf->out_floats;
-    const int maps = (is_segcd(e->arch) && !is_unetseg(e->arch)) ? 3 : sn_out_maps(e->arch);
+    const int maps = (is_segcd(e->arch) && !is_unetseg(e->arch) && !is_bres(e->arch)) ? 3 : sn_out_maps(e->arch);
     return (int64_t)maps * e->B * e->label * e->H * e->W;
 }
 int stcd_cf_output_info(const stcd_engine* e, int i, int64_t* offset, int* height, int* width) {
@@ -3022,7 +3141,8 @@ int stcd_create(int arch, int in_ch, int label_ch, int dtype, stcd_engine** out)
         cfg.in_ch = in_ch; cfg.out_ch = label_ch;
         return stcd_create_changeformer(&cfg, dtype, out);
     }
-    STCD_CHECK((arch >= STCD_ARCH_DIFF && arch <= STCD_ARCH_SEGCD_R152) || arch == STCD_ARCH_FCEF || arch == STCD_ARCH_XCONC || is_snconc(arch) || is_unetseg(arch) || is_ffctlcd(arch), "unknown arch");
+    STCD_CHECK((arch >= STCD_ARCH_DIFF && arch <= STCD_ARCH_SEGCD_R152) || arch == STCD_ARCH_FCEF || arch == STCD_ARCH_XCONC || is_snconc(arch) || is_unetseg(arch) || is_ffctlcd(arch) || is_bres(arch), "unknown arch");
+    STCD_CHECK(!is_bres(arch) || in_ch == 3, "base_resnet: in_ch must be 3 (the reference's resnet.conv1 always takes 3 channels, models/networks.py:234)");
     STCD_CHECK(arch != STCD_ARCH_FCEF || in_ch <= 4, "FC-EF concatenates the two dates along the channels: in_ch must be <= 4");
     STCD_CHECK(in_ch >= 1 && in_ch <= 8, "in_ch must be in [1,8]");
     STCD_CHECK(label_ch >= 1 && label_ch <= 8, "label_ch must be in [1,8]");
@@ -3076,6 +3196,7 @@ int stcd_configure(stcd_engine* e, int batch, int height, int width) {
         STCD_CHECK(height % 16 == 0 && width % 16 == 0, "SNUNet needs height and width divisible by 16 (the reference's cat of up-sampled maps fails otherwise)");
         if (configure_snunet(*e, batch, height, width)) return 1;
     } else if (is_segcd(e->arch)) {
+        STCD_CHECK(!is_bres(e->arch) || (height % 32 == 0 && width % 32 == 0), "base_resnet needs height and width divisible by 32 (the engine's rule: 1/8-resolution trunk, row tiles of 4 pixels at that level)");
         STCD_CHECK(height % 32 == 0 && width % 32 == 0, "SegCD needs height and width divisible by 32 (five stride-2 stages; the reference's cat of the x2 up-sampled maps fails otherwise)");
         STCD_CHECK((int64_t)3 * batch * height * width * 16 < ((int64_t)1 << 31), "tensor too large for 32-bit pixel indexing");
         if (configure_segcd(*e, batch, height, width)) return 1;

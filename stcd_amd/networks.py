@@ -18,7 +18,7 @@ _ON_PATH = {
     "SiamUnet_cross_conc": lambda n: SiamUnet_cross_conc(input_nbr=3, label_nbr=n),   # :152-153
 }
 _ON_PATH_ARGS = {}      # builders that also read the run's arguments
-_OFF_PATH = ("DTCDSCN", "IFNet", "base_resnet18", "base_transformer_pos_s4",
+_OFF_PATH = ("DTCDSCN", "IFNet", "base_transformer_pos_s4",
              "base_transformer_pos_s4_dd8", "base_transformer_pos_s4_dd8_dedim8", "ChangeFormerV1", "ChangeFormerV2",
              "ChangeFormerV3", "ChangeFormerV4", "ChangeFormerV5", "ChangeGNNV1", "ChangeGNNV2",
              "ChangeGNNV2_sub", "ChangeGNNV2_abs", "ChangeGNNV2_conc", "GNN")
@@ -37,6 +37,13 @@ def _register_snunet():
 
 
 _register_snunet()
+
+
+def __getattr__(name):
+    if name == "ResNet":          # re-exported like the reference's module does; imported lazily (stcd_amd.bit pulls in segcd's holders)
+        from .bit import ResNet
+        return ResNet
+    raise AttributeError(name)
 
 
 def get_scheduler(optimizer, args):
@@ -100,6 +107,9 @@ def define_G(args, init_type="normal", init_gain=0.02, gpu_ids=[]):
     if name == "ChangeFormerV6":                           # networks.py:195-196: ChangeFormerV6(embed_dim=args.embed_dim), two classes
         from .changeformer import ChangeFormerV6
         net = ChangeFormerV6(embed_dim=getattr(args, "embed_dim", 256))
+    elif name == "base_resnet18":                          # networks.py:172-173: ignores args.n_class
+        from .bit import ResNet
+        net = ResNet(input_nc=3, output_nc=2, output_sigmoid=False)
     elif name in _ON_PATH:
         net = _ON_PATH[name](args.n_class)
     elif name in _ON_PATH_ARGS:                            # "SNUNet_conc": Siam_NestedUNet_Conc, a name of this project (the reference

@@ -1,5 +1,5 @@
 """Inference throughput (eval-mode forward, bf16, weights frozen so the filters are packed once): pairs/s for one family.
-python tools/infer_bench.py --model diff|conc|snunet|snunet_conc|segcd [--batch 16] [--size 256]"""
+python tools/infer_bench.py --model diff|conc|snunet|snunet_conc|segcd|base_resnet18|base_resnet18_s4 [--batch 16] [--size 256]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -11,6 +11,9 @@ dev = "cuda:0"
 if a.model == "segcd":
     from stcd_amd.segcd import SegCD
     m = SegCD().to(dev).eval()
+elif a.model in ("base_resnet18", "base_resnet18_s4"):
+    from stcd_amd.bit import ResNet
+    m = ResNet(3, 2, resnet_stages_num=4 if a.model.endswith("_s4") else 5).to(dev).eval()
 else:
     from stcd_amd import modules
     m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model](3, 2).to(dev).eval()

@@ -1,5 +1,5 @@
 """Per-kernel table of one training step through the engine's own HIP-event instrumentation (stcd_profile_*): launches,
-ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|snunet_conc|segcd|diff|conc [--batch 16]"""
+ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|snunet_conc|segcd|base_resnet18|base_resnet18_s4|diff|conc [--batch 16]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +16,10 @@ if a.model == "segcd":
     from stcd_amd.segcd import SegCD
     m = SegCD().to(dev).train()
     label = 1
+elif a.model in ("base_resnet18", "base_resnet18_s4"):
+    from stcd_amd.bit import ResNet
+    m = ResNet(3, 2, resnet_stages_num=4 if a.model.endswith("_s4") else 5).to(dev).train()
+    label = 2
 else:
     from stcd_amd import modules
     cls = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "sub": modules.SiamUnet_sub, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model]

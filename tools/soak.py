@@ -12,6 +12,9 @@ dev = "cuda:0"
 if a.model == "segcd":
     from stcd_amd.segcd import SegCD
     m, label = SegCD().to(dev).train(), 1
+elif a.model in ("base_resnet18", "base_resnet18_s4"):
+    from stcd_amd.bit import ResNet
+    m, label = ResNet(3, 2, resnet_stages_num=4 if a.model.endswith("_s4") else 5).to(dev).train(), 2
 else:
     from stcd_amd import modules
     m = {"diff": modules.SiamUnet_diff, "conc": modules.SiamUnet_conc, "snunet": modules.SNUNet_ECAM, "snunet_conc": modules.Siam_NestedUNet_Conc}[a.model](3, 2).to(dev).train(); label = 2
