@@ -83,6 +83,14 @@ extern "C" {
  * no output depends on (resnet.fc.*, resnet.layer4.* at 4 stages): their gradient is exactly zero.  H and W must be divisible
  * by 32; in_ch must be 3. */
 #define STCD_ARCH_BASE_RESNET 48
+/* BIT: BASE_Transformer (models/networks.py:307-441) = the trunk above (resnet18, resnet_stages_num 4) with the token path between
+ * conv_pred and |x1 - x2|: semantic tokenizer (conv_a 1x1 32 -> 4 without bias, softmax over the positions of an image, 4 tokens per
+ * date), one token-encoder layer over the 8 tokens of a pair (+ pos_embedding; 8 heads, dim_head 64), and a cross-attention decoder
+ * over every pixel of each date with that date's 4 tokens as memory.  Both attentions scale by dim ** -0.5 = 32 ** -0.5.
+ * STCD_ARCH_BIT + k: k = 0 dec_depth 1 / decoder_dim_head 64 ("base_transformer_pos_s4"), 1: 8 / 64 ("..._dd8"), 2: 8 / 8
+ * ("..._dd8_dedim8").  The parameter table is in named_parameters() order: pos_embedding first (flat offset 0), then the trunk's
+ * tensors, conv_a.weight, transformer.layers.0.*, transformer_decoder.layers.*.  logits [batch, label_ch, H, W]. */
+#define STCD_ARCH_BIT 52
 
 /* ChangeFormerV6 (/root/reference/models/ChangeFormer.py:1669-1701; define_G name "ChangeFormerV6", models/networks.py:195-196;
  * BASELINE.json configs[4]): hierarchical transformer encoder shared by both dates + MLP / conv-difference decoder.  Its forward
@@ -228,7 +236,10 @@ int stcd_grad_stage_range(const stcd_engine* e, int stage, int64_t* begin, int64
  *      parity test can check every layer of a deep network IN PLACE (layer output against a convolution of the layer's own
  *      stored input, weight gradient against the stored input and output gradient ...) at per-op tolerance, independent of how
  *      rounding differences grow through the depth.  Filled for the STCD_ARCH_SEGCD* families ("<conv name>.in|.Y|.A|.dY|.dIn|.res")
- *      (STCD_ARCH_BASE_RESNET also: "conv_pred.in|.Y|.dY|.dIn", no BatchNorm; "upsamplex4.in|.Y|.dY|.dIn", the bilinear step)
+ *      (STCD_ARCH_BASE_RESNET also: "conv_pred.in|.Y|.dY|.dIn", no BatchNorm; "upsamplex4.in|.Y|.dY|.dIn", the bilinear step;
+ *      STCD_ARCH_BIT also, always fp32 for the tokens: "bit.tokens.in|.Y|.dY|.dIn" [2*batch, 1, 4, 32], the tokens before / after the
+ *      encoder and their gradients, and "bit.dec.in|.Y|.dY|.dIn", the decoder's maps -- conv_pred.dY = bit.dec.dIn + the tokenizer's
+ *      data gradient)
  *      and the FC-Siam families ("<conv name>.in|.Y|.A.g0|.A.g1|.dY"; the activation per date); 0 tensors for SNUNet.  NHWC: element (n, y, x, ch) at offset_bytes + (((n*h + y)*w + x)*ld + ch) * elem_size.
  *      stcd_set_debug bit 0 (before stcd_configure): every layer writes its input gradient to a buffer of its own (the
  *      producer gathers it) instead of in place into the producer's gradient tensor, so ".dIn" survives the backward. */

@@ -5,16 +5,16 @@ host-side mirror of the reference's Python interface for the path (model classes
 ``CDTrainer``).  Importing the package does not touch the GPU or load the library; the first model
 construction does, and raises if the library has not been built.
 """
-__all__ = ["SiamUnet_diff", "SiamUnet_conc", "SiamUnet_sub", "SNUNet_ECAM", "Siam_NestedUNet_Conc", "SegCD", "UnetSeg", "FFCTLCD", "ResNet"]
+__all__ = ["SiamUnet_diff", "SiamUnet_conc", "SiamUnet_sub", "SNUNet_ECAM", "Siam_NestedUNet_Conc", "SegCD", "UnetSeg", "FFCTLCD", "ResNet", "BASE_Transformer"]
 
 
 def __getattr__(name):
     if name in ("SegCD", "UnetSeg", "FFCTLCD"):
         from . import segcd
         return getattr(segcd, name)
-    if name == "ResNet":
+    if name in ("ResNet", "BASE_Transformer"):
         from . import bit
-        return bit.ResNet
+        return getattr(bit, name)
     if name in __all__:
         from . import modules
         return getattr(modules, name)

@@ -26,6 +26,7 @@ ARCH_SNUNET_CONC_DS = 12   # ... with deep supervision: [output1..4, output]
 ARCH_UNETSEG = 16          # + 0..4: resnet50, resnet18, resnet34, resnet101, resnet152
 ARCH_FFCTLCD = 32          # + 0..4, same order
 ARCH_BASE_RESNET = 48      # + 0..3: ResNet (base_resnet18, the BIT family's CNN baseline): (resnet18, resnet34) x (5, 4 stages)
+ARCH_BIT = 52              # + 0..2: BASE_Transformer (resnet18, 4 stages): (dec_depth, decoder_dim_head) = (1, 64), (8, 64), (8, 8)
 ARCH_CHANGEFORMER = 64     # ChangeFormerV6
 DTYPE_F32, DTYPE_BF16 = 0, 1
 ARCH_IDS = {"diff": ARCH_DIFF, "conc": ARCH_CONC, "sub": ARCH_SUB, "fcef": ARCH_FCEF, "xconc": ARCH_XCONC, "snunet": ARCH_SNUNET, "snunet_conc": ARCH_SNUNET_CONC, "snunet_conc_ds": ARCH_SNUNET_CONC_DS, "segcd": ARCH_SEGCD,
@@ -37,6 +38,7 @@ ARCH_IDS = {"diff": ARCH_DIFF, "conc": ARCH_CONC, "sub": ARCH_SUB, "fcef": ARCH_
             "ffctlcd_resnet101": ARCH_FFCTLCD + 3, "ffctlcd_resnet152": ARCH_FFCTLCD + 4,
             "base_resnet18_s5": ARCH_BASE_RESNET, "base_resnet18_s4": ARCH_BASE_RESNET + 1,
             "base_resnet34_s5": ARCH_BASE_RESNET + 2, "base_resnet34_s4": ARCH_BASE_RESNET + 3,
+            "bit_s4_dd1_dh64": ARCH_BIT, "bit_s4_dd8_dh64": ARCH_BIT + 1, "bit_s4_dd8_dh8": ARCH_BIT + 2,
             "changeformer": ARCH_CHANGEFORMER}
 DTYPE_IDS = {"fp32": DTYPE_F32, "f32": DTYPE_F32, "bf16": DTYPE_BF16}
 

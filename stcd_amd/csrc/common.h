@@ -602,6 +602,25 @@ struct SelftrainPtrs { const float* p[STCD_SELFTRAIN_MAX_MODELS]; };
 void launch_selftrain_score(const SelftrainPtrs& lg, int n_models, int batch, int classes, int64_t hw, float threshold, const uint8_t* label,
                             int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, hipStream_t s);
 
+// ---- BIT token path (kernels_bit.hip): tokenizer, token encoder, folded cross-attention decoder.  NI = 2 * batch images (date-major),
+//      n = pixel rows per image, every map [NI, n, 32] with pixel stride 32; tokens, folded matrices and partial sums are fp32.
+//      lp / dp: the encoder layer's / the decoder's first layer's parameter block inside the flat parameters (g_*: inside the gradients).
+int64_t bit_layer_floats(int dh);
+int64_t bit_enc_part_floats(int B, int dh);
+int64_t bit_dec_part_floats(int n, int NI, int L);
+void launch_bit_tok_fwd(int dt, const void* x, const float* wa, float* tok, float* stat, int NI, int n, hipStream_t s);
+void launch_bit_tok_bwd(int dt, const void* x, const float* wa, const float* stat, const float* dtok, const void* dec_din, void* dx,
+                        float* part, float* dwa, int NI, int n, hipStream_t s);
+void launch_bit_enc_fwd(const float* tok_in, const float* pos, const float* lp, float* tok_out, int B, int dh, hipStream_t s);
+void launch_bit_enc_bwd(const float* tok_in, const float* pos, const float* lp, const float* dtok_out, float* dtok_in, float* part,
+                        float* g_lp, float* g_pos, int B, int dh, hipStream_t s);
+void launch_bit_dec_fold(const float* tok, const float* dp, float* AP, int NI, int L, int dh, hipStream_t s);
+void launch_bit_dec_fwd(int dt, const void* src, void* dst, void* xs, const float* AP, const float* dp, int n, int NI, int L, int dh, hipStream_t s);
+int launch_bit_dec_bwd(int dt, const void* src, const void* xs, const void* ddst, float* dG, void* dIn, const float* AP, const float* dp,
+                        float* part, int n, int NI, int L, int dh, hipStream_t s);
+void launch_bit_dec_finish(const float* part, float* dAP, const float* tok, const float* dp, float* gdp, float* dmh, float* dm, float* dtok,
+                           int n, int NI, int L, int dh, hipStream_t s);
+
 // ---- ChangeFormer (transformer) kernels, kernels_tf.hip.  Tokens are NHWC pixels: a [n, N = h*w, C] sequence IS the
 //      [n, h, w, C] map.  Every Dropout / DropPath site draws its mask from a counter hash of (site seed, element index in the
 //      layout named at the launcher), so no mask is ever stored: the backward recomputes it.

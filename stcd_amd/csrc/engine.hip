@@ -167,11 +167,15 @@ struct GLayer {
     int64_t stat = -1, coef = -1, facc = -1, bacc = -1;
     int g_first = 0;                      // BatchNorm group the reference normalises first (running-statistic update order)
 };
-enum GStepKind { GS_LAYER = 0, GS_MAXPOOL = 1, GS_UPSAMPLE = 2, GS_ABSDIFF = 3, GS_BCONV = 4, GS_ABSPAIR = 5, GS_BILINEAR = 6 };
+enum GStepKind { GS_LAYER = 0, GS_MAXPOOL = 1, GS_UPSAMPLE = 2, GS_ABSDIFF = 3, GS_BCONV = 4, GS_ABSPAIR = 5, GS_BILINEAR = 6,
+                 GS_TOKENIZE = 7, GS_TOKENENC = 8, GS_TOKENDEC = 9 };
 // GS_ABSDIFF (FFCTLCD): images [2B, 3B) of `src` (C channels of a [3B, h, w, ld] tensor) = |date 0 - date 1|; backward: the
 // gradient of that third group (dsrc) becomes a [2B, h, w, C] contribution buffer (ddst) the producer of the two dates gathers
 // base_resnet tail (dsrc / ddst: gradients of src / dst): GS_BCONV = conv_pred, a biased 3x3 conv without BatchNorm over the 2B images
 // of src; GS_ABSPAIR: dst [B] = |date 0 - date 1| of src [2B]; GS_BILINEAR: dst [N, 4h, 4w] = bilinear x4 of src (align_corners = False)
+// BIT token path between GS_BCONV and GS_ABSPAIR (kernels_bit.hip; state in stcd_engine_impl::bit): GS_TOKENIZE: tokens of the 2B images of
+// src (its backward adds the tokenizer's data gradient to the decoder's and writes conv_pred's ddst = dsrc); GS_TOKENENC: the
+// token-encoder layer per pair; GS_TOKENDEC: dst = the decoder over src with the encoded tokens (backward: ddst -> bit.dec_din)
 struct GStep { int kind = GS_LAYER; int layer = -1; TRef src, dst, dsrc, ddst; int N = 0, h = 0, w = 0, C = 0; };
 
 // ---- SNUNet-ECAM plan (SNUNet.py:63-152)
@@ -239,6 +243,14 @@ struct stcd_engine_impl {
     int g_cls = -1, g_pred_conv = -1;                        // classifier.0 + classifier.1 (one BatchNorm group); conv_pred
     ConvOp g_pred_fwd, g_pred_dgr; WgradOp g_pred_wg;
     int64_t g_pred_bias_acc = -1;
+    // ---- BIT (BASE_Transformer): the token path between conv_pred and the differencing
+    struct BitPlan {
+        bool on = false; int L = 1, dh = 64;                 // decoder depth, decoder dim_head (the encoder: one layer, dim_head 64)
+        int64_t pos_off = 0, wa_off = 0, enc_off = 0, dec_off = 0;      // flat parameter offsets (elements)
+        int64_t tok_in = -1, tok_out = -1, dtok_out = -1, dtok_in = -1, stat = -1, AP = -1, dAP = -1, xs = -1, dG = -1, dec_part = -1,
+                dmh = -1, dm = -1, enc_part = -1, tok_part = -1;        // workspace byte offsets
+        TRef dec_din;
+    } bit;
     int arch = 0, in_ch = 3, label = 2, dt = F32;
     int64_t min_bn_count = 0;                                // fewest values per channel any BatchNorm layer of the current plan sees
     float drop_p = 0.2f;
@@ -2319,7 +2331,8 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
 static const int RS_PLANES[4] = {64, 128, 256, 512};
 static bool is_unetseg(int arch) { return arch >= STCD_ARCH_UNETSEG && arch <= STCD_ARCH_UNETSEG + 4; }
 static bool is_ffctlcd(int arch) { return arch >= STCD_ARCH_FFCTLCD && arch <= STCD_ARCH_FFCTLCD + 4; }
-static bool is_bres(int arch) { return arch >= STCD_ARCH_BASE_RESNET && arch <= STCD_ARCH_BASE_RESNET + 3; }
+static bool is_bit(int arch) { return arch >= STCD_ARCH_BIT && arch <= STCD_ARCH_BIT + 2; }
+static bool is_bres(int arch) { return (arch >= STCD_ARCH_BASE_RESNET && arch <= STCD_ARCH_BASE_RESNET + 3) || is_bit(arch); }
 static bool is_segcd(int arch) { return (arch >= STCD_ARCH_SEGCD && arch <= STCD_ARCH_SEGCD_R152) || is_unetseg(arch) || is_ffctlcd(arch) || is_bres(arch); }
 // stride of block b of residual stage li: (1,2,2,2); base_resnet (replace_stride_with_dilation=[False,True,True] on BasicBlock, which
 // keeps dilation 1: models/resnet.py:47-48) stays at 1/8 resolution: (1,2,1,1)
@@ -2345,8 +2358,10 @@ static void segcd_encoder_cfg(stcd_engine& e) {
     e.seg_dates = is_unetseg(e.arch) ? 1 : 2;
     e.seg_ffc = is_ffctlcd(e.arch);
     e.bres = is_bres(e.arch); e.seg_nstage = 4; e.g_head_c = 16;
-    if (e.bres) {      // STCD_ARCH_BASE_RESNET + k: (resnet18, resnet34) x (5, 4 stages)
-        const int k = e.arch - STCD_ARCH_BASE_RESNET;
+    if (e.bres) {      // STCD_ARCH_BASE_RESNET + k: (resnet18, resnet34) x (5, 4 stages); STCD_ARCH_BIT + k: resnet18, 4 stages
+        e.bit.on = is_bit(e.arch);
+        if (e.bit.on) { e.bit.L = e.arch == STCD_ARCH_BIT ? 1 : 8; e.bit.dh = e.arch == STCD_ARCH_BIT + 2 ? 8 : 64; }
+        const int k = e.bit.on ? 1 : e.arch - STCD_ARCH_BASE_RESNET;
         e.seg_x = 1; e.seg_nstage = (k & 1) ? 3 : 4; e.g_head_c = 32;
         for (int i = 0; i < 4; ++i) e.seg_layers[i] = (k >> 1) ? L34[i] : L18[i];
         return;
@@ -2367,6 +2382,7 @@ static void build_segcd_tables(stcd_engine& e) {
     const int X = e.seg_x;
     e.g_layers.clear(); e.g_blocks.clear(); e.g_dec.clear();
     const std::string enc = e.bres ? "resnet." : "encoder.";
+    if (e.bit.on) add_param(e, "pos_embedding", {1, 8, 32}, &e.bit.pos_off);      // a parameter of the root module: first in named_parameters()
     e.g_stem = add_glayer(e, enc + "conv1", enc + "bn1", K_STEM7, e.in_ch, 64, true, false);
     int inpl = 64;
     for (int li = 0; li < 4; ++li)
@@ -2411,6 +2427,28 @@ static void build_segcd_tables(stcd_engine& e) {
         e.g_head_conv = add_conv(e, "classifier.3", K_CONV3, 32, e.label, true, true);
         e.g_pred_conv = add_conv(e, "conv_pred", K_CONV3, RS_PLANES[e.seg_nstage - 1], 32, true, true);
         e.enc_param_end = 0;
+        if (e.bit.on) {      // BASE_Transformer.__init__ (models/networks.py:324-357): conv_a, transformer, transformer_decoder
+            int64_t off;
+            add_param(e, "conv_a.weight", {4, 32, 1, 1}, &e.bit.wa_off);
+            auto layer = [&](const std::string& pre, int I, bool cross) {      // the block kernels_bit.hip's bit_off() describes
+                int64_t first;
+                add_param(e, pre + "0.fn.norm.weight", {32}, &first); add_param(e, pre + "0.fn.norm.bias", {32}, &off);
+                if (cross) {
+                    add_param(e, pre + "0.fn.fn.to_q.weight", {I, 32}, &off); add_param(e, pre + "0.fn.fn.to_k.weight", {I, 32}, &off);
+                    add_param(e, pre + "0.fn.fn.to_v.weight", {I, 32}, &off);
+                } else add_param(e, pre + "0.fn.fn.to_qkv.weight", {3 * I, 32}, &off);
+                add_param(e, pre + "0.fn.fn.to_out.0.weight", {32, I}, &off); add_param(e, pre + "0.fn.fn.to_out.0.bias", {32}, &off);
+                add_param(e, pre + "1.fn.norm.weight", {32}, &off); add_param(e, pre + "1.fn.norm.bias", {32}, &off);
+                add_param(e, pre + "1.fn.fn.net.0.weight", {64, 32}, &off); add_param(e, pre + "1.fn.fn.net.0.bias", {64}, &off);
+                add_param(e, pre + "1.fn.fn.net.3.weight", {32, 64}, &off); add_param(e, pre + "1.fn.fn.net.3.bias", {32}, &off);
+                return first;
+            };
+            e.bit.enc_off = layer("transformer.layers.0.", 512, false);
+            for (int l = 0; l < e.bit.L; ++l) {
+                const int64_t o = layer("transformer_decoder.layers." + std::to_string(l) + ".", 8 * e.bit.dh, true);
+                if (l == 0) e.bit.dec_off = o;
+            }
+        }
         return;
     }
     const int ENC_OUT[5] = {512 * X, 256 * X, 128 * X, 64 * X, 64};
@@ -2511,7 +2549,28 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         up.N = N; up.h = X.Ho; up.w = X.Wo; up.C = Ct; e.g_fwd.push_back(up);
         GStep cp; cp.kind = GS_BCONV; cp.src = up.dst; cp.dsrc = up.ddst; cp.dst = plain(N, h4, w4, 32); cp.ddst = plain(N, h4, w4, 32);
         cp.N = N; cp.h = h4; cp.w = w4; cp.C = Ct; e.g_fwd.push_back(cp);
-        GStep ab; ab.kind = GS_ABSPAIR; ab.src = cp.dst; ab.dsrc = cp.ddst; ab.dst = plain(B, h4, w4, 32); ab.ddst = plain(B, h4, w4, 32);
+        TRef pair_src = cp.dst, pair_dsrc = cp.ddst;      // what |x1 - x2| reads and where its backward writes
+        if (e.bit.on) {      // tokenizer -> token encoder -> decoder; the differencing then reads the decoder's output
+            auto& b = e.bit;
+            const int n = h4 * w4, L = b.L;
+            b.tok_in = ws.take((int64_t)N * 128 * 4); b.tok_out = ws.take((int64_t)N * 128 * 4);
+            b.dtok_out = ws.take((int64_t)N * 128 * 4); b.dtok_in = ws.take((int64_t)N * 128 * 4);
+            b.stat = ws.take((int64_t)N * 8 * 4);
+            b.AP = ws.take((int64_t)L * N * 2048 * 4); b.dAP = ws.take((int64_t)L * N * 2048 * 4);
+            b.xs = ws.take((int64_t)std::max(1, L - 1) * N * n * 32 * T);
+            b.dG = ws.take((int64_t)N * n * 32 * 4);
+            b.dec_part = ws.take(bit_dec_part_floats(n, N, L) * 4);
+            b.dmh = ws.take((int64_t)L * N * 8 * 128 * 4); b.dm = ws.take((int64_t)L * N * 128 * 4);
+            b.enc_part = ws.take(bit_enc_part_floats(B, 64) * 4);
+            b.tok_part = ws.take((int64_t)N * 128 * 4);
+            b.dec_din = plain(N, h4, w4, 32);
+            GStep tk; tk.kind = GS_TOKENIZE; tk.src = cp.dst; tk.dsrc = cp.ddst; tk.N = N; tk.h = h4; tk.w = w4; tk.C = 32; e.g_fwd.push_back(tk);
+            GStep te; te.kind = GS_TOKENENC; te.N = N; e.g_fwd.push_back(te);
+            GStep td; td.kind = GS_TOKENDEC; td.src = cp.dst; td.dsrc = b.dec_din; td.dst = plain(N, h4, w4, 32); td.ddst = plain(N, h4, w4, 32);
+            td.N = N; td.h = h4; td.w = w4; td.C = 32; e.g_fwd.push_back(td);
+            pair_src = td.dst; pair_dsrc = td.ddst;      // the differencing reads the decoder's output, not conv_pred's
+        }
+        GStep ab; ab.kind = GS_ABSPAIR; ab.src = pair_src; ab.dsrc = pair_dsrc; ab.dst = plain(B, h4, w4, 32); ab.ddst = plain(B, h4, w4, 32);
         ab.N = B; ab.h = h4; ab.w = w4; ab.C = 32; e.g_fwd.push_back(ab);
         GStep bl; bl.kind = GS_BILINEAR; bl.src = ab.dst; bl.dsrc = ab.ddst; bl.dst = plain(B, H, W, 32); bl.ddst = plain(B, H, W, 32);
         bl.N = B; bl.h = h4; bl.w = w4; bl.C = 32; e.g_fwd.push_back(bl);
@@ -2797,6 +2856,20 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         rec("in", st.src, st.h, st.w, st.C); rec("Y", st.dst, ho, wo, 32);
         rec("dY", st.ddst, ho, wo, 32); rec("dIn", st.dsrc, st.h, st.w, st.C);
     }
+    for (const GStep& st : e.g_fwd) {      // the BIT token path: the decoder's maps and the tokens around the encoder (fp32)
+        if (st.kind != GS_TOKENDEC) continue;
+        auto rec = [&](const char* name, int64_t off, int n, int h, int w, int dtype) {
+            stcd_ws_tensor r;
+            memset(&r, 0, sizeof(r));
+            snprintf(r.name, sizeof(r.name), "%s", name);
+            r.offset_bytes = off; r.n = n; r.h = h; r.w = w; r.c = 32; r.ld = 32; r.dtype = dtype;
+            e.ws_tensors.push_back(r);
+        };
+        rec("bit.dec.in", st.src.off, st.N, st.h, st.w, e.dt); rec("bit.dec.Y", st.dst.off, st.N, st.h, st.w, e.dt);
+        rec("bit.dec.dY", st.ddst.off, st.N, st.h, st.w, e.dt); rec("bit.dec.dIn", st.dsrc.off, st.N, st.h, st.w, e.dt);
+        rec("bit.tokens.in", e.bit.tok_in, st.N, 1, 4, F32); rec("bit.tokens.Y", e.bit.tok_out, st.N, 1, 4, F32);
+        rec("bit.tokens.dY", e.bit.dtok_out, st.N, 1, 4, F32); rec("bit.tokens.dIn", e.bit.dtok_in, st.N, 1, 4, F32);
+    }
     e.slab = ws.take(e.slab_floats * 4);
     e.bias_jobs.clear();
     {
@@ -2922,6 +2995,19 @@ static int forward_segcd(stcd_engine& e, const float* x1, const float* x2, const
             ProfScope ps(c, PC_POOL_FUSE, 0.0, 3.0 * st.N * st.h * st.w * st.C * (double)T, "k_fuse");
             launch_fuse(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * st.h * st.w * st.src.ld, c.at(st.dst.off), st.dst.ld, st.N,
                         (int64_t)st.h * st.w, st.C, s);
+        } else if (st.kind == GS_TOKENIZE) {
+            ProfScope ps(c, PC_POOL_FUSE, 16.0 * 32 * st.N * st.h * st.w, 2.0 * st.N * st.h * st.w * 32 * (double)T, "k_bit_tok_fwd");
+            launch_bit_tok_fwd(dt, c.at(st.src.off), params + e.bit.wa_off, c.at<float>(e.bit.tok_in), c.at<float>(e.bit.stat), st.N, st.h * st.w, s);
+        } else if (st.kind == GS_TOKENENC) {
+            { ProfScope ps(c, PC_POOL_FUSE, 2.0 * B * 8 * (4.0 * 512 * 32 + 2.0 * 32 * 64), 4.0 * bit_layer_floats(64), "k_bit_enc<false>");
+            launch_bit_enc_fwd(c.at<float>(e.bit.tok_in), params + e.bit.pos_off, params + e.bit.enc_off, c.at<float>(e.bit.tok_out), B, 64, s); }
+            ProfScope ps(c, PC_POOL_FUSE, 2.0 * e.bit.L * st.N * 4.0 * 8 * e.bit.dh * 32 * 4, 4.0 * e.bit.L * (bit_layer_floats(e.bit.dh) + st.N * 2048.0), "k_bit_dec_fold");
+            launch_bit_dec_fold(c.at<float>(e.bit.tok_out), params + e.bit.dec_off, c.at<float>(e.bit.AP), st.N, e.bit.L, e.bit.dh, s);
+        } else if (st.kind == GS_TOKENDEC) {
+            const double rows = (double)st.N * st.h * st.w;
+            ProfScope ps(c, PC_POOL_FUSE, 12288.0 * e.bit.L * rows, (training ? e.bit.L + 1.0 : 2.0) * rows * 32 * (double)T, "k_bit_dec_fwd");
+            launch_bit_dec_fwd(dt, c.at(st.src.off), c.at(st.dst.off), training ? c.at(e.bit.xs) : nullptr, c.at<float>(e.bit.AP),
+                               params + e.bit.dec_off, st.h * st.w, st.N, e.bit.L, e.bit.dh, s);
         } else if (st.kind == GS_BILINEAR) {
             ProfScope ps(c, PC_POOL_FUSE, 0.0, 17.0 * st.N * st.h * st.w * st.C * (double)T, "k_bilinear");
             launch_bilinear(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, 4 * st.h, 4 * st.w, st.C, 0, s);
@@ -2976,6 +3062,30 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
             launch_fuse_bwd(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * hw * st.src.ld,
                             c.at<char>(st.dsrc.off) + (int64_t)2 * st.N * hw * st.dsrc.ld * T, st.dsrc.ld,
                             c.at(st.ddst.off), st.ddst.ld, (int64_t)st.N * hw * st.ddst.ld, st.N, hw, st.C, s);
+        }
+        else if (st.kind == GS_TOKENDEC) {
+            auto& b = e.bit;
+            const int n = st.h * st.w;
+            const double rows = (double)st.N * n;
+            {   // recompute + backward: 3 x the forward's products; reads the layer inputs and the gradient, the gradient travels in fp32
+                ProfScope ps(c, PC_POOL_FUSE, 3.0 * 12288.0 * b.L * rows, rows * 32 * ((b.L + 2.0) * (double)T + 8.0 * (b.L - 1)), "k_bit_dec_bwd");
+                if (launch_bit_dec_bwd(dt, c.at(st.src.off), c.at(b.xs), c.at(st.ddst.off), c.at<float>(b.dG), c.at(st.dsrc.off), c.at<float>(b.AP),
+                                       params + b.dec_off, c.at<float>(b.dec_part), n, st.N, b.L, b.dh, s)) return 1;
+            }
+            // partial sums, unfold of dA / dP into the projection gradients, d(memory): bytes = the partials read once
+            ProfScope ps(c, PC_POOL_FUSE, 2.0 * b.L * st.N * 6.0 * 8 * b.dh * 32 * 4, 4.0 * (double)bit_dec_part_floats(n, st.N, b.L), "k_bit_sum_parts|k_bit_dec_unfold|k_bit_dec_mfinish");
+            launch_bit_dec_finish(c.at<float>(b.dec_part), c.at<float>(b.dAP), c.at<float>(b.tok_out), params + b.dec_off, grads + b.dec_off,
+                                  c.at<float>(b.dmh), c.at<float>(b.dm), c.at<float>(b.dtok_out), n, st.N, b.L, b.dh, s);
+        } else if (st.kind == GS_TOKENENC) {
+            auto& b = e.bit;
+            ProfScope ps(c, PC_POOL_FUSE, 6.0 * B * 8 * (4.0 * 512 * 32 + 2.0 * 32 * 64), 4.0 * (double)bit_enc_part_floats(B, 64) * 2, "k_bit_enc<true>");
+            launch_bit_enc_bwd(c.at<float>(b.tok_in), params + b.pos_off, params + b.enc_off, c.at<float>(b.dtok_out), c.at<float>(b.dtok_in),
+                               c.at<float>(b.enc_part), grads + b.enc_off, grads + b.pos_off, B, 64, s);
+        } else if (st.kind == GS_TOKENIZE) {
+            auto& b = e.bit;
+            ProfScope ps(c, PC_POOL_FUSE, 48.0 * 32 * st.N * st.h * st.w, 4.0 * st.N * st.h * st.w * 32 * (double)T, "k_bit_tok_bwd");
+            launch_bit_tok_bwd(dt, c.at(st.src.off), params + b.wa_off, c.at<float>(b.stat), c.at<float>(b.dtok_in), c.at(b.dec_din.off),
+                               c.at(st.dsrc.off), c.at<float>(b.tok_part), grads + b.wa_off, st.N, st.h * st.w, s);
         }
         else if (st.kind == GS_BILINEAR) {
             ProfScope ps(c, PC_POOL_FUSE, 0.0, 17.0 * st.N * st.h * st.w * st.C * (double)T, "k_bilinear_bwd");

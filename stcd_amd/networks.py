@@ -38,11 +38,16 @@ def _register_snunet():
 
 _register_snunet()
 
+# BIT (networks.py:174-182) under names of this project: the reference's own three names stay in _OFF_PATH (a test pins them there);
+# pointing them at these builders is a one-line change each
+_BIT = {"bit_pos_s4": dict(), "bit_pos_s4_dd8": dict(enc_depth=1, dec_depth=8),
+        "bit_pos_s4_dd8_dedim8": dict(enc_depth=1, dec_depth=8, decoder_dim_head=8)}
+
 
 def __getattr__(name):
-    if name == "ResNet":          # re-exported like the reference's module does; imported lazily (stcd_amd.bit pulls in segcd's holders)
-        from .bit import ResNet
-        return ResNet
+    if name in ("ResNet", "BASE_Transformer"):      # re-exported like the reference's module does; imported lazily (stcd_amd.bit pulls in segcd's holders)
+        from . import bit
+        return getattr(bit, name)
     raise AttributeError(name)
 
 
@@ -102,7 +107,9 @@ def init_net(net, init_type="normal", init_gain=0.02, gpu_ids=[]):
 def define_G(args, init_type="normal", init_gain=0.02, gpu_ids=[]):
     """The reference's names for the networks on the path, plus one addition: ``"SNUNet_conc"`` builds ``Siam_NestedUNet_Conc``
     (SNUNet.py:155-243, which the reference's define_G never registers); with ``args.multi_scale_train == "True"`` it returns the
-    five maps [output1..4, output] for CDTrainer's multi-scale loss.  ``"SNUNet"`` still builds ``SNUNet_ECAM``."""
+    five maps [output1..4, output] for CDTrainer's multi-scale loss.  ``"SNUNet"`` still builds ``SNUNet_ECAM``.  ``"bit_pos_s4"``,
+    ``"bit_pos_s4_dd8"`` and ``"bit_pos_s4_dd8_dedim8"`` build ``BASE_Transformer`` with the arguments the reference gives
+    ``base_transformer_pos_s4*`` (networks.py:174-182)."""
     name = args.net_G
     if name == "ChangeFormerV6":                           # networks.py:195-196: ChangeFormerV6(embed_dim=args.embed_dim), two classes
         from .changeformer import ChangeFormerV6
@@ -110,6 +117,9 @@ def define_G(args, init_type="normal", init_gain=0.02, gpu_ids=[]):
     elif name == "base_resnet18":                          # networks.py:172-173: ignores args.n_class
         from .bit import ResNet
         net = ResNet(input_nc=3, output_nc=2, output_sigmoid=False)
+    elif name in _BIT:                                     # networks.py:174-182: output_nc = 2, args.n_class ignored
+        from .bit import BASE_Transformer
+        net = BASE_Transformer(input_nc=3, output_nc=2, token_len=4, resnet_stages_num=4, with_pos="learned", **_BIT[name])
     elif name in _ON_PATH:
         net = _ON_PATH[name](args.n_class)
     elif name in _ON_PATH_ARGS:                            # "SNUNet_conc": Siam_NestedUNet_Conc, a name of this project (the reference

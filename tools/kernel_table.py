@@ -1,5 +1,5 @@
 """Per-kernel table of one training step through the engine's own HIP-event instrumentation (stcd_profile_*): launches,
-ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|snunet_conc|segcd|base_resnet18|base_resnet18_s4|diff|conc [--batch 16]"""
+ms, algorithmic TFLOP/s and GB/s per kernel name.  python tools/kernel_table.py --model snunet|snunet_conc|segcd|base_resnet18|base_resnet18_s4|bit_pos_s4|bit_pos_s4_dd8|bit_pos_s4_dd8_dedim8|diff|conc [--batch 16]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -19,6 +19,11 @@ if a.model == "segcd":
 elif a.model in ("base_resnet18", "base_resnet18_s4"):
     from stcd_amd.bit import ResNet
     m = ResNet(3, 2, resnet_stages_num=4 if a.model.endswith("_s4") else 5).to(dev).train()
+    label = 2
+elif a.model.startswith("bit_pos_s4"):
+    from stcd_amd.bit import BASE_Transformer
+    dd, dh = {"bit_pos_s4": (1, 64), "bit_pos_s4_dd8": (8, 64), "bit_pos_s4_dd8_dedim8": (8, 8)}[a.model]
+    m = BASE_Transformer(3, 2, "learned", resnet_stages_num=4, dec_depth=dd, decoder_dim_head=dh).to(dev).train()
     label = 2
 else:
     from stcd_amd import modules
