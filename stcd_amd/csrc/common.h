@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <string.h>
 
@@ -16,6 +17,12 @@ enum DType { F32 = STCD_DTYPE_F32, BF16 = STCD_DTYPE_BF16 };
 inline size_t dsize(int dt) { return dt == BF16 ? 2 : 4; }
 
 void set_error(const std::string& msg);
+
+// Run-time switches (README.md, "Environment switches"): every STCD_* variable the library reads goes through these two.
+// env_int: atoi of the value, dflt when unset.  env_flag: a switch that is off by default turns on with a value starting with '1',
+// one that is on by default turns off with a value starting with '0'; anything else leaves the default.
+static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+static inline bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v && v[0] == (dflt ? '0' : '1') ? !dflt : dflt; }
 
 #define STCD_CHECK(cond, msg)                                              \
     do {                                                                   \
@@ -194,7 +201,7 @@ struct XfSrc {
     int C = 0, groups = 1, npg = 0, publish = 0;
     long long ppg = 0;                 // values per channel and group
     float momentum = 0.1f, eps = 1e-5f;
-    int on = 0;                        // 0: plain input tensor
+    int on = 0;                        // 0: plain input tensor; 1: staged through xf_act8
 };
 // one 16-B piece (8 consecutive channels of one pixel).  sc / sh: the channel's BatchNorm scale / shift ALREADY multiplied by the
 // image's Dropout2d factor (mk >= 0, so max(y * sc + sh, 0) * mk == max(y * (sc * mk) + sh * mk, 0): k_bn_act folds the same way);
@@ -434,7 +441,6 @@ void launch_pack_jobs(const PackJob* jobs_dev, int njobs, int64_t total, const f
 int bn_stats_chunks(int64_t pixels_per_group, int C);
 void launch_bn_stats(int dt, const void* Y, int ld, int C, int groups, int64_t pixels_per_group, long long* acc, hipStream_t s);
 // eval mode: stat fp32 [groups][4][C] = mean, invstd, scale, shift from the running statistics
-void launch_bn_finalize(const XfSrc& x, hipStream_t s);
 void launch_bn_eval_prepare(int C, int groups, const float* gamma, const float* beta, const float* running_mean,
                             const float* running_var, float* stat, float eps, hipStream_t s);
 // A = relu(Y*scale+shift) * mask ; optional fused 2x2 max-pool output P (floor).

@@ -73,15 +73,12 @@ struct WgradOp {
     int group = -1;                      // index of its WgradGroup inside e.wgroups[stage]
     // X is a virtual activation (the producer's raw conv output, transformed while staged: XfSrc / wgrad_job_set_xf); xf_C == 0: plain
     int64_t xf_stat_off = -1, xf_mask_off = -1; int xf_C = 0, xf_groups = 1, xf_npg = 1;
-    bool tail = false;                   // the network's first conv: its dY is the LAST tensor of the backward, so it gets a group of
-                                         // its own -- its stage-mates' grid goes out as soon as THEY are ready, not with it
     bool own_taps = false;               // filter taps (ky, kx) of this launch given here instead of conv.fwd.ky/kx[tap0 + t]
     int8_t oky[9] = {0}, okx[9] = {0};   // (the 7x7 stem: 49 taps spread over 7 launches)
 };
 struct WgradGroup {                      // all launches of one kernel variant in one backward stage
     int WCI = 1, NTW = 1; bool t9 = false;
     bool xf = false;                     // its jobs stage X through the virtual-activation transform (k_wgrad_group<.., XF = true>)
-    bool tail = false;                   // holds only the network's first conv (WgradOp::tail)
     int gemm = 0;                        // > 0: k_wgrad_gemm<gemm> group (one-tap launches; WCI / NTW / t9 unused)
     int dma = 0;                         // 1: k_wgrad_dma group (256 x 256 channel tiles, LDS-DMA staging; splits chosen for the group)
     std::vector<WgradJob> jobs;
@@ -274,8 +271,6 @@ struct stcd_engine_impl {
     int use_virt = 0;                   // STCD_VIRT_ACT=1: virtual activations (round 4: built, bit-identical, MEASURED 2-3 % SLOWER on the
                                         // headline step -- DESIGN.md section 4 -- so every activation is materialised by default)
     int fc_virt_layers = 0;             // layers of the current FC-Siam plan whose activation is virtual
-    int xf_mode = 0;                    // STCD_XF_MODE bit 0: the virtual layers' tables come from a k_bn_finalize launch instead of every
-                                        // consumer block's prologue; bit 1: timing experiment (no transform, wrong results)
     std::vector<ConvOp*> conv_ops;      // every ConvOp of the plan (weight-image packing walks this)
     int64_t slab = -1, slab_floats = 0;
     std::vector<WgradOp*> wgrad_ops;                    // every WgradOp of the plan
@@ -295,11 +290,13 @@ struct stcd_engine_impl {
     int64_t final_bias_acc = -1;
     std::vector<BiasJob> bias_jobs; int64_t bias_jobs_off = -1;
     int64_t masks = -1, dwe_begin = -1, dwe_end = -1, scratch8 = -1;
-    int use_mfma = 1, use_small = 1, use_wgroup = 1, wgroup_min_tiles = 8, wgroup_rounds = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, wg_tail_split = 0, use_bwdsum = 1, use_bwdsum_res = 0;
+    int use_mfma = 1, use_small = 1, use_wgroup = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, use_bwdsum = 1, use_bwdsum_res = 0;
     // FC-Siam backward: the decoder's grouped weight gradients (+ slab reduce, bias finish) run on a low-priority side stream beside
-    // the encoder's backward chain on the caller's stream; their grids get 1 / wg_side_div of the planner's block budget so that the
+    // the encoder's backward chain on the caller's stream; their grids get 1 / WG_SIDE_DIV of the planner's block budget so that the
     // chain's blocks find free slots (wgrad_side_stream)
-    int wg_side_on = 1, wg_side_div = 4;
+    int wg_side_on = 1;
+    static constexpr int WG_SIDE_DIV = 4;                // share of the planner's block budget for stage 0's grouped grids: 1 / div
+    static constexpr int WGROUP_ROUNDS = 1, WGROUP_MIN_TILES = 8;      // build_pack_jobs: resident rounds of a group's blocks, fewest tiles per block
     bool wg_early = false; hipStream_t wg_cur_side = nullptr;      // set by backward_fcsiam for the duration of a call (exec_wgrad)
     hipStream_t wg_side = nullptr; hipEvent_t wg_fork = nullptr, wg_join = nullptr; int wg_side_dev = -1;
 };
@@ -314,6 +311,7 @@ namespace stcd {
 // ------------------------------------------------------------------------------------------ model tables
 static const int ENC_STAGE_CONVS[4] = {2, 2, 3, 3};
 static const int ENC_C[4] = {16, 32, 64, 128};
+static const int SKIP_IDX[4] = {1, 3, 6, 9};           // the encoder layer whose activation is level s's skip connection
 
 static void add_param(stcd_engine& e, const std::string& name, std::initializer_list<int64_t> shape, int64_t* off_out) {
     stcd_tensor_info ti;
@@ -557,21 +555,19 @@ static stcd_conv_geom geom_up_phase(const UpConv& U, int py, int px, int ldi, in
 
 static void conv_work(const stcd_engine& e, const stcd_conv_geom& g, int kreal, int nreal, double* flops, double* bytes);
 
-// the tap-list GEMM kernel takes what the resident-filter kernel cannot, and (STCD_GEMM_OVER_RES: 0 never, 1 [default] when the
-// resident kernel would run 16-channel output slices, i.e. re-read X once per 16 output channels, 2 always)
+// the tap-list GEMM kernel takes what the resident-filter kernel cannot, and -- for ChangeFormer -- what the resident kernel would
+// run in 16-channel output slices, i.e. re-read X once per 16 output channels
 static void pick_gemm_or_res(const stcd_engine& e, ConvOp& op, const stcd_conv_geom& g, int groups) {
     op.gemm = ConvGemmPlan();
     if (!e.use_gemm || op.small) return;
-    static const int env_mode = [] { const char* v = getenv("STCD_GEMM_OVER_RES"); return v ? atoi(v) : -1; }();
     // (ChangeFormer's 256-channel decoder convolutions get 16-channel output slices from the resident-filter kernel, i.e. X is
     //  re-read 16 times through L2: the GEMM kernel's 128 x 128 tile measured 8.3 vs 9.5 ms per step there; a tie elsewhere)
-    const int mode = env_mode >= 0 ? env_mode : (e.cf ? 1 : 0);
-    if (op.res.ok && !(mode == 2 || (mode == 1 && op.res.NT == 1))) return;
+    if (op.res.ok && !(e.cf && op.res.NT == 1)) return;
     op.gemm = conv_gemm_plan(g, op.plan, groups);
     if (op.gemm.ok) op.res = ConvResPlan();
     // opt-in (measured 0.93 - 1.03 of k_conv_gemm on ChangeFormer's 256 -> 256 layers): layers that take the GEMM kernel,
     // carry no fused BatchNorm statistics (groups == 1 callers that pass none) and fill the chip with 16 x 16 tiles
-    static const bool halo_on = [] { const char* v = getenv("STCD_HALO_KERNEL"); return v && v[0] == '1'; }();
+    static const bool halo_on = env_flag("STCD_HALO_KERNEL", false);
     op.halo = ConvHaloPlan();
     // the LDS-DMA kernel takes the layers it fits once they fill the chip with 256-position tiles (ChangeFormer's decoder head)
     op.dma = ConvDmaPlan();
@@ -597,6 +593,15 @@ static WgradMfmaPlan pick_wgrad_plan(const stcd_engine& e, const stcd_conv_geom&
     return wgrad_mfma_plan(g, kpad, wld, is_snunet(e.arch) || (e.cf && g.ntaps == 9));
 }
 
+// the grouped launch a weight gradient belongs to: same kernel variant (one LDS-DMA group per stage, whatever the tap count)
+static bool same_group(const WgradGroup& G, const WgradOp& op) {
+    const bool t9 = !op.plan.dma && op.g.ntaps == 9;
+    return G.gemm == op.plan.gemm && G.dma == op.plan.dma && G.WCI == op.plan.WCI && G.NTW == op.plan.NTW && G.t9 == t9 && G.xf == (op.xf_C > 0);
+}
+
+// STCD_CF_SIDE=0: ChangeFormer's single-call backward keeps its grouped weight gradients on the caller's stream
+static bool cf_side_on() { static const bool on = env_flag("STCD_CF_SIDE", true); return on; }
+
 static void build_pack_jobs(stcd_engine& e, Bump& ws) {
     // ---- per-launch slab regions + the batched reduce job tables (MFMA path only)
     for (int st = 0; st < 2; ++st) { e.rjobs[st].clear(); e.rjobs_total[st] = 0; }
@@ -611,9 +616,8 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
                 const bool t9 = !op->plan.dma && op->g.ntaps == 9;      // (one LDS-DMA group per stage, whatever the tap count)
                 std::vector<WgradGroup>& gs = e.wgroups[op->stage];
                 size_t gi = 0;
-                for (; gi < gs.size(); ++gi)
-                    if (gs[gi].gemm == op->plan.gemm && gs[gi].dma == op->plan.dma && gs[gi].WCI == op->plan.WCI && gs[gi].NTW == op->plan.NTW && gs[gi].t9 == t9 && gs[gi].xf == (op->xf_C > 0) && gs[gi].tail == op->tail) break;
-                if (gi == gs.size()) { WgradGroup g; g.WCI = op->plan.WCI; g.NTW = op->plan.NTW; g.t9 = t9; g.gemm = op->plan.gemm; g.dma = op->plan.dma; g.xf = op->xf_C > 0; g.tail = op->tail; gs.push_back(g); }
+                while (gi < gs.size() && !same_group(gs[gi], *op)) ++gi;
+                if (gi == gs.size()) { WgradGroup g; g.WCI = op->plan.WCI; g.NTW = op->plan.NTW; g.t9 = t9; g.gemm = op->plan.gemm; g.dma = op->plan.dma; g.xf = op->xf_C > 0; gs.push_back(g); }
                 op->grouped = true;
             }
             for (int st = 0; st < 2; ++st)
@@ -635,12 +639,10 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
                             return b;
                         };
                         int64_t lo = 1, hi = 1;
-                        // (STCD_WGRAD_DMA_BLOCKS: fewer than one block per CU leaves whole CUs to the kernels of the backward chain the
-                        //  group runs beside -- its blocks fill the register file of the CUs they sit on)
-                        static const int dma_env = [] { const char* v = getenv("STCD_WGRAD_DMA_BLOCKS"); return v && atoi(v) > 0 ? atoi(v) : 0; }();
-                        static const bool cf_side_env = [] { const char* v = getenv("STCD_CF_SIDE"); return !(v && v[0] == '0'); }();
+                        // (fewer than one block per CU leaves whole CUs to the kernels of the backward chain the group runs beside -- its
+                        //  blocks fill the register file of the CUs they sit on)
                         // 192 when the group runs on the side stream (single-call backwards): measured 26.9 -> 26.3 ms; 256 gains nothing there
-                        const int dma_blocks = dma_env ? dma_env : (e.wg_side_on && cf_side_env ? 192 : 256);
+                        const int dma_blocks = e.wg_side_on && cf_side_on() ? 192 : 256;
                         while (blocks_at(hi) > dma_blocks) hi *= 2;
                         while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (blocks_at(mid) <= dma_blocks) hi = mid; else lo = mid + 1; }
                         for (WgradOp* op : dops) {
@@ -656,7 +658,7 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
                     std::vector<WgradOp*> ops;
                     int64_t W = 0;
                     for (WgradOp* op : e.wgrad_ops)
-                        if (op->grouped && op->stage == st && !op->plan.gemm && !op->plan.dma && op->plan.WCI == G.WCI && op->plan.NTW == G.NTW && (op->g.ntaps == 9) == G.t9 && (op->xf_C > 0) == G.xf && op->tail == G.tail) {
+                        if (op->grouped && op->stage == st && same_group(G, *op)) {
                             ops.push_back(op);
                             const int64_t ntiles = (int64_t)op->g.n * ((op->g.wm + 15) / 16) * ((op->g.hm + 7) / 8);
                             W += ntiles * op->plan.gy * op->plan.gz;
@@ -670,9 +672,9 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
                     int slots = wgrad_variant_slots(G.WCI, G.NTW, G.t9, G.lds_bytes);
                     // stage 0 of the FC-Siam family runs beside stage 1's chain on a side stream: its grids leave room for the chain's blocks
                     // (stage 1's groups keep the full budget: half cost 2 %, a quarter 7 %)
-                    if (st == 0 && e.wg_side_on && e.wg_side_div > 1 && fc_family(e)) slots = std::max(64, slots / e.wg_side_div);
-                    const int64_t rounds = e.wgroup_rounds;
-                    const int64_t tpb = std::max<int64_t>(e.wgroup_min_tiles, (W + rounds * slots - 1) / (rounds * slots));
+                    if (st == 0 && e.wg_side_on && fc_family(e)) slots = std::max(64, slots / stcd_engine_impl::WG_SIDE_DIV);
+                    const int64_t rounds = stcd_engine_impl::WGROUP_ROUNDS;
+                    const int64_t tpb = std::max<int64_t>(stcd_engine_impl::WGROUP_MIN_TILES, (W + rounds * slots - 1) / (rounds * slots));
                     for (WgradOp* op : ops) {
                         const ConvW& cv = e.convs[op->conv];
                         const int64_t ntiles = (int64_t)op->g.n * ((op->g.wm + 15) / 16) * ((op->g.hm + 7) / 8);
@@ -690,9 +692,8 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
             const ConvW& cv = e.convs[op->conv];
             op->slab = ws.take(op->plan.slab_floats * 4);
             if (op->grouped) {
-                const bool t9 = !op->plan.dma && op->g.ntaps == 9;      // (one LDS-DMA group per stage, whatever the tap count)
                 for (WgradGroup& G : e.wgroups[op->stage])
-                    if (G.gemm == op->plan.gemm && G.dma == op->plan.dma && G.WCI == op->plan.WCI && G.NTW == op->plan.NTW && G.t9 == t9 && G.xf == (op->xf_C > 0) && G.tail == op->tail) {
+                    if (same_group(G, *op)) {
                         op->group = (int)(&G - e.wgroups[op->stage].data());
                         WgradJob j = op->plan.dma ? wgrad_dma_make_job(op->g, op->plan, op->in_off, op->dout_off, op->slab, cv.fwd.kpad, cv.fwd.wld)
                                    : op->plan.gemm ? wgrad_gemm_make_job(op->g, op->plan, op->in_off, op->dout_off, op->slab, cv.fwd.kpad, cv.fwd.wld)
@@ -984,8 +985,6 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
     for (auto& L : e.enc) bind_cbrd(L);
     for (auto& L : e.dec) bind_cbrd(L);
     for (auto& X : e.xc) bind_cbrd(X.res);
-    for (auto& L : e.enc) L.wg.tail = false;
-    if (e.wg_tail_split && !e.enc.empty()) e.enc[0].wg.tail = true;
     for (auto& U : e.ups) {
         const ConvW& cv = e.convs[U.conv];
         for (int ph = 0; ph < 4; ++ph) {
@@ -1423,14 +1422,8 @@ static XfSrc xf_source(const Ctx& c, const Cbrd& P, float* bn_running, bool trai
     x.mask = (training && e.drop_p > 0.f && P.drop >= 0) ? c.at<float>(e.masks) + e.drops[P.drop].off : nullptr;
     x.publish = training ? 1 : 0;
     x.on = 1;
-    if (training && (e.xf_mode & 1)) {       // the table was published by k_bn_finalize right behind the producer (cbrd_forward)
-        x.facc = nullptr; x.gamma = nullptr; x.beta = nullptr; x.rmean = nullptr; x.rvar = nullptr; x.publish = 0;
-    }
-    if (e.xf_mode & 2) x.on = 2;             // TIMING EXPERIMENT ONLY (wrong results): stage the raw tensor, no transform
     return x;
 }
-
-static const float* a_gamma(const Ctx& c, const Cbrd& L) { return c.params + c.e.bns[L.bn].g_off; }
 
 static void cbrd_forward(const Ctx& c, const Cbrd& L, float* bn_running, bool training) {
     stcd_engine& e = c.e;
@@ -1451,16 +1444,7 @@ static void cbrd_forward(const Ctx& c, const Cbrd& L, float* bn_running, bool tr
             launch_bn_stats(e.dt, c.at(L.Y.off), L.Y.ld, C, L.groups, ppg, c.at<long long>(L.facc), c.s);
         }
     }
-    if (L.virt) {            // the consumer applies scale / shift / ReLU / Dropout2d while staging Y (and publishes the statistics)
-        if (training && (e.xf_mode & 1)) {
-            XfSrc x = xf_source(c, L, bn_running, training);
-            x.facc = c.at<long long>(L.facc); x.gamma = a_gamma(c, L); x.beta = x.gamma ? c.params + e.bns[L.bn].b_off : nullptr;
-            x.rmean = bn_running + e.bns[L.bn].run_off; x.rvar = x.rmean + C;
-            ProfScope ps(c, PC_BN_STATS, 0.0, 0.0, "k_bn_finalize");
-            launch_bn_finalize(x, c.s);
-        }
-        return;
-    }
+    if (L.virt) return;      // the consumer applies scale / shift / ReLU / Dropout2d while staging Y (and publishes the statistics)
     BnActArgs a;
     a.Y = c.at(L.Y.off); a.ldy = L.Y.ld;
     a.A = skip_recomputed(e, L) ? nullptr : c.at(L.A.off); a.lda = L.A.ld; a.a_group_off = L.A.goff;
@@ -1601,7 +1585,6 @@ static int forward_fcsiam(stcd_engine& e, const float* x1, const float* x2, cons
     Ctx c{e, (char*)workspace, params, nullptr, s};
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt);
-    static const int SKIP_IDX[4] = {1, 3, 6, 9};
     if (training && e.drop_p > 0.f) {
         if (masks) STCD_HIP(hipMemcpyAsync(c.at(e.masks), masks, e.drop_floats * 4, hipMemcpyDeviceToDevice, s));
         else launch_dropout_gen(c.at<float>(e.masks), e.drop_floats, seed, e.drop_p, s);
@@ -1668,6 +1651,28 @@ static hipStream_t wgrad_side_stream(stcd_engine& e, hipStream_t s) {
     return st;
 }
 
+static void finish_biases(const Ctx& c) {
+    launch_bias_finish(c.at<BiasJob>(c.e.bias_jobs_off), (int)c.e.bias_jobs.size(), c.ws, c.grads, c.s);
+}
+
+// The tail of a backward stage: the stage's groups that have not gone out and its slab reduction (reduce_stage), then `extra` (column
+// sums, bias finish).  With a side stream all of it runs there, behind an event of the caller's stream, and wg_join is recorded; the
+// caller's stream waits on it only where wait_join says so (the last stage of a call: an earlier stage's tail runs beside the next
+// stage's chain, and the side stream's order carries it to the last join).
+template <typename Extra>
+static int stage_tail(const Ctx& c, int stage, hipStream_t side, bool wait_join, Extra extra) {
+    stcd_engine& e = c.e;
+    if (!side) { reduce_stage(c, stage); extra(c); return 0; }
+    STCD_HIP(hipEventRecord(e.wg_fork, c.s));
+    STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
+    Ctx cs{e, c.ws, c.params, c.grads, side};
+    reduce_stage(cs, stage);
+    extra(cs);
+    STCD_HIP(hipEventRecord(e.wg_join, side));
+    if (wait_join) STCD_HIP(hipStreamWaitEvent(c.s, e.wg_join, 0));
+    return 0;
+}
+
 struct EarlyScope {      // exec_wgrad sends a group out with its last member for the duration of a backward call
     stcd_engine& e;
     EarlyScope(stcd_engine& e_, bool on, hipStream_t sd) : e(e_) { e.wg_early = on; e.wg_cur_side = sd; }
@@ -1680,14 +1685,12 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
     // both stages in one call (no gradient all-reduce between them): stage 0's weight gradients only read stored tensors and write
     // their own slabs / gradient entries, so they can run beside stage 1's chain
     hipStream_t side = stage < 0 ? wgrad_side_stream(e, s) : nullptr;
-    static const bool early_on = [] { const char* v = getenv("STCD_WGRAD_EARLY"); return !(v && v[0] == '0'); }();
-    EarlyScope early_scope(e, early_on && mfma_on(e) && e.use_wgroup, side);
+    EarlyScope early_scope(e, mfma_on(e) && e.use_wgroup, side);
     for (int st = 0; st < 2; ++st)
         if (stage < 0 || stage == st)
             for (WgradGroup& G : e.wgroups[st]) { G.seen = 0; G.launched = false; }      // (a failed call may have left them set)
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt);
-    static const int SKIP_IDX[4] = {1, 3, 6, 9};
     if (stage <= 0) {
         STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
         if (!mfma_on(e)) STCD_HIP(hipMemsetAsync(c.at(e.dwe_begin), 0, e.dwe_end - e.dwe_begin, s));
@@ -1718,17 +1721,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
                                 (int64_t)e.Hs[s_] * e.Ws[s_], C, s);
             }
         }
-        if (side) {
-            STCD_HIP(hipEventRecord(e.wg_fork, s));
-            STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
-            Ctx cs{e, (char*)workspace, params, grads, side};
-            reduce_stage(cs, 0);
-            launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, side);
-            STCD_HIP(hipEventRecord(e.wg_join, side));
-        } else {
-            reduce_stage(c, 0);
-            launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, s);
-        }
+        if (stage_tail(c, 0, side, false, finish_biases)) return 1;      // (stage 1's join below is the one the caller's stream waits on)
     }
     if (stage < 0 || stage == 1) {
         for (int li = (int)e.enc.size() - 1; li >= 0; --li) {
@@ -1761,16 +1754,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
             }
             cbrd_backward(c, L, skip_chunks);
         }
-        if (side) {
-            STCD_HIP(hipEventRecord(e.wg_fork, s));
-            STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
-            Ctx cs{e, (char*)workspace, params, grads, side};
-            reduce_stage(cs, 1);
-            STCD_HIP(hipEventRecord(e.wg_join, side));
-            STCD_HIP(hipStreamWaitEvent(s, e.wg_join, 0));
-        } else {
-            reduce_stage(c, 1);
-        }
+        if (stage_tail(c, 1, side, true, [](const Ctx&) {})) return 1;
     }
     STCD_HIP(hipGetLastError());
     return 0;
@@ -2263,8 +2247,7 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
     // groups whose members all sit deep in the backward order -- the GEMM groups, the 32 x 32 tile group -- run beside the rest of
     // the chain: 13.22 -> 12.80 ms; cutting the groups into buckets of the backward order, or smaller grids, added nothing)
     hipStream_t side = stage < 0 ? wgrad_side_stream(e, s) : nullptr;
-    static const bool early_on = [] { const char* v = getenv("STCD_WGRAD_EARLY"); return !(v && v[0] == '0'); }();
-    EarlyScope early_scope(e, early_on && mfma_on(e) && e.use_wgroup, side);
+    EarlyScope early_scope(e, mfma_on(e) && e.use_wgroup, side);
     for (WgradGroup& G : e.wgroups[0]) { G.seen = 0; G.launched = false; }
     const int dt = e.dt, B = e.B;
     const int64_t T = (int64_t)dsize(dt);
@@ -2302,18 +2285,7 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
         sn_block_backward(c, b);       // (its concat gradient b.dIn is gathered by the producers' reductions later on)
         if (b.up >= 0) sn_up_backward(c, e.sn_ups[b.up]);
     }
-    if (side) {
-        STCD_HIP(hipEventRecord(e.wg_fork, s));
-        STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
-        Ctx cs{e, (char*)workspace, params, grads, side};
-        reduce_stage(cs, 0);
-        launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, side);
-        STCD_HIP(hipEventRecord(e.wg_join, side));
-        STCD_HIP(hipStreamWaitEvent(s, e.wg_join, 0));
-    } else {
-        reduce_stage(c, 0);
-        launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, s);
-    }
+    if (stage_tail(c, 0, side, true, finish_biases)) return 1;
     STCD_HIP(hipGetLastError());
     return 0;
 }
@@ -3124,41 +3096,19 @@ extern "C" {
 const char* stcd_last_error(void) { return stcd::g_err.c_str(); }
 int stcd_abi_version(void) { return STCD_ABI_VERSION; }
 
-static void engine_env_switches(stcd_engine* e) {
-    const char* env = getenv("STCD_FORCE_REF_KERNELS");
-    e->use_mfma = !(env && env[0] == '1');
-    env = getenv("STCD_NO_SMALL_KERNEL");
-    e->use_small = !(env && env[0] == '1');
-    env = getenv("STCD_NO_GEMM_KERNEL");
-    e->use_gemm = !(env && env[0] == '1');
-    env = getenv("STCD_NO_RES_KERNEL");
-    e->use_res = !(env && env[0] == '1');
-    env = getenv("STCD_NO_WGRAD_GROUPS");
-    e->use_wgroup = !(env && env[0] == '1');
-    env = getenv("STCD_NO_ACT_FUSE");
-    e->use_act_fuse = !(env && env[0] == '1');
-    env = getenv("STCD_NO_SKIP_FUSED");
-    e->use_skip_fused = !(env && env[0] == '1');
-    env = getenv("STCD_NO_SKIP_RECOMPUTE");       // 1: the skip layers of diff / sub store their activations again
-    e->use_skip_recompute = !(env && env[0] == '1');
-    env = getenv("STCD_WGRAD_TAIL_SPLIT");        // 1: the first conv's weight gradient gets a grid of its own, so its stage-mates' grid
-    e->wg_tail_split = env && env[0] == '1';      //    goes out ~120 us earlier (measured neutral: the step is HBM-bound)
-    env = getenv("STCD_NO_BWDSUM_FUSE");          // 1: every layer runs its own k_bn_reduce (no sums in k_conv_small data gradients)
-    e->use_bwdsum = !(env && env[0] == '1');
-    env = getenv("STCD_BWDSUM_RES");              // 1: also the layers behind a k_conv_res data gradient (measured slower, see configure_fcsiam)
-    e->use_bwdsum_res = env && env[0] == '1';
-    env = getenv("STCD_VIRT_ACT");                // 1: virtual activations (opt-in); 0 / unset: k_bn_act per layer
-    if (env) e->use_virt = atoi(env) != 0;
-    env = getenv("STCD_XF_MODE");
-    if (env) e->xf_mode = atoi(env);
-    env = getenv("STCD_WGRAD_SIDE");              // 0: the decoder's weight gradients stay on the caller's stream
-    if (env) e->wg_side_on = atoi(env) != 0;
-    env = getenv("STCD_WGRAD_SIDE_DIV");          // share of the planner's block budget for stage 0's grouped grids: 1 / div
-    if (env && atoi(env) > 0) e->wg_side_div = atoi(env);
-    env = getenv("STCD_WGRAD_ROUNDS");
-    if (env && atoi(env) > 0) e->wgroup_rounds = atoi(env);
-    env = getenv("STCD_WGRAD_MIN_TILES");
-    if (env && atoi(env) > 0) e->wgroup_min_tiles = atoi(env);
+static void engine_env_switches(stcd_engine* e) {       // read at every stcd_create*
+    e->use_mfma = !env_flag("STCD_FORCE_REF_KERNELS", false);
+    e->use_small = !env_flag("STCD_NO_SMALL_KERNEL", false);
+    e->use_gemm = !env_flag("STCD_NO_GEMM_KERNEL", false);
+    e->use_res = !env_flag("STCD_NO_RES_KERNEL", false);
+    e->use_wgroup = !env_flag("STCD_NO_WGRAD_GROUPS", false);
+    e->use_act_fuse = !env_flag("STCD_NO_ACT_FUSE", false);
+    e->use_skip_fused = !env_flag("STCD_NO_SKIP_FUSED", false);
+    e->use_skip_recompute = !env_flag("STCD_NO_SKIP_RECOMPUTE", false);     // 1: the skip layers of diff / sub store their activations again
+    e->use_bwdsum = !env_flag("STCD_NO_BWDSUM_FUSE", false);                // 1: every layer runs its own k_bn_reduce (no sums in k_conv_small data gradients)
+    e->use_bwdsum_res = env_flag("STCD_BWDSUM_RES", false);                 // 1: also the layers behind a k_conv_res data gradient (measured slower, see configure_fcsiam)
+    e->use_virt = env_int("STCD_VIRT_ACT", e->use_virt) != 0;               // 1: virtual activations (opt-in); 0 / unset: k_bn_act per layer
+    e->wg_side_on = env_int("STCD_WGRAD_SIDE", e->wg_side_on) != 0;         // 0: the decoder's weight gradients stay on the caller's stream
 }
 
 int stcd_cf_default_config(stcd_cf_config* cfg) {
@@ -3676,14 +3626,14 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
             STCD_HIP(hipGetLastError());
             return 0;
         }
-        if (impl == 1 && !(getenv("STCD_NO_RES_KERNEL") && getenv("STCD_NO_RES_KERNEL")[0] == '1')) {
+        if (impl == 1 && !env_flag("STCD_NO_RES_KERNEL", false)) {
             const ConvResPlan rp = conv_res_plan(*g, p, 1);
             if (rp.ok && launch_conv_res(*g, p, rp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0) {
                 STCD_HIP(hipGetLastError());
                 return 0;
             }
         }
-        if (impl == 1 && !(getenv("STCD_NO_GEMM_KERNEL") && getenv("STCD_NO_GEMM_KERNEL")[0] == '1')) {
+        if (impl == 1 && !env_flag("STCD_NO_GEMM_KERNEL", false)) {
             const ConvGemmPlan gp = conv_gemm_plan(*g, p, 1);
             if (gp.ok && launch_conv_gemm(*g, p, gp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0) {
                 STCD_HIP(hipGetLastError());

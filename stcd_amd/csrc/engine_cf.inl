@@ -793,8 +793,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
     const int h1 = P.st[0].h, w1 = P.st[0].w;
     // both stages in one call: the grouped weight gradients go out with their last member on the engine's side stream (the head's
     // LDS-DMA group right after the second up-sampling layer's backward) and run beside the rest of the chain
-    static const bool cf_side = [] { const char* v = getenv("STCD_CF_SIDE"); return !(v && v[0] == '0'); }();
-    hipStream_t side = (stage < 0 && cf_side) ? wgrad_side_stream(e, s) : nullptr;
+    hipStream_t side = (stage < 0 && cf_side_on()) ? wgrad_side_stream(e, s) : nullptr;
     EarlyScope early_scope(e, side != nullptr, side);
     for (int st = 0; st < 2; ++st)
         if (stage < 0 || stage == st)
@@ -842,19 +841,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
             launch_slice(dt, c.at<char>(F.lo.g.off) + rows * D * T, D, c.at<char>(F.cat.g.off) + D * T, 2 * D, rows, D, 0, s);
             cf_gemm_bwd(c, F.lin);                 // -> d(stage output) (written; the next stage's patch embedding accumulates)
         }
-        if (side) {
-            STCD_HIP(hipEventRecord(e.wg_fork, s));
-            STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
-            Ctx cs{e, (char*)workspace, params, grads, side};
-            reduce_stage(cs, 0);
-            cf_colsum_stage(cs, 0);
-            launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, side);
-            STCD_HIP(hipEventRecord(e.wg_join, side));
-        } else {
-            reduce_stage(c, 0);
-            cf_colsum_stage(c, 0);
-            launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, s);
-        }
+        if (stage_tail(c, 0, side, false, [](const Ctx& x) { cf_colsum_stage(x, 0); finish_biases(x); })) return 1;
     }
     if (stage < 0 || stage == 1) {
         for (int si = 3; si >= 0; --si) {
@@ -869,18 +856,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
                 launch_col2im(dt, c.at(S.col.g.off), S.Kp, c.at(S.in_g.off), S.in_ld, N2, S.hin, S.win, S.cin, S.k, S.stride, S.k / 2, S.h, S.w, 1, s);
             }
         }
-        if (side) {
-            STCD_HIP(hipEventRecord(e.wg_fork, s));
-            STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
-            Ctx cs{e, (char*)workspace, params, grads, side};
-            reduce_stage(cs, 1);
-            cf_colsum_stage(cs, 1);
-            STCD_HIP(hipEventRecord(e.wg_join, side));
-            STCD_HIP(hipStreamWaitEvent(s, e.wg_join, 0));
-        } else {
-            reduce_stage(c, 1);
-            cf_colsum_stage(c, 1);
-        }
+        if (stage_tail(c, 1, side, true, [](const Ctx& x) { cf_colsum_stage(x, 1); })) return 1;
     }
     STCD_HIP(hipGetLastError());
     return 0;

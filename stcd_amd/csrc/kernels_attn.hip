@@ -322,7 +322,7 @@ static inline int attn_mfma_qsplit(int n, int heads, int N, int Nkv) {
     return (int)std::min<int64_t>(qs, 64);
 }
 bool attn_mfma_ok(int dt, int Nkv, int d) {
-    static const bool off = [] { const char* e = getenv("STCD_NO_MFMA_ATTENTION"); return e && e[0] == '1'; }();
+    static const bool off = env_flag("STCD_NO_MFMA_ATTENTION", false);
     return dt == BF16 && !off && attn_mfma_shape_ok(Nkv, d);
 }
 int64_t attn_mfma_bwd_scratch_floats(int n, int N, int Nkv, int heads, int d) {

@@ -303,7 +303,7 @@ k_conv_halo(const ConvHaloArgs a) {
 }
 
 static bool conv_halo_enabled() {
-    static const bool on = [] { const char* e = getenv("STCD_NO_HALO_KERNEL"); return !(e && e[0] == '1'); }();
+    static const bool on = !env_flag("STCD_NO_HALO_KERNEL", false);
     return on;
 }
 

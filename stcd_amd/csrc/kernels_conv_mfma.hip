@@ -245,19 +245,9 @@ __global__ void __launch_bounds__(256, 2)     // <= 256 registers: hipcc then se
 k_conv_mfma_x4(const ConvMfmaArgs4 j) {
     conv_mfma_body<NT>(j.a[blockIdx.z], blockIdx.x, blockIdx.y);
 }
-// ... or all four phases of a tile in ONE block, back to back (large maps: >= 1024 tiles).  The phases read the same input tile
-// (one HBM fetch, three L2 hits instead of four fetches by blocks scattered over the XCDs) and write the interleaved halves /
-// quarters of the same output lines within microseconds of each other on one XCD, so its L2 merges them into whole-line writes
-// (a phase alone writes 32-B pieces at a 64-B stride on the 16-channel level).
-template <int NT>
-__global__ void __launch_bounds__(256, 2)     // <= 256 registers: hipcc then selects the VGPR form of the MFMAs (see k_conv_small)
-k_conv_mfma_x4s(const ConvMfmaArgs4 j) {
-#pragma unroll 1
-    for (int z = 0; z < 4; ++z) {
-        conv_mfma_body<NT>(j.a[z], blockIdx.x, blockIdx.y);
-        __syncthreads();       // the next phase rewrites the tap table and the halo
-    }
-}
+// (all four phases of a tile in ONE block, back to back -- one input fetch, merged output lines -- MEASURED SLOWER and was removed:
+//  round 4, SiamUnet_diff 16 x 256^2: the four launches 0.088 -> 0.133 ms per step; SNUNet 12.94 -> 13.20 ms: a quarter of the
+//  blocks, each four times as long, fill the chip worse than the extra input fetches cost)
 
 // ------------------------------------------------------------------ host side
 static void taps_extent(const stcd_conv_geom& g, int* dymin, int* dymax, int* dxmin, int* dxmax) {
@@ -446,22 +436,15 @@ int launch_conv_mfma_x4(const stcd_conv_geom g[4], const ConvMfmaPlan p[4], cons
         lds = std::max(lds, conv_mfma_args(g[k], p[k], in, wf[k], bias, out, false, j.a[k]));
     }
     if (lds > 160 * 1024) return 1;
-    const int64_t tiles = (int64_t)j.a[0].tiles_x * j.a[0].tiles_y * g[0].n * (p[0].NTtot / p[0].NT);
-    // MEASURED SLOWER (round 4, SiamUnet_diff 16 x 256^2: the four launches 0.088 -> 0.133 ms per step; SNUNet 12.94 -> 13.20 ms): a
-    // quarter of the blocks, each four times as long, fill the chip worse than the extra input fetches cost -- opt-in (STCD_X4_SEQ=1)
-    static const int seq_env = [] { const char* e = getenv("STCD_X4_SEQ"); return e ? atoi(e) : 0; }();
-    const bool seq = seq_env != 0 && tiles >= 1;
-    dim3 grid((unsigned)(j.a[0].tiles_x * j.a[0].tiles_y * g[0].n), (unsigned)(p[0].NTtot / p[0].NT), seq ? 1 : 4);
+    dim3 grid((unsigned)(j.a[0].tiles_x * j.a[0].tiles_y * g[0].n), (unsigned)(p[0].NTtot / p[0].NT), 4);
 #define LAUNCH_X4(N_)                                                                                             \
     do {                                                                                                          \
         static bool attr_set = false;                                                                             \
         if (!attr_set) {                                                                                          \
             (void)hipFuncSetAttribute((const void*)k_conv_mfma_x4<N_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            (void)hipFuncSetAttribute((const void*)k_conv_mfma_x4s<N_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_set = true;                                                                                      \
         }                                                                                                         \
-        if (seq) k_conv_mfma_x4s<N_><<<grid, 256, lds, s>>>(j);                                                   \
-        else k_conv_mfma_x4<N_><<<grid, 256, lds, s>>>(j);                                                        \
+        k_conv_mfma_x4<N_><<<grid, 256, lds, s>>>(j);                                                             \
     } while (0)
     switch (p[0].NT) {
         case 1: LAUNCH_X4(1); break;
@@ -903,8 +886,7 @@ WgradMfmaPlan wgrad_mfma_plan(const stcd_conv_geom& g, int kpad, int wld, bool a
     // block tile: 16 / 32 / 64 input channels x 16 / 32 output channels.  <= 32 x 32: 72 accumulator registers, >= 3 waves per
     // SIMD, the k-steps of a tile split over the waves; 64 x 32 (wide layers): every wave owns one 16-channel ci tile for all
     // k-steps, dY is re-read once per 64 input channels instead of 32, twice the MFMAs per staged tile.
-    static const int wide_env = [] { const char* e = getenv("STCD_WGRAD_CI64"); return e ? atoi(e) : -1; }();     // -1: the caller decides
-    const bool wide_ok = wide_env < 0 ? allow_wide : wide_env != 0;
+    const bool wide_ok = allow_wide;      // the caller decides (see below)
     const int tiles_x = (g.wm + 15) / 16, tiles_y = (g.hm + 7) / 8;
     const int64_t ntiles = (int64_t)g.n * tiles_x * tiles_y;
     // STCD_WGRAD_CO64=1 (default off): 64 x 64-channel tile for layers with >= 64 channels on both sides -- 26 transposed LDS reads per
@@ -912,7 +894,7 @@ WgradMfmaPlan wgrad_mfma_plan(const stcd_conv_geom& g, int kpad, int wld, bool a
     // runs it through impl 4) and MEASURED SLOWER: its 144 accumulators leave one wave per SIMD and one block per CU (102 KB of LDS),
     // so nothing hides the staging round trips -- ChangeFormer's 3x3 group 6.05 ms vs 5.40 (32 x 32 tiles), SNUNet's 2.61 vs 1.86
     // (64 x 32).  Kept as an opt-in variant.
-    static const int co64_env = [] { const char* e = getenv("STCD_WGRAD_CO64"); return e ? atoi(e) : 0; }();
+    static const int co64_env = env_int("STCD_WGRAD_CO64", 0);
     const bool co64 = (force_co64 >= 0 ? force_co64 != 0 : co64_env != 0) && wide_ok && g.ci >= 64 && g.co >= 64 && HH * HWp * 8 <= 6 * 256;
     p.NTW = co64 ? 4 : g.co >= 32 ? 2 : 1;
     // (allow_wide is the ENGINE's per-family choice: all qualifying layers of a stage must move together -- two grouped launches
@@ -923,7 +905,7 @@ WgradMfmaPlan wgrad_mfma_plan(const stcd_conv_geom& g, int kpad, int wld, bool a
     p.gy = (g.ci + p.WCI * 16 - 1) / (p.WCI * 16);
     p.gz = (g.co + p.NTW * 16 - 1) / (p.NTW * 16);
     const int64_t slab_bytes = (int64_t)g.ntaps * kpad * wld * 4;
-    static const int target_blocks = [] { const char* e = getenv("STCD_WGRAD_BLOCKS"); return e ? atoi(e) : 1536; }();
+    constexpr int target_blocks = 1536;
     int64_t gx = std::max<int64_t>(1, target_blocks / (p.gy * p.gz));
     gx = std::min<int64_t>(gx, std::max<int64_t>(1, ((int64_t)24 << 20) / slab_bytes));
     gx = std::min<int64_t>(gx, ntiles);
@@ -1213,7 +1195,7 @@ k_conv_small(const ConvSmallArgs a) {
 #pragma unroll
             for (int p = 0; p < MAXP; ++p) {
                 const int i = tid + p * 256;
-                if (i < npieces) *reinterpret_cast<uint4*>(halo0 + buf_ * halo_elems + i * 8) = a.xf.on == 2 ? pre[p] : xf_act8(pre[p], xf_fs, xf_fh, 0u - ((xf_ok >> p) & 1u));
+                if (i < npieces) *reinterpret_cast<uint4*>(halo0 + buf_ * halo_elems + i * 8) = xf_act8(pre[p], xf_fs, xf_fh, 0u - ((xf_ok >> p) & 1u));
             }
         } else {
 #pragma unroll
@@ -1388,9 +1370,8 @@ bool conv_small_ok(const stcd_conv_geom& g, const ConvMfmaPlan& p) {
     const int HH = 7 * g.in_stride + (dymax - dymin) + 1, HWp = 15 * g.in_stride + (dxmax - dxmin) + 1;
     // measured: the register-resident filter only pays for one n-tile and <= 5 k-steps (Ci <= 16, Co <= 16);
     // wider cases run faster on the generic kernel (fewer registers, more waves)
-    // (STCD_SMALL_NT2=1: also two n-tiles, i.e. the 16 -> 32-channel layers -- re-measured in round 4)
-    static const int nt2 = [] { const char* e = getenv("STCD_SMALL_NT2"); return e ? atoi(e) : 0; }();
-    return ks <= 5 && nt <= (nt2 ? 2 : 1) && g.ci <= 32 && HH * HWp * (g.ci / 8) <= 3 * 256;
+    // (two n-tiles, i.e. the 16 -> 32-channel layers: re-measured in round 4 and lost again)
+    return ks <= 5 && nt <= 1 && g.ci <= 32 && HH * HWp * (g.ci / 8) <= 3 * 256;
 }
 
 // blocks the launcher will use (the BN-partial slab is sized from this)
@@ -1446,18 +1427,18 @@ int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_mo
         else k_conv_small<1, 5, false, 2, true><<<blocks, 256, lds, s>>>(a);
         return 0;
     }
-    // STCD_SMALL_FAST=0: the generic kernel for every layer; 1: exact k-step count only; 2 (default): + full-tile NHWC epilogue
-    static const int fast_on = [] { const char* e = getenv("STCD_SMALL_FAST"); return e ? atoi(e) : 2; }();
-    const bool full = fast_on >= 2 && !out_nchw && g.co == nt * 16 && g.hm % 8 == 0 && g.wm % 16 == 0;
+    if (nt != 1) return 1;      // (conv_small_ok)
+    // exact k-step count where there is a kernel for it, + full-tile NHWC epilogue where the layer allows it
+    const bool full = !out_nchw && g.co == nt * 16 && g.hm % 8 == 0 && g.wm % 16 == 0;
 #define LAUNCH_SMALL(N_, K_, F_) do { if (use_xf) k_conv_small<N_, K_, true, F_><<<blocks, 256, lds, s>>>(a); else k_conv_small<N_, K_, false, F_><<<blocks, 256, lds, s>>>(a); } while (0)
 #define LAUNCH_SMALL_K(N_, K_) do { if (full) LAUNCH_SMALL(N_, K_, 2); else LAUNCH_SMALL(N_, K_, 1); } while (0)
 #define LAUNCH_SMALL_N(N_) do { \
-        if (fast_on >= 1 && a.KS == 3) LAUNCH_SMALL_K(N_, 3); \
-        else if (fast_on >= 1 && a.KS == 5) LAUNCH_SMALL_K(N_, 5); \
+        if (a.KS == 3) LAUNCH_SMALL_K(N_, 3); \
+        else if (a.KS == 5) LAUNCH_SMALL_K(N_, 5); \
         else if (a.KS <= 5) LAUNCH_SMALL(N_, 5, 0); \
-        else if (fast_on >= 1 && a.KS == 9) LAUNCH_SMALL_K(N_, 9); \
+        else if (a.KS == 9) LAUNCH_SMALL_K(N_, 9); \
         else LAUNCH_SMALL(N_, 9, 0); } while (0)
-    if (nt == 1) LAUNCH_SMALL_N(1); else LAUNCH_SMALL_N(2);
+    LAUNCH_SMALL_N(1);
 #undef LAUNCH_SMALL_K
 #undef LAUNCH_SMALL_N
 #undef LAUNCH_SMALL
@@ -1645,7 +1626,7 @@ k_conv_res(const ConvResArgs a) {
             xf_fold8(tb_, tb_ + a.xf.C, (XS_).m0, (XS_).m1, sc_, sh_);                                                 \
             _Pragma("unroll") for (int p = 0; p < MAXP; ++p)                                                           \
                 if ((tid >> LG8) + p * PIXSTEP < RES_HW * RES_HW)                                                      \
-                    *reinterpret_cast<uint4*>(halo0 + (BUF_) * HALO_BYTES + plds[p]) = a.xf.on == 2 ? (PRE_)[p] : xf_act8((PRE_)[p], sc_, sh_, 0u - (((XS_).ok >> p) & 1u)); \
+                    *reinterpret_cast<uint4*>(halo0 + (BUF_) * HALO_BYTES + plds[p]) = xf_act8((PRE_)[p], sc_, sh_, 0u - (((XS_).ok >> p) & 1u)); \
         } else {                                                                                                       \
             _Pragma("unroll") for (int p = 0; p < MAXP; ++p)                                                           \
                 if ((tid >> LG8) + p * PIXSTEP < RES_HW * RES_HW)                                                      \
@@ -1866,10 +1847,7 @@ k_conv_res(const ConvResArgs a) {
     }
 }
 
-static int conv_res_filter_budget() {
-    static const int kb = [] { const char* e = getenv("STCD_CONV_RES_KB"); return e ? atoi(e) : 38; }();
-    return kb;
-}
+constexpr int RES_FILTER_KB = 38;      // largest filter slice (KB) a two-blocks-per-CU plan takes
 
 ConvResPlan conv_res_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int groups) {
     ConvResPlan rp;
@@ -1884,9 +1862,8 @@ ConvResPlan conv_res_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int gr
     }
     for (int t = 0; t < 9; ++t) if (!seen[t]) return rp;
     const int nchunks = g.ci / 32;
-    static const bool wide_ok = [] { const char* e = getenv("STCD_CONV_RES_NO_CW64"); return !(e && e[0] == '1'); }();
     int CW = 32, NT = 1;
-    if (wide_ok && g.ci % 64 == 0 && g.ci >= 256) {
+    if (g.ci % 64 == 0 && g.ci >= 256) {
         // 64-channel steps, one block per CU (measured: only pays for the deepest layers, whose 32-channel form has
         // twice the steps; below that two resident blocks per CU win): widest co slice that fits beside the halos
         const int halo2 = 2 * RES_HW * RES_HW * 64 * 2;
@@ -1903,26 +1880,16 @@ ConvResPlan conv_res_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int gr
         };
         const int ntmax = std::min(4, p.NT);
         NT = 0;
-        // STCD_CONV_RES_ONE=<tiles>: layers with at most that many 16 x 16 tiles take the widest slice that fits ONE block per CU
-        // (fewer, longer pipeline steps and fewer re-reads of the input per output slice) -- round-4 experiment, DESIGN.md section 4
-        static const int one_tiles = [] { const char* e = getenv("STCD_CONV_RES_ONE"); return e ? atoi(e) : 0; }();
-        {
-            const int64_t tiles_ = (int64_t)g.n * ((g.wm + 15) / 16) * ((g.hm + 15) / 16);
-            if (one_tiles > 0 && tiles_ <= one_tiles)
-                for (int nt = ntmax; nt >= 1 && !NT; nt >>= 1)
-                    if (fits(nt, 1)) NT = nt;
-        }
         for (int nt = ntmax; nt >= 1 && !NT; nt >>= 1)
-            if (fits(nt, 2) && nchunks * 9 * nt <= conv_res_filter_budget()) NT = nt;
+            if (fits(nt, 2) && nchunks * 9 * nt <= RES_FILTER_KB) NT = nt;
         for (int nt = ntmax; nt >= 1 && !NT; nt >>= 1)
             if (fits(nt, 1)) NT = nt;
         if (!NT) return rp;
         // Layers whose filter slice leaves ONE block per CU either way (SNUNet's 160 ... 224 concatenated input channels -> 32 on
         // 256^2 maps): with a single halo buffer (the refill waits for a second barrier) the slice can be twice as wide, so the
         // 0.3 - 0.5 GB input is read once instead of once per 16 output channels.
-        static const int sh_mode = [] { const char* e = getenv("STCD_CONV_RES_SH"); return e ? atoi(e) : 1; }();
         const int64_t tiles = (int64_t)g.n * ((g.wm + 15) / 16) * ((g.hm + 15) / 16);
-        if (sh_mode && tiles >= 2048 && !fits(NT, 2)) {
+        if (tiles >= 2048 && !fits(NT, 2)) {
             const int halo1 = RES_HW * RES_HW * 64;
             for (int nt = ntmax; nt > NT; nt >>= 1)
                 if (p.NTtot % nt == 0 && nchunks * 9 * nt * 1024 + halo1 <= cap) { NT = nt; rp.single_halo = 1; break; }
@@ -1984,12 +1951,9 @@ int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvRe
         k_conv_res<N_, W_, false, P_, X_><<<(unsigned)rp.blocks, 256, lds, s>>>(a);                               \
     } while (0)
 #define LAUNCH_RES(N_, W_) do { if (use_xf) LAUNCH_RES_V(N_, W_, false, true); else LAUNCH_RES_V(N_, W_, false, false); } while (0)
-#define LAUNCH_RES_PIPE(N_, W_) do { if (use_xf) LAUNCH_RES_V(N_, W_, true, true); else LAUNCH_RES_V(N_, W_, true, false); } while (0)
     // measured (SNUNet / SegCD, 16 x 256^2): <1, 64> 0.67 -> 0.58 ms per step (-13 %); the CW = 32 variants do not move (their
     // layers sit on the HBM roofline: 134 MB in + 134 MB out per 32 -> 32 full-resolution layer in 66 us), <2, 64> has no registers
-    // left for the second fragment set.  Default: <1, 64> only; STCD_CONV_RES_PIPE=1 pipelines every variant that fits, 0 none.
-    static const int pipe_env = [] { const char* e = getenv("STCD_CONV_RES_PIPE"); return e ? atoi(e) : -1; }();
-    const int pipe = pipe_env >= 0 ? pipe_env : (rp.CW == 64 && rp.NT == 1 && !use_xf);      // (<1, 64, PIPE, XF> spills: 112 B / lane)
+    // left for the second fragment set.  So <1, 64> alone is pipelined, and not with XF (<1, 64, PIPE, XF> spills: 112 B / lane).
 #define LAUNCH_RES_SH(N_)                                                                                         \
     do {                                                                                                          \
         static bool attr_set = false;                                                                             \
@@ -2016,14 +1980,14 @@ int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvRe
         if (rp.NT == 2) LAUNCH_RES_SH(2); else LAUNCH_RES_SH(4);
     } else if (rp.CW == 64) {
         switch (rp.NT) {
-            case 1: if (pipe) LAUNCH_RES_PIPE(1, 64); else LAUNCH_RES(1, 64); break;
-            case 2: if (pipe) LAUNCH_RES_PIPE(2, 64); else LAUNCH_RES(2, 64); break;
+            case 1: if (use_xf) LAUNCH_RES_V(1, 64, false, true); else LAUNCH_RES_V(1, 64, true, false); break;
+            case 2: LAUNCH_RES(2, 64); break;
             default: LAUNCH_RES(4, 64); break;
         }
     } else {
         switch (rp.NT) {
-            case 1: if (pipe) LAUNCH_RES_PIPE(1, 32); else LAUNCH_RES(1, 32); break;
-            case 2: if (pipe) LAUNCH_RES_PIPE(2, 32); else LAUNCH_RES(2, 32); break;
+            case 1: LAUNCH_RES(1, 32); break;
+            case 2: LAUNCH_RES(2, 32); break;
             default: LAUNCH_RES(4, 32); break;       // NT = 4 has no registers for a second fragment set (it spills)
         }
     }
@@ -2539,8 +2503,7 @@ WgradMfmaPlan wgrad_gemm_plan(const stcd_conv_geom& g, int kpad, int wld) {
     p.gy = (g.ci + T - 1) / T; p.gz = (g.co + T - 1) / T;
     const int64_t nchunks = (M + 63) / 64;
     // about 1024 blocks per launch (two rounds of two blocks per CU), at least 4 chunks per block, slabs <= 16 MB per layer
-    static const int target_blocks = [] { const char* e = getenv("STCD_WGEMM_BLOCKS"); return e ? atoi(e) : 512; }();
-    static const int min_chunks = [] { const char* e = getenv("STCD_WGEMM_MIN_CHUNKS"); return e ? atoi(e) : 16; }();
+    constexpr int target_blocks = 512, min_chunks = 16;
     int64_t gx = std::max<int64_t>(1, target_blocks / ((int64_t)p.gy * p.gz));
     gx = std::min<int64_t>(gx, std::max<int64_t>(1, nchunks / min_chunks));
     gx = std::min<int64_t>(gx, std::max<int64_t>(1, ((int64_t)16 << 20) / ((int64_t)kpad * wld * 4)));

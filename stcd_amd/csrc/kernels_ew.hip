@@ -83,7 +83,7 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int ew_grid(int64_t total_threads) { return (int)std::min<int64_t>(cdiv(total_threads, 256), 2048); }
 // channel slabs of the BatchNorm consumer kernels: 64 channels per block from 128 channels up (a pixel's slab is one 128-B line)
 static inline int bn_slabs(int C) {
-    static const int min_c = [] { const char* e = getenv("STCD_BN_SLAB_MIN_C"); return e ? atoi(e) : 128; }();
+    constexpr int min_c = 128;
     return (C >= min_c && C % 64 == 0) ? C / 64 : 1;
 }
 
@@ -237,7 +237,7 @@ __device__ __forceinline__ float block_reduce16_get(const float* __restrict__ re
 // chunks per group: ~2048 16-byte pieces (8 per thread) per block, so small-spatial / wide-channel layers still
 // spread over the whole chip (a 32x32x128-channel map used to get 16 blocks)
 int bn_stats_chunks(int64_t ppg, int C) {
-    static const int per = [] { const char* e = getenv("STCD_BN_CHUNK_PIECES"); return e && atoi(e) >= 256 ? atoi(e) : 2048; }();
+    constexpr int per = 2048;
     int64_t c = ppg * (C / 8) / per;
     if (c < 1) c = 1;
     if (c > 1024) c = 1024;
@@ -397,17 +397,6 @@ __device__ __forceinline__ void bn_bwd_table(float* tab, const long long* __rest
         }
         if (publish && dgamma) { dgamma[c] = (float)tg; dbeta[c] = (float)tb; if (dbeta_copy) dbeta_copy[c] = (float)tb; }
     }
-}
-
-// One small launch that turns a layer's forward accumulators into its published table (stat: mean, invstd, scale, shift) and updates the
-// running statistics -- for virtual activations (XfSrc): the consumers' blocks then read 2 * C floats instead of each deriving the
-// table from 2 * C * BN_REP integers with double-precision divisions and square roots in its prologue (STCD_XF_MODE, engine.hip).
-__global__ void k_bn_finalize(const XfSrc x) {
-    extern __shared__ float fin_tab[];
-    bn_fwd_table(fin_tab, x.facc, x.gamma, x.beta, x.rmean, x.rvar, x.stat, x.C, x.groups, x.ppg, x.momentum, x.eps, true);
-}
-void launch_bn_finalize(const XfSrc& x, hipStream_t s) {
-    k_bn_finalize<<<1, 128, (size_t)x.groups * 2 * x.C * 4, s>>>(x);
 }
 
 __global__ void k_bn_eval_prepare(int C, int groups, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -1600,10 +1589,8 @@ void launch_skip_bwd(int dt, int mode, const void* A, int lda, int64_t a_goff, c
 
 // channels per thread: 8 (2 waves / SIMD, fewer instructions per element) or 4 (4 waves / SIMD).  Measured at 16 pairs of 256 x 256
 // (us, V = 8 / V = 4): level 1 (16 ch, 256^2) 75.3 / 60.4; level 2 32.1 / 32.0; level 3 23.1 / 27.5; level 4 13.4 / 19.4 -- the
-// narrow piece pays where the map is large enough for the latency hiding to matter.  STCD_SKIP_PAIR_V=4|8 forces one.
+// narrow piece pays where the map is large enough for the latency hiding to matter.
 static int skip_pair_v(int B, int H, int W, int C) {
-    static const int env = [] { const char* e = getenv("STCD_SKIP_PAIR_V"); return e ? atoi(e) : 0; }();
-    if (env == 4 || env == 8) return env;
     return (int64_t)B * H * W * C >= ((int64_t)12 << 20) ? 4 : 8;
 }
 bool skip_pair_supported(int B, int H, int W, int C) {

@@ -195,7 +195,7 @@ void launch_col2im(int dt, const void* dcol, int ldc, void* dX, int lddx, int n,
         else k_col2im_patch<float><<<grid, 256, lds, s>>>((const float*)dcol, ldc, (float*)dX, lddx, H, W, C, k, Ho, Wo, accumulate);
         return;
     }
-    static const bool no_tile = [] { const char* e = getenv("STCD_NO_COL2IM_TILE"); return e && e[0] == '1'; }();
+    static const bool no_tile = env_flag("STCD_NO_COL2IM_TILE", false);
     if (stride < k && !no_tile) {
         const int tx = (W + 7) / 8, ty = (H + 7) / 8;
         const size_t lds = (size_t)64 * 64 * 4 + (size_t)64 * k * k * dsize(dt);
@@ -921,7 +921,7 @@ k_dw_strip(const T* __restrict__ src, T* __restrict__ u, T* __restrict__ a, cons
     }
 }
 static bool dw_strip_on() {
-    static const bool on = [] { const char* e = getenv("STCD_NO_DW_STRIP"); return !(e && e[0] == '1'); }();
+    static const bool on = !env_flag("STCD_NO_DW_STRIP", false);
     return on;
 }
 void launch_dwgelu_fwd(int dt, const void* h, void* u, void* a, const float* w, const float* b, int n, int H, int W, int Ch,

@@ -279,7 +279,7 @@ k_wgrad_dma(const WgradJob* __restrict__ jobs, int njobs, const char* base) {
 }
 
 static bool wgrad_dma_enabled() {
-    static const bool on = [] { const char* e = getenv("STCD_NO_WGRAD_DMA"); return !(e && e[0] == '1'); }();
+    static const bool on = !env_flag("STCD_NO_WGRAD_DMA", false);
     return on;
 }
 

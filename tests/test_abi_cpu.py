@@ -135,3 +135,27 @@ def test_segcd_family_state_dict_layout_is_the_reference_layout(cls_name, encode
     calls = {b.name: b.calls_per_forward for b in m._engine.bns}
     enc_calls, dec_calls = {"SegCD": (2, 2), "UnetSeg": (1, 1), "FFCTLCD": (2, 3)}[cls_name]
     assert calls["encoder.bn1"] == enc_calls and calls["decoder.blocks.0.conv1.1"] == dec_calls      # num_batches_tracked increments
+
+
+def test_environment_switches_are_the_documented_ones():
+    """Every STCD_* variable the library reads (all through env_int / env_flag of csrc/common.h) is in README.md's switch section,
+    the section names no C-level switch the library does not read, and the set stays small."""
+    import glob
+
+    csrc = os.path.join(REPO, "stcd_amd", "csrc")
+    read = set()
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.inl")) + glob.glob(os.path.join(csrc, "*.h"))):
+        text = open(path).read()
+        read |= set(re.findall(r"\benv_(?:int|flag)\(\s*\"(STCD_[A-Z0-9_]+)\"", text))
+        if os.path.basename(path) != "common.h":
+            assert "getenv" not in text, f"{os.path.basename(path)} reads the environment past env_int / env_flag"
+    assert read, "no switch reads found"
+    readme = open(os.path.join(REPO, "README.md")).read()
+    section = readme.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    documented = set(re.findall(r"STCD_[A-Z0-9_]+", section))
+    # read by Python, bench.py or the tests only
+    elsewhere = {"STCD_DTYPE", "STCD_DROPOUT_SEED", "STCD_LIB_PATH", "STCD_DDP_REHEARSAL", "STCD_CPU_THREADS", "STCD_TEST_FULL"}
+    c_level = {n for n in documented if n not in elsewhere and not n.startswith("STCD_BENCH_")}
+    assert read - documented == set(), f"read but not documented: {sorted(read - documented)}"
+    assert c_level - read == set(), f"documented but not read: {sorted(c_level - read)}"
+    assert len(read) <= 25, sorted(read)
