@@ -9,6 +9,25 @@ at exactly the points where the HIP engine's bf16 mode STORES a tensor, forward 
             data-gradient conv's output, or pool + fusion gradient summed then rounded -- k_skip_bwd; dY: k_bn_bwd_apply's output);
             d(logits) is rounded when it is packed for the last layer's gradient launches (k_gout_pack)
 
+Per network (stcd_amd/csrc/engine.hip: forward_fcsiam, xconc_forward, xconc_backward, the encoder loop of backward_fcsiam):
+
+  diff, sub   two streams; the fused skip is formed from the rounded activations and rounded once more; its gradient and the pool
+              gradient are summed in fp32 and rounded once (k_skip_bwd)
+  conc        two streams; the skip IS the stored activation (inside the concat buffer: not rounded a second time).  Backward: the
+              decoder conv's data gradient stores the gradient of the whole concat buffer (rounded); k_pool_bwd(accumulate = 1) then
+              reads that stored value, adds the pool gradient in fp32 and stores the sum -- rounded AGAIN (skip_branch below)
+  fcef        ONE stream over cat(x1, x2) (k_in_pack, concat mode: the concatenated input is stored rounded); skip and skip gradient
+              as conc, one date
+  xconc       two streams; per level the cross_conc block (cross_conc below), in order: G = pairwise depthwise conv of the stored
+              skip activations, stored rounded (k_pairdw_* read the fp32 filter from the parameter buffer: no bf16 filter image);
+              R = relu(BN(G)) stored rounded, batch statistics of the rounded G; Y = conv_res of R with the bf16 filter image, stored
+              rounded; A = relu(BN(Y)) stored rounded into the concat slice; no dropout inside the block.  Backward: dA (the concat
+              gradient), dY, dR, dG are each rounded where they are written; k_pairdw_bwd_data stores both dates' skip gradient
+              (rounded) and the pool gradient is accumulated onto it as for conc (rounded again)
+
+q and ste keep the dtype of their argument, so the same emulation runs in float64 arithmetic with the same roundings
+(tests/bf16_yardstick.py: the distance between two correct bf16 evaluations).
+
 What this file is for: rounding noise of ~20 bf16-stored layers moves whole-network gradients far from
 the fp32 reference's, so a bound against the fp32 reference alone cannot tell rounding from a wrong term.  Against THIS emulation
 the engine's bf16 gradients must agree closely (tests/test_bf16_emulation_gpu.py): what is left is accumulation order and the
@@ -29,11 +48,11 @@ class _Q(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, fwd, bwd):
         ctx.bwd = bwd
-        return x.bfloat16().float() if fwd else x.clone()
+        return x.bfloat16().to(x.dtype) if fwd else x.clone()
 
     @staticmethod
     def backward(ctx, g):
-        return (g.bfloat16().float() if ctx.bwd else g), None, None
+        return (g.bfloat16().to(g.dtype) if ctx.bwd else g), None, None
 
 
 def q(x, fwd=True, bwd=True):
@@ -42,7 +61,7 @@ def q(x, fwd=True, bwd=True):
 
 def ste(w):
     """bf16 filter image in the products, fp32 weight gradient (straight through)"""
-    return w + (w.detach().bfloat16().float() - w.detach())
+    return w + (w.detach().bfloat16().to(w.dtype) - w.detach())
 
 
 @contextlib.contextmanager
@@ -71,16 +90,40 @@ def emulate():
         R.conv3x3, R.convT3x3_s1, R.convT3x3_s2, R.maxpool2, R._cbrd = orig[:5]
 
 
+def skip_branch(f, date):
+    """The skip activation as the concat / cross_conc consumer reads it (conc, fcef, xconc).  Forward: the stored activation itself, not
+    rounded again.  Backward: that consumer's data gradient is STORED in the activation's gradient buffer (rounded: the decoder conv's
+    data-gradient launch writes the whole concat gradient, k_pairdw_bwd_data both dates' halves) before k_pool_bwd(accumulate = 1)
+    reads it back, adds the pool gradient in fp32 and stores the sum (rounded again, by the q(a) of the producing layer)."""
+    return q(f, fwd=False)
+
+
+def cross_conc(st, l, f1, f2):
+    """The cross_conc block as xconc_forward / xconc_backward store it (training mode, no dropout inside the block)."""
+    n, c, h, w = f1.shape
+    p = f"cross_conc{l}."
+    pair = torch.stack((skip_branch(f1, 0), skip_branch(f2, 1)), 2).reshape(n, 2 * c, h, w)
+    # k_pairdw_* read the fp32 filter from the parameter buffer: no bf16 filter image here
+    g = q(torch.nn.functional.conv2d(pair, st[p + "diff.0.weight"], st[p + "diff.0.bias"], padding=1, groups=c))       # G, dG
+    z = R.batchnorm(g, st[p + "diff.1.weight"], st[p + "diff.1.bias"], st[p + "diff.1.running_mean"], st[p + "diff.1.running_var"], True)
+    st[p + "diff.1.num_batches_tracked"] += 1
+    r = q(torch.relu(z))                                                                                                # R, dR
+    y = q(R.conv3x3(r, ste(st[p + "conv_res.0.weight"]), st[p + "conv_res.0.bias"]))                                    # Y, dY
+    z = R.batchnorm(y, st[p + "conv_res.1.weight"], st[p + "conv_res.1.bias"], st[p + "conv_res.1.running_mean"],
+                    st[p + "conv_res.1.running_var"], True)
+    st[p + "conv_res.1.num_batches_tracked"] += 1
+    return q(torch.relu(z))                                                                                             # A in the concat slice
+
+
 def forward(arch, st, x1, x2, masks):
-    """Training-mode forward of the emulation.  The skip fusion is rounded where the oracle concatenates it."""
-    fuse_q = {"diff": lambda f1, f2: q(torch.abs(f1 - f2)), "sub": lambda f1, f2: q(f2 - f1)}
+    """Training-mode forward of the emulation, all five networks of oracle.fcsiam_ref.ARCHS.  The loops of R.forward are restated to
+    place the roundings that sit between its layers (tests/test_bf16_emulation_cpu.py: with every rounding a no-op this IS R.forward)."""
+    assert arch in R.ARCHS
     with emulate():
-        if arch == "conc":
-            return R.forward(arch, st, q(x1, bwd=False), q(x2, bwd=False), training=True, masks=masks)
-        # diff / sub: re-state the decoder loop only to place the rounding of the fused skip (R.forward computes it inline)
         B = x1.shape[0]
         skips, bott = [], None
-        for t, x in enumerate((q(x1, bwd=False), q(x2, bwd=False))):
+        x1, x2 = q(x1, bwd=False), q(x2, bwd=False)
+        for t, x in enumerate((torch.cat((x1, x2), 1),) if arch == "fcef" else (x1, x2)):
             feats = []
             for stage in R.ENCODER:
                 for sfx, _, _ in stage:
@@ -91,9 +134,18 @@ def forward(arch, st, x1, x2, masks):
             bott = x
         x = bott
         for lvl, (up, c, convs) in zip((3, 2, 1, 0), R.DECODER):
-            f1, f2 = skips[0][lvl], skips[1][lvl]
+            f1, f2 = skips[0][lvl], skips[-1][lvl]
             x = R.pad_to(R.convT3x3_s2(x, st[f"{up}.weight"], st[f"{up}.bias"]), f1)
-            x = torch.cat((x, fuse_q[arch](f1, f2)), 1)
+            if arch == "xconc":
+                x = torch.cat((x, cross_conc(st, lvl + 1, f1, f2)), 1)
+            elif arch == "fcef":
+                x = torch.cat((x, skip_branch(f1, 0)), 1)
+            elif arch == "conc":
+                x = torch.cat((x, skip_branch(f1, 0), skip_branch(f2, 1)), 1)
+            elif arch == "diff":
+                x = torch.cat((x, q(torch.abs(f1 - f2))), 1)
+            else:
+                x = torch.cat((x, q(f2 - f1)), 1)
             for sfx, _, _ in convs:
                 if sfx == "11d":
                     x = R.convT3x3_s1(x, st["conv11d.weight"], st["conv11d.bias"])

@@ -1138,6 +1138,17 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
     };
     for (const Cbrd& L : e.enc) rec_layer(L);
     for (const Cbrd& L : e.dec) rec_layer(L);
+    for (const XConc& X : e.xc) {      // cross_conc block: the pairwise conv as a layer of its own (Y = G, A = R, dY = dG), then conv_res
+        auto rec = [&](const char* sfx, const TRef& t) {
+            stcd_ws_tensor r;
+            memset(&r, 0, sizeof(r));
+            snprintf(r.name, sizeof(r.name), "cross_conc%d.diff.0.%s", X.level + 1, sfx);
+            r.offset_bytes = t.off; r.n = X.res.N; r.h = X.res.H; r.w = X.res.W; r.c = X.C; r.ld = t.ld; r.dtype = e.dt;
+            e.ws_tensors.push_back(r);
+        };
+        rec("Y", X.G); rec("A.g0", X.R); rec("dY", X.dG);
+        rec_layer(X.res);
+    }
 
     build_pack_jobs(e, ws);
     e.jobs_uploaded_ws = nullptr;

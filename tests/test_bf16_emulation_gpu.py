@@ -12,13 +12,15 @@ import torch
 from oracle import fcsiam_bf16 as E
 from oracle import fcsiam_ref as R
 from stcd_amd import synth
-from stcd_amd.modules import SiamUnet_conc, SiamUnet_diff, SiamUnet_sub
+from stcd_amd.modules import SiamUnet_conc, SiamUnet_cross_conc, SiamUnet_diff, SiamUnet_sub, Unet
 from stcd_amd.optim import FlatAdamW
 from tests import _util
+from tests import bf16_yardstick as Y
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-CLS = {"diff": SiamUnet_diff, "conc": SiamUnet_conc, "sub": SiamUnet_sub}
+CLS = {"diff": SiamUnet_diff, "conc": SiamUnet_conc, "sub": SiamUnet_sub, "fcef": Unet, "xconc": SiamUnet_cross_conc}
+NEW = ("fcef", "xconc")      # no absolute floors measured for these two: bounded by the order-noise yardstick (tests/bf16_yardstick.py)
 
 
 def _first(out):
@@ -26,14 +28,7 @@ def _first(out):
 
 
 def _oracle_grads(arch, st, x1, x2, tgt, masks, emulate):
-    ref = {k: v.clone() for k, v in st.items()}
-    for k, v in ref.items():
-        if v.dtype.is_floating_point and "running" not in k:
-            v.requires_grad_(True)
-    logits = E.forward(arch, ref, x1, x2, masks) if emulate else R.forward(arch, ref, x1, x2, training=True, masks=masks)
-    loss = R.cross_entropy(logits, tgt)
-    loss.backward()
-    return loss.item(), logits.detach(), {k: v.grad for k, v in ref.items() if v.requires_grad}
+    return Y.oracle_grads(arch, st, x1, x2, tgt, masks, emulate)
 
 
 def _engine_grads(arch, st, x1, x2, tgt, masks, dtype):
@@ -48,17 +43,10 @@ def _engine_grads(arch, st, x1, x2, tgt, masks, dtype):
     return loss.item(), logits.detach().cpu(), {k: p.grad.detach().cpu() for k, p in m.named_parameters()}
 
 
-def _cosines(got, ref):
-    out = []
-    for k, g in ref.items():
-        if _util.zero_grad_by_construction(k) or float(g.abs().max()) < 1e-9:
-            continue
-        rel, cos = _util.rel_l2_cos(got[k].numpy(), g.numpy())
-        out.append((cos, rel, k))
-    return sorted(out)
+_cosines = Y.cosines
 
 
-@pytest.mark.parametrize("arch", ["diff", "conc", "sub"])
+@pytest.mark.parametrize("arch", ["diff", "conc", "sub", "fcef", "xconc"])
 def test_bf16_engine_matches_the_bf16_emulating_oracle_at_random_init(arch):
     seed = 700
     rng = np.random.default_rng(seed + 1)
@@ -72,6 +60,8 @@ def test_bf16_engine_matches_the_bf16_emulating_oracle_at_random_init(arch):
     lm, om, gm = _oracle_grads(arch, st, x1, x2, tgt, masks, emulate=True)
     lf, of_, gf = _oracle_grads(arch, st, x1, x2, tgt, masks, emulate=False)
     vs_emul, vs_fp32, emul_vs_fp32 = _cosines(ge, gm), _cosines(ge, gf), _cosines(gm, gf)
+    yard = Y.yardstick(arch, st, x1, x2, tgt, masks, gm)
+    print(f"{arch} random init: yardstick (emulation in fp32 vs fp64 arithmetic) worst {yard[0][0]:.4f} ({yard[0][2]}) median {yard[len(yard) // 2][0]:.4f}")
     print(f"{arch} random init: engine vs emulation worst {vs_emul[0][0]:.4f} ({vs_emul[0][2]}) median {vs_emul[len(vs_emul) // 2][0]:.4f} | "
           f"engine vs fp32 oracle worst {vs_fp32[0][0]:.4f} median {vs_fp32[len(vs_fp32) // 2][0]:.4f} | "
           f"emulation vs fp32 oracle worst {emul_vs_fp32[0][0]:.4f} median {emul_vs_fp32[len(emul_vs_fp32) // 2][0]:.4f}")
@@ -82,24 +72,53 @@ def test_bf16_engine_matches_the_bf16_emulating_oracle_at_random_init(arch):
     # which differ only in accumulation order decorrelate a little -- but the engine is 3x closer to the emulation than either is to
     # fp32, and no further from fp32 than the emulation is (medians within 0.005; the single worst tensor, an extreme statistic of 48,
     # within 0.07).  The partly-trained fixture below carries the tight bounds.
-    assert vs_emul[0][0] >= 0.90, vs_emul[:4]
-    assert vs_emul[len(vs_emul) // 2][0] >= 0.97
+    if arch in NEW:
+        # FC-EF / cross_conc: two CORRECT bf16 evaluations of this fixture that differ only in accumulation order (the emulation in
+        # fp32 and in fp64 arithmetic) already sit at median 0.963 / 0.966, worst 0.910 / 0.897: the floors above do not carry over.
+        # With D = 1 - cosine the engine may be twice as far from the emulation as that pair is from each other (the conc
+        # calibration: the engine's MFMA accumulation order measures up to 1.6 x the CPU pair's distance, worst D 0.05-0.08 against
+        # 0.049, median 0.02 against 0.017).  A consistency screen: the partly-trained fixture below carries the tight bound.
+        # Measured (MI355X), worst / median: fcef engine vs emulation 0.9255 / 0.9673, yardstick 0.9104 / 0.9632 (both at 0.72-0.74 /
+        # 0.90 against the fp32 oracle); xconc 0.9185 / 0.9680, yardstick 0.8969 / 0.9658 (0.70 / 0.89 against the fp32 oracle).
+        assert 1.0 - vs_emul[0][0] <= 2.0 * (1.0 - yard[0][0]), (vs_emul[:4], yard[:4])
+        assert 1.0 - vs_emul[len(vs_emul) // 2][0] <= 2.0 * (1.0 - yard[len(yard) // 2][0])
+    else:
+        assert vs_emul[0][0] >= 0.90, vs_emul[:4]
+        assert vs_emul[len(vs_emul) // 2][0] >= 0.97
     assert vs_fp32[0][0] >= emul_vs_fp32[0][0] - 0.10 and vs_fp32[len(vs_fp32) // 2][0] >= emul_vs_fp32[len(emul_vs_fp32) // 2][0] - 0.02, \
         "the engine's bf16 gradients are further from the fp32 reference than bf16 storage explains"
 
 
-@pytest.mark.parametrize("arch", ["diff", "conc"])
+# partly-trained fixtures: arch -> (initialisation seed, AdamW steps).  For sub / fcef / xconc the REFERENCE ALONE (the yardstick on the
+# trained state) must keep every tensor at cosine >= 0.9975, half of the 0.005 the engine is allowed against the emulation.  xconc
+# after 100 steps does not (yardstick worst 0.99554, conv31.weight; the engine passed at 0.9963 all the same): it takes 200 steps
+# (yardstick, seed 31 / 32 / 33: 100 steps 0.99554 / 0.99771 / 0.99704, 200 steps 0.99829 / 0.99863 / 0.99713, 300 steps 0.99733 /
+# 0.99911 / 0.99933).  The fp32 engine's steps are bit-reproducible, so the state and the yardstick are the same in every run.
+TRAINED = {"diff": (31, 100), "conc": (31, 100), "sub": (31, 100), "fcef": (31, 100), "xconc": (31, 200)}
+
+
+@pytest.mark.parametrize("arch", ["diff", "conc", "sub", "fcef", "xconc"])
 def test_bf16_gradients_on_a_partly_trained_state(arch):
-    """100 AdamW steps of the fp32 engine on LEVIR-shaped synthetic pairs (stcd_amd.synth.make_batch: smooth imagery, ~5 % change),
-    then one step on a held-out batch: bf16 engine vs the emulation (tight) and vs the fp32 oracle (the meaningful bf16 bound)."""
+    """AdamW steps of the fp32 engine on LEVIR-shaped synthetic pairs (stcd_amd.synth.make_batch: smooth imagery, ~5 % change),
+    then one step on a held-out batch: bf16 engine vs the emulation (tight: a wrong term worth 10 % of a gradient is a cosine of
+    0.995 on every tensor it reaches, tests/test_bf16_emulation_cpu.py shows it on the xconc pairwise-conv data gradient) and vs
+    the fp32 oracle (the meaningful bf16 bound).
+    Measured (MI355X), worst cosine over the tensors (median 0.9997-0.9999 against the emulation everywhere):
+              engine vs emulation   engine vs fp32   emulation vs fp32   yardstick (emulation, fp32 vs fp64 arithmetic)
+      diff          0.9984              0.9833            0.9835              0.9957
+      conc          0.9980              0.9938            0.9944              0.9991
+      sub           0.9984              0.9944            0.9946              0.9979
+      fcef          0.9976              0.9973            0.9976              0.9984
+      xconc         0.9989                 -                 -                0.9983   (200 steps; after 100: 0.9963 / 0.9875 / 0.9875 / 0.9955)"""
     B, S = 8, 128
+    seed, steps = TRAINED[arch]
     a, b, lab = synth.make_batch(B, S, S, seed=77)
     A, Bt, L = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV), torch.from_numpy(lab).to(DEV)
     m = CLS[arch](3, 2, dtype="fp32")
-    m.load_state_dict(R.synth_state(arch, 3, 2, 31))
+    m.load_state_dict(R.synth_state(arch, 3, 2, seed))
     m.to(DEV).train()
     opt = FlatAdamW(m, lr=1e-3, betas=(0.9, 0.999), weight_decay=0.01)
-    for _ in range(100):
+    for _ in range(steps):
         opt.zero_grad(set_to_none=True)
         torch.nn.functional.cross_entropy(_first(m(A, Bt)), L).backward()
         opt.step()
@@ -111,13 +130,21 @@ def test_bf16_gradients_on_a_partly_trained_state(arch):
     le, oe, ge = _engine_grads(arch, st, x1, x2, tgt, masks, "bf16")
     lm, om, gm = _oracle_grads(arch, st, x1, x2, tgt, masks, emulate=True)
     lf, of_, gf = _oracle_grads(arch, st, x1, x2, tgt, masks, emulate=False)
-    vs_emul, vs_fp32 = _cosines(ge, gm), _cosines(ge, gf)
+    vs_emul, vs_fp32, emul_vs_fp32 = _cosines(ge, gm), _cosines(ge, gf), _cosines(gm, gf)
+    yard = Y.yardstick(arch, st, x1, x2, tgt, masks, gm)
     print(f"{arch} trained state: loss engine {le:.4f} emulation {lm:.4f} fp32 {lf:.4f} | engine vs emulation worst {vs_emul[0][0]:.4f} "
           f"({vs_emul[0][2]}) median {vs_emul[len(vs_emul) // 2][0]:.4f} | engine vs fp32 oracle worst {vs_fp32[0][0]:.4f} ({vs_fp32[0][2]}) "
-          f"median {vs_fp32[len(vs_fp32) // 2][0]:.4f}")
-    # measured: vs emulation worst 0.9985 / 0.9992 (median 0.9998), vs the fp32 oracle worst 0.991 / 0.994 (median 0.999)
+          f"median {vs_fp32[len(vs_fp32) // 2][0]:.4f} | emulation vs fp32 oracle worst {emul_vs_fp32[0][0]:.4f} | "
+          f"yardstick worst {yard[0][0]:.5f} ({yard[0][2]}) median {yard[len(yard) // 2][0]:.5f}")
+    # a condition on the FIXTURE, not a measurement of the engine: the reference alone may use at most half of the 0.005 allowance
+    new = arch in ("sub",) + NEW                                   # new to this test: diff / conc keep their assertions as they were
+    assert yard[0][0] >= 0.9975 or not new, (f"fixture of {arch} (synth_state seed {seed}, {steps} AdamW steps on make_batch(8, 128, 128, seed=77), held-out "
+                                  f"seed 78): two correct bf16 evaluations already differ by {yard[:3]}; change the fixture, not the bound")
     assert vs_emul[0][0] >= 0.995, vs_emul[:4]
-    assert vs_fp32[0][0] >= 0.98, vs_fp32[:4]
+    if new:
+        assert vs_fp32[0][0] >= emul_vs_fp32[0][0] - 0.01, (vs_fp32[:4], emul_vs_fp32[:4])
+    else:
+        assert vs_fp32[0][0] >= 0.98, vs_fp32[:4]                # measured for diff / conc
     assert abs(le - lf) < 5e-3
 
 

@@ -1,6 +1,8 @@
 """Parity of the HIP engine (through the nn.Module boundary -> C ABI) against the golden vectors captured
 from the reference and against the CPU oracle.  fp32 mode carries the 1e-3 bar of BASELINE.json;
 bf16 mode is checked against the same vectors at a bf16-sized tolerance (stated per test)."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -442,6 +444,7 @@ def test_full_size_properties_other_configs_bf16(arch):
 # changes nothing: cosine 1.0000).  The engine measures median 0.88 / 0.91, worst 0.76 / 0.76; SNUNet (residual blocks, no
 # |a-b| fusion) median 0.987, worst 0.952.  The bounds sit just under the measured values: what they catch is a wrong
 # term, not rounding (the exact-arithmetic checks of the same kernels are the fp32 runs above and the per-op tests).
+# The bf16 bound that CAN see a wrong term is tests/test_bf16_emulation_gpu.py (all five FC-Siam networks against the bf16-emulating oracle).
 BF16_LOGIT_ERR, BF16_LOSS_ERR = 6e-2, 2e-2
 BF16_GRAD = {"diff": (0.72, 0.80), "conc": (0.72, 0.80), "snunet": (0.94, 0.36), "fcef": (0.72, 0.80), "xconc": (0.70, 0.82)}      # (xconc: two more BatchNorm-ed layers on every skip; measured 0.7198 / 0.761)     # (min cosine, max relative l2) per tensor
 
@@ -554,8 +557,17 @@ def test_frozen_weights_context_packs_once_and_is_exact():
 # torch's own layer applied to the layer's stored input / output gradient: conv output (one bf16 rounding), weight and bias
 # gradient (fp32 accumulation on both sides), BatchNorm + ReLU per date.  Dropout is switched off (p = 0) so the activation is a
 # function of the stored conv output alone.
+# FC-EF: one stream (every encoder layer is ONE BatchNorm group), conv11 reads 6 of 8 padded channels, the skip activation sits in the
+# concat buffer.  SiamUnet_cross_conc: the block of every level adds two layers -- `cross_conc{l}.diff.0`, the pairwise depthwise
+# conv (kernels_xconc.hip: reads the two dates' stored skip activations `goff` apart, fp32 filter, recorded as Y = G, A.g0 = R,
+# dY = dG), checked against torch's grouped conv of the interleaved stored activations, and `cross_conc{l}.conv_res.0`, whose
+# BatchNorm + ReLU writes the skip slice of the concat buffer (ld = 2 C) -- 64 x 64 / 48 x 80 leave a level-4 map of 4 x 4 / 3 x 5.
+# NOT checked in place, on purpose: the two dates' data gradient out of k_pairdw_bwd_data -- its buffer receives the pool gradient
+# and is then overwritten by the BatchNorm backward (in place); test_pairwise_depthwise_conv_vs_torch (strided) and
+# tests/test_bf16_emulation_gpu.py cover it.
 @pytest.mark.parametrize("arch,dtype,B,H,W,virt", [("diff", "bf16", 2, 64, 64, 0), ("conc", "bf16", 3, 48, 80, 0), ("sub", "bf16", 2, 32, 32, 0),
-                                                   ("diff", "fp32", 2, 32, 48, 0), ("diff", "bf16", 2, 64, 64, 1), ("conc", "bf16", 3, 48, 80, 1)])
+                                                   ("diff", "fp32", 2, 32, 48, 0), ("diff", "bf16", 2, 64, 64, 1), ("conc", "bf16", 3, 48, 80, 1),
+                                                   ("fcef", "bf16", 2, 64, 64, 0), ("xconc", "bf16", 2, 64, 64, 0), ("xconc", "fp32", 3, 48, 80, 0)])
 def test_fcsiam_every_layer_in_place(monkeypatch, arch, dtype, B, H, W, virt):
     monkeypatch.setenv("STCD_VIRT_ACT", str(virt))      # 1: the virtual-activation plan (opt-in)
     rng = np.random.default_rng(41)
@@ -570,8 +582,11 @@ def test_fcsiam_every_layer_in_place(monkeypatch, arch, dtype, B, H, W, virt):
     loss.backward()
     torch.cuda.synchronize()
     ws = m._engine.ws_tensors()
-    names = sorted({k.split(".")[0] for k in ws})
-    assert len(names) == 19, names              # 10 encoder + 9 decoder conv+BN layers (conv11d has no BatchNorm: checked end to end)
+    names = sorted({re.sub(r"\.(in|in\.virt|Y|A\.g\d+|dY)$", "", k) for k in ws})
+    # 10 encoder + 9 decoder conv+BN layers (conv11d has no BatchNorm: checked end to end); cross_conc: two more on each of the 4 skips
+    assert len(names) == (19 + 8 if arch == "xconc" else 19), names
+    if arch == "fcef":
+        assert ws["conv11.in"].shape[0] == B and not any(k.endswith(".A.g1") for k in ws)      # one stream, one BatchNorm group
     tol = 5e-6 if dtype == "fp32" else 3e-3      # bf16: the stored Y is rounded to bf16 (2^-9 per element)
     wq = (lambda w: w.detach().to(torch.bfloat16).float()) if dtype == "bf16" else (lambda w: w.detach())
     nchw = lambda t_: t_.permute(0, 3, 1, 2).float().contiguous()
@@ -598,8 +613,14 @@ def test_fcsiam_every_layer_in_place(monkeypatch, arch, dtype, B, H, W, virt):
 
     n_virt = 0
     for name in names:
-        conv, bn = getattr(m, name), getattr(m, "bn" + name[4:])
-        if name + ".in.virt" in ws:
+        conv, bn = (getattr(m, name), getattr(m, "bn" + name[4:])) if name.startswith("conv") else (m.get_submodule(name), m.get_submodule(name[:-1] + "1"))
+        pairdw = name.endswith(".diff.0")
+        if pairdw:
+            # the pairwise depthwise conv reads the level's skip layer as the encoder stored it, one date per BatchNorm group
+            skip = ("conv12", "conv22", "conv33", "conv43")[int(name[len("cross_conc")]) - 1]
+            f1, f2 = nchw(ws[skip + ".A.g0"]), nchw(ws[skip + ".A.g1"])
+            X = torch.stack((f1, f2), 2).reshape(f1.shape[0], 2 * f1.shape[1], f1.shape[2], f1.shape[3])      # 0::2 = date 1, 1::2 = date 2
+        elif name + ".in.virt" in ws:
             # virtual activation (round 4): the layer reads its producer's RAW conv output and applies BN + ReLU (+ Dropout2d) while
             # staging -- in the forward launch and in the weight gradient.  Both are checked against torch's convolution of the
             # activation computed HERE from that raw tensor; the producer records no A of its own.
@@ -611,17 +632,20 @@ def test_fcsiam_every_layer_in_place(monkeypatch, arch, dtype, B, H, W, virt):
         else:
             X = nchw(ws[name + ".in"])[:, :conv.in_channels]      # conv11: 3 of 8 padded channels
         Y, dY = nchw(ws[name + ".Y"]), nchw(ws[name + ".dY"])
-        Wv = wq(conv.weight).requires_grad_(True)
+        Wv = (conv.weight.detach().clone() if pairdw else wq(conv.weight)).requires_grad_(True)      # k_pairdw_* read the fp32 filter
         bv = conv.bias.detach().clone().requires_grad_(True)
-        if isinstance(conv, torch.nn.ConvTranspose2d):
+        if pairdw:
+            Yt = torch.nn.functional.conv2d(X, Wv, bv, padding=1, groups=conv.groups)
+        elif isinstance(conv, torch.nn.ConvTranspose2d):
             Yt = torch.nn.functional.conv_transpose2d(X, Wv, bv, stride=1, padding=1)
         else:
             Yt = torch.nn.functional.conv2d(X, Wv, bv, padding=1)
-        chk("conv output" + (" (virtual input)" if name + ".in.virt" in ws else ""), name, Y, Yt.detach())
+        chk(("pairwise depthwise output" if pairdw else "conv output") + (" (virtual input)" if name + ".in.virt" in ws else ""), name, Y, Yt.detach())
         Yt.backward(dY)
         # fp32 accumulation of the same bf16 products on both sides; a virtual input is re-derived HERE from the raw tensor (torch's
         # batch statistics against the engine's fixed-point sums): a handful of activations round to the neighbouring bf16 value
-        chk("weight gradient" + (" (virtual input)" if name + ".in.virt" in ws else ""), name, conv.weight.grad, Wv.grad, 2e-4 if name + ".in.virt" in ws else 5e-6)
+        chk(("pairwise depthwise " if pairdw else "") + "weight gradient" + (" (virtual input)" if name + ".in.virt" in ws else ""), name, conv.weight.grad, Wv.grad,
+            2e-4 if name + ".in.virt" in ws else 5e-6)
         # a bias in front of a training-mode BatchNorm has a mathematically zero gradient (the per-date sums of dY vanish): both
         # sides are rounding noise, so bound them against the natural scale sum|dY| instead of against each other
         scale = float(dY.abs().sum(dim=(0, 2, 3)).max())
@@ -642,6 +666,9 @@ def test_fcsiam_every_layer_in_place(monkeypatch, arch, dtype, B, H, W, virt):
         assert n_virt >= 9, n_virt          # 6 encoder + >= 3 decoder layers read a virtual activation in the bf16 plan
     else:
         assert n_virt == 0                  # the default plan and the fp32 parity path materialise everything
+    if arch == "xconc":
+        for l, c in enumerate((16, 32, 64, 128), 1):      # the block's second BatchNorm + ReLU wrote the skip half of the 2 C-wide concat buffer
+            assert ws[f"cross_conc{l}.conv_res.0.A.g0"].stride(2) == 2 * c and ws[f"conv{l}{2 if l < 3 else 3}d.in"].shape[-1] == 2 * c
     print(f"SiamUnet_{arch} {dtype} B={B} {H}x{W} layer-local worst relative l2: " + ", ".join(f"{k} {v[0]:.1e} ({v[1]})" for k, v in worst.items()))
 
 

@@ -425,12 +425,16 @@ def test_stem_maxpool3_and_gradient_vs_torch(dtype, n, c, h, w):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("n,c,h,w", [(2, 16, 12, 10), (1, 32, 7, 5), (3, 8, 16, 16), (2, 128, 8, 8), (2, 16, 64, 64), (1, 64, 33, 17)])
-def test_pairwise_depthwise_conv_vs_torch(dtype, n, c, h, w):
+@pytest.mark.parametrize("n,c,h,w,strided", [pytest.param(*shp, 0, id="-".join(map(str, shp))) for shp in
+                                             [(2, 16, 12, 10), (1, 32, 7, 5), (3, 8, 16, 16), (2, 128, 8, 8), (2, 16, 64, 64), (1, 64, 33, 17)]] +
+                         [pytest.param(2, 16, 12, 10, 1, id="2-16-12-10-strided"), pytest.param(1, 64, 33, 17, 1, id="1-64-33-17-strided")])
+def test_pairwise_depthwise_conv_vs_torch(dtype, n, c, h, w, strided):
     """cross_conc's Conv2d(2C, C, 3, padding=1, groups=C) on the channel-interleaved pair (SiamUnet_crossconc.py:14-18,24-29) as the
     engine runs it -- on the two dates stacked in the batch dimension, nothing interleaved in memory -- against torch's grouped
     convolution of the interleaved tensor: forward, both dates' data gradients, the filter gradient; odd maps, 1 ... 16 channel blocks,
-    multi-chunk filter-gradient grids."""
+    multi-chunk filter-gradient grids.  strided: every map sits in a buffer 2 C wide, as inside the engine -- the inputs in channels
+    [0, C) with NaN beside them (pixel stride lda = 2 C > C), the outputs written at channel offset C (ldo = 2 C) into a prefilled
+    buffer whose other half must come back untouched."""
     rng = np.random.default_rng(c * 100 + h + n)
     x1, x2 = rq(rng.standard_normal((n, c, h, w)), dtype), rq(rng.standard_normal((n, c, h, w)), dtype)
     wt = (rng.standard_normal((c, 2, 3, 3)) / 3).astype(np.float32)
@@ -443,20 +447,37 @@ def test_pairwise_depthwise_conv_vs_torch(dtype, n, c, h, w):
     y = torch.nn.functional.conv2d(inter, tw, torch.from_numpy(bias).double(), padding=1, groups=c)
     y.backward(torch.from_numpy(gy).double())
     geo = mg(2 * n, h, w, c, 2)
-    A = nhwc(np.concatenate([x1, x2]), dtype, ld=c)
-    out = torch.zeros(n, h, w, c, dtype=A.dtype, device=DEV)
+    ld, off = (2 * c, c) if strided else (c, 0)
+    FILL = 7.0
+
+    def src(x):          # an input map: channels [0, c) of an ld-wide buffer, NaN in the rest
+        t_ = nhwc(x, dtype, ld=ld)
+        t_[..., c:] = float("nan")
+        return t_
+
+    def dst(nimg):       # an output buffer and the pointer of its channel `off`
+        t_ = torch.full((nimg, h, w, ld), FILL if strided else float("nan"), dtype=DT[dtype][1], device=DEV)
+        return t_, C.c_void_p(t_.data_ptr() + off * t_.element_size())
+
+    def written(t_):     # the op's output as NCHW; the neighbouring half must still hold the prefill
+        if strided:
+            assert bool((t_[..., :off] == FILL).all()), "the op wrote outside its channel slice"
+        return nchw(t_[..., off:], c)
+
+    A = src(np.concatenate([x1, x2]))
+    out, out_p = dst(n)
     l = _lib.lib()
     W_, B_ = f32(wt), f32(bias)
-    _lib.check(l.stcd_op_pairdw(DT[dtype][0], C.byref(geo), P(A), c, P(W_), P(B_), P(out), c, stream()))
-    np.testing.assert_allclose(nchw(out, c), y.detach().numpy(), **TOL[dtype])
-    dO = nhwc(gy, dtype, ld=c)
-    dA = torch.full_like(A, float("nan"))
+    _lib.check(l.stcd_op_pairdw(DT[dtype][0], C.byref(geo), P(A), ld, P(W_), P(B_), out_p, ld, stream()))
+    np.testing.assert_allclose(written(out), y.detach().numpy(), **TOL[dtype])
+    dO = src(gy)
+    dA, dA_p = dst(2 * n)
     dw = torch.full((c, 2, 3, 3), float("nan"), dtype=torch.float32, device=DEV)
     nb = l.stcd_op_pairdw_scratch_bytes(C.byref(geo))
     sc = torch.zeros(nb, dtype=torch.uint8, device=DEV)
-    _lib.check(l.stcd_op_pairdw_bwd(DT[dtype][0], C.byref(geo), P(A), c, P(dO), c, P(W_), P(dA), c, P(dw), P(sc), nb, stream()))
+    _lib.check(l.stcd_op_pairdw_bwd(DT[dtype][0], C.byref(geo), P(A), ld, P(dO), ld, P(W_), dA_p, ld, P(dw), P(sc), nb, stream()))
     torch.cuda.synchronize()
-    got = nchw(dA, c)
+    got = written(dA)
     np.testing.assert_allclose(got[:n], t1.grad.numpy(), **TOL[dtype])
     np.testing.assert_allclose(got[n:], t2.grad.numpy(), **TOL[dtype])
     scale = float(tw.grad.abs().max())
