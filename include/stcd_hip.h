@@ -416,7 +416,10 @@ typedef struct stcd_conv_geom {
  * 2 = generic MFMA kernel, 3 = resident-halo kernel (wide 3x3 layers, opt-in in the engine), 6 = LDS-DMA kernel (Ci % 64 == 0,
  * Co % 256 == 0, an even number >= 4 of (64-channel chunk, tap) K-tiles: 256 positions x 256 channels per persistent 8-wave block,
  * `buffer_load ... lds` staging with counted vmcnt -- what the engine runs for ChangeFormer's 256 -> 256 decoder-head layers,
- * /root/reference/models/ChangeFormerBaseNetworks.py:85-120) */
+ * /root/reference/models/ChangeFormerBaseNetworks.py:85-120), 8 = LDS-DMA tile kernel (3x3 stride 1 over the full map, Ci % 64 == 0,
+ * Co % 16 == 0: the resident-filter kernel's 16 x 16 tile with the filter slice and the halo of all input channels requested by
+ * `buffer_load ... lds` before the first MFMA -- what the engine runs for FC-Siam's 64- to 256-channel layers on 64^2 / 32^2 maps;
+ * outputs bit-identical to impl 1's) */
 int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, const float* w, const float* bias,
                  void* out, void* scratch, int64_t scratch_bytes, void* hip_stream);
 /* dw: fp32 [ntaps][ci][co], overwritten; impl: 0 = reference FMA kernel, 1 = MFMA tile kernel (4: its 64 x 32-channel tile

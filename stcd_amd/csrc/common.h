@@ -285,6 +285,18 @@ int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvRe
                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
                     float s1_scale = BN_FS1, float s2_scale = BN_FS2, const XfSrc* xf = nullptr, const BwdSum* bs = nullptr);
 bool conv_res_bwdsum_ok(const stcd_conv_geom& g, const ConvResPlan& rp);
+// k_conv_res's tile and epilogue for 3x3 stride-1 convs with Ci % 64 == 0, Co % 16 == 0 on SMALL maps, staged by LDS-DMA: the filter
+// slice once per block and the 18 x 18 halo in 64-channel parts, all K of a tile requested before its first MFMA (Ci <= 128; two
+// parts in flight for Ci = 256); kernels_conv_tile.hip.  Reads the CiB = 64 fragment image; outputs bit-identical to k_conv_res's.
+struct ConvTilePlan {
+    int NT = 0, nparts = 0, nbuf = 0, nslices = 0, P = 0, blocks = 0, ntiles = 0;
+    int filt_bytes = 0, lds_bytes = 0;
+    bool ok = false;
+};
+ConvTilePlan conv_tile_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int groups);
+int launch_conv_tile(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvTilePlan& tp, const void* in, const void* wf,
+                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
+                     float s1_scale = BN_FS1, float s2_scale = BN_FS2);
 // Tap-list convolutions with Ci % 64 == 0, Co % 64 == 0 as a tiled GEMM [positions x (taps * Ci)] . [(taps * Ci) x Co]: 128x128
 // or 64x64 block tiles staged through LDS in (64-channel chunk, tap) steps, fused bias + BN statistics, LDS-transposed 16-B
 // output stores.  1x1 convolutions of any stride, and the wide layers the resident-filter kernel cannot take.

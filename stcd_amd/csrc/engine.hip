@@ -61,6 +61,7 @@ struct ConvOp {
     ConvGemmPlan gemm;                    // 1x1 convs with Ci % 64 == 0, Co % 64 == 0: tiled GEMM
     ConvDmaPlan dma;                      // wide layers on large maps: 256 x 256 implicit-GEMM tile staged by LDS-DMA (kernels_conv_dma.hip)
     ConvHaloPlan halo;                    // wide 3x3 layers on large maps: resident halo, streamed filter (opt-in, STCD_HALO_KERNEL=1)
+    ConvTilePlan tile;                    // k_conv_res layers with Ci % 64 == 0 on small maps: LDS-DMA staged tile kernel (pick_tile, FC-Siam only)
 };
 struct WgradOp {
     stcd_conv_geom g{};
@@ -290,7 +291,7 @@ struct stcd_engine_impl {
     int64_t final_bias_acc = -1;
     std::vector<BiasJob> bias_jobs; int64_t bias_jobs_off = -1;
     int64_t masks = -1, dwe_begin = -1, dwe_end = -1, scratch8 = -1;
-    int use_mfma = 1, use_small = 1, use_wgroup = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, use_bwdsum = 1, use_bwdsum_res = 0;
+    int use_mfma = 1, use_small = 1, use_wgroup = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, use_bwdsum = 1, use_bwdsum_res = 0, use_tile = 1;
     // FC-Siam backward: the decoder's grouped weight gradients (+ slab reduce, bias finish) run on a low-priority side stream beside
     // the encoder's backward chain on the caller's stream; their grids get 1 / WG_SIDE_DIV of the planner's block budget so that the
     // chain's blocks find free slots (wgrad_side_stream)
@@ -559,6 +560,7 @@ static void conv_work(const stcd_engine& e, const stcd_conv_geom& g, int kreal, 
 // run in 16-channel output slices, i.e. re-read X once per 16 output channels
 static void pick_gemm_or_res(const stcd_engine& e, ConvOp& op, const stcd_conv_geom& g, int groups) {
     op.gemm = ConvGemmPlan();
+    op.tile = ConvTilePlan();
     if (!e.use_gemm || op.small) return;
     // (ChangeFormer's 256-channel decoder convolutions get 16-channel output slices from the resident-filter kernel, i.e. X is
     //  re-read 16 times through L2: the GEMM kernel's 128 x 128 tile measured 8.3 vs 9.5 ms per step there; a tie elsewhere)
@@ -573,6 +575,17 @@ static void pick_gemm_or_res(const stcd_engine& e, ConvOp& op, const stcd_conv_g
     op.dma = ConvDmaPlan();
     if (op.gemm.ok && (int64_t)g.n * g.hm * g.wm >= 256 * 192) op.dma = conv_dma_plan(g, op.plan);
     if (halo_on && op.gemm.ok && (int64_t)g.n * ((g.hm + 15) / 16) * ((g.wm + 15) / 16) >= 512) op.halo = conv_halo_plan(g, op.plan);
+}
+
+// The LDS-DMA tile kernel takes a resident-filter layer (same tile, same results) where the launch is a short chain of steps per
+// block: Ci % 64 == 0 and at most TILE_MAX_TILES 16 x 16 tiles, i.e. each block of k_conv_res would walk only a few (tile, chunk)
+// steps and wait out a memory round trip in each.  Measured per shape in DESIGN.md section 4; STCD_NO_TILE_KERNEL=1 turns it off.
+constexpr int TILE_MAX_TILES = 512;
+static void pick_tile(const stcd_engine& e, ConvOp& op, const stcd_conv_geom& g, int groups) {
+    op.tile = ConvTilePlan();
+    if (!e.use_tile || !op.res.ok || op.gemm.ok || op.small) return;
+    const ConvTilePlan tp = conv_tile_plan(g, op.plan, groups);
+    if (tp.ok && tp.ntiles <= TILE_MAX_TILES) op.tile = tp;
 }
 
 // weight-gradient plan of one launch: the GEMM kernel for one-tap launches with >= 64 channels on both sides, else the tile kernel
@@ -961,6 +974,7 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
             op.small = conv_small_ok(g, op.plan);
             if (e.use_res && !op.small) op.res = conv_res_plan(g, op.plan, groups);
             pick_gemm_or_res(e, op, g, groups);
+            pick_tile(e, op, g, groups);
         }
         e.conv_ops.push_back(&op);
     };
@@ -1215,10 +1229,12 @@ static void exec_conv(const Ctx& c, const ConvOp& op, const void* in, const floa
     const bool small_path = !gemm_path && mfma_on(c.e) && op.small && op.wf >= 0 && c.e.use_small;
     const bool res_path = !gemm_path && !small_path && mfma_on(c.e) && op.res.ok && op.wf >= 0 && !nchw;
     const bool mfma_path = !small_path && !res_path && mfma_on(c.e) && op.plan.ok && op.wf >= 0;
+    const bool tile_path = res_path && op.tile.ok && !(xf && xf->on) && !bs;
     const bool dma_path = gemm_path && op.dma.ok && op.res_groups == 1 && !(stat_groups > 0 && stat_acc);
     if (dma_path) snprintf(kname, sizeof(kname), "k_conv_dma");
     else if (gemm_path && op.halo.ok && !(stat_groups > 0 && stat_acc)) snprintf(kname, sizeof(kname), "k_conv_halo");
     else if (gemm_path) snprintf(kname, sizeof(kname), "k_conv_gemm<%d>", op.gemm.W);
+    else if (tile_path) snprintf(kname, sizeof(kname), "k_conv_tile<%d>", op.tile.NT);
     else if (res_path) snprintf(kname, sizeof(kname), "k_conv_res<%d, %d, %s>", op.res.NT, op.res.CW, op.res.single_halo ? "true" : "false");
     else if (small_path) snprintf(kname, sizeof(kname), "k_conv_small<1, %d>", (op.g.ntaps * op.g.ci + 31) / 32 <= 5 ? 5 : 9);
     else if (mfma_path) snprintf(kname, sizeof(kname), "k_conv_mfma<%d>", op.plan.NT);
@@ -1261,6 +1277,15 @@ static void exec_conv(const Ctx& c, const ConvOp& op, const void* in, const floa
         long long* sp = (stat_groups > 0 && bn_form && stat_groups == groups) ? stat_acc : nullptr;
         if (launch_conv_small(op.g, in, c.at(op.wf), bias, out, nchw, groups, sp, op.g.co, c.s, xf) == 0) {
             if (stat_chunks && sp) *stat_chunks = 1;
+            return;
+        }
+    }
+    if (tile_path) {
+        const bool want = stat_groups > 0 && stat_groups == op.res_groups && stat_acc;
+        long long* sp = want ? stat_acc : nullptr;
+        if (launch_conv_tile(op.g, op.plan, op.tile, in, c.at(op.wf), bias, out, op.res_groups, sp, want ? sr->C : op.g.co, c.s,
+                             want ? sr->c0 : 0, want ? sr->s1 : BN_FS1, want ? sr->s2 : BN_FS2) == 0) {
+            if (stat_chunks && want) *stat_chunks = 1;
             return;
         }
     }
@@ -3112,6 +3137,7 @@ static void engine_env_switches(stcd_engine* e) {       // read at every stcd_cr
     e->use_small = !env_flag("STCD_NO_SMALL_KERNEL", false);
     e->use_gemm = !env_flag("STCD_NO_GEMM_KERNEL", false);
     e->use_res = !env_flag("STCD_NO_RES_KERNEL", false);
+    e->use_tile = !env_flag("STCD_NO_TILE_KERNEL", false);                  // 1: the small-map Ci % 64 == 0 layers of FC-Siam stay on k_conv_res
     e->use_wgroup = !env_flag("STCD_NO_WGRAD_GROUPS", false);
     e->use_act_fuse = !env_flag("STCD_NO_ACT_FUSE", false);
     e->use_skip_fused = !env_flag("STCD_NO_SKIP_FUSED", false);
@@ -3611,7 +3637,7 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
                  void* out, void* scratch, int64_t scratch_bytes, void* hip_stream) {
     if (check_geom(g)) return 1;
     STCD_CHECK(in && w && out, "null pointer argument");
-    if (impl == 1 || impl == 2 || impl == 3 || impl == 6) {
+    if (impl == 1 || impl == 2 || impl == 3 || impl == 6 || impl == 8) {
         STCD_CHECK(dtype == STCD_DTYPE_BF16, "the MFMA implementation is bf16 only");
         ConvMfmaPlan p = conv_mfma_plan(*g);
         STCD_CHECK(p.ok, "geometry not supported by the MFMA kernel");
@@ -3628,6 +3654,13 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
             const ConvDmaPlan dp = conv_dma_plan(*g, p);
             STCD_CHECK(dp.ok, "geometry not supported by the LDS-DMA kernel (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
             STCD_CHECK(launch_conv_dma(*g, p, dp, in, scratch, bias, out, (hipStream_t)hip_stream) == 0, "launch failed");
+            STCD_HIP(hipGetLastError());
+            return 0;
+        }
+        if (impl == 8) {      // k_conv_res's tile staged by LDS-DMA (3x3 stride 1, Ci % 64 == 0, Co % 16 == 0; the engine's choice on small maps)
+            const ConvTilePlan tp = conv_tile_plan(*g, p, 1);
+            STCD_CHECK(tp.ok, "geometry not supported by the LDS-DMA tile kernel (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
+            STCD_CHECK(launch_conv_tile(*g, p, tp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0, "launch failed");
             STCD_HIP(hipGetLastError());
             return 0;
         }
@@ -3655,7 +3688,7 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
         STCD_HIP(hipGetLastError());
         return 0;
     }
-    STCD_CHECK(impl == 0, "impl must be 0 (reference FMA), 1 (MFMA, auto-selected kernel), 2 (generic MFMA kernel), 3 (resident-halo kernel) or 6 (LDS-DMA kernel)");
+    STCD_CHECK(impl == 0, "impl must be 0 (reference FMA), 1 (MFMA, auto-selected kernel), 2 (generic MFMA kernel), 3 (resident-halo kernel), 6 (LDS-DMA kernel) or 8 (LDS-DMA tile kernel)");
     launch_conv_ref(dtype, *g, in, w, g->ci, g->co, bias, out, false, (hipStream_t)hip_stream);
     STCD_HIP(hipGetLastError());
     return 0;
