@@ -6,7 +6,7 @@ The reference crops its scenes into 256-pixel tiles offline (/root/reference/spl
 The scene is synthetic (stcd_amd.synth); with ``--load_path`` the weights of a trained ``SiamUnet_diff`` are used, otherwise the
 scores are those of a randomly initialised network and only show the plumbing.
 
-    python examples/predict_scene_synth.py --size 1024 --tile 256 --stride 128 --window hann
+    python examples/predict_scene_synth.py --size 1024 --tile 256 --stride 128 --window hann --tta d4
 """
 import argparse
 import os
@@ -27,6 +27,8 @@ parser.add_argument("--tile", type=int, default=256)
 parser.add_argument("--stride", type=int, default=128, help="<= tile; tile = no overlap")
 parser.add_argument("--batch", type=int, default=16)
 parser.add_argument("--window", type=str, default="hann", choices=("flat", "hann"))
+parser.add_argument("--tta", type=str, default="none", choices=("none", "flip", "d4"),
+                    help="test-time augmentation: average the 4 mirror views or all 8 symmetries of the square")
 parser.add_argument("--load_path", type=str, default="", help="state_dict of a trained SiamUnet_diff(3, 2)")
 parser.add_argument("--seed", type=int, default=7)
 
@@ -47,11 +49,11 @@ def main(argv=None):
     plan = plan_tiles(args.size, args.size, args.tile, args.stride)
     t0 = time.perf_counter()
     res = predict_scene(model, scene_a, scene_b, tile=args.tile, stride=args.stride, batch=args.batch, window=args.window,
-                        label=label, return_prob=True)
+                        label=label, return_prob=True, tta=None if args.tta == "none" else args.tta)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     s = res.scores
-    print(f"{args.size} x {args.size} scene, {plan.tiles_y} x {plan.tiles_x} tiles of {plan.tile} at stride {plan.stride} ({args.window}): "
+    print(f"{args.size} x {args.size} scene, {plan.tiles_y} x {plan.tiles_x} tiles of {plan.tile} at stride {plan.stride} ({args.window}, tta {args.tta}): "
           f"{dt * 1e3:.1f} ms including the first-call set-up")
     print(f"change pixels predicted {int(res.mask.sum())} / labelled {int((label >= 1).sum())}; mean change probability {float(res.prob.mean()):.4f}")
     print(f"confusion matrix [label, pred]: {res.cm.tolist()}")

@@ -378,6 +378,25 @@ int stcd_scene_stitch(const float* logits, int classes, int height, int width, i
  * device, cm[2*label+pred] += count as stcd_confusion_update does; both or neither. */
 int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold,
                         const uint8_t* label, uint8_t* mask, float* prob, int64_t* cm, void* hip_stream);
+/* Test-time augmentation over the eight symmetries of the square, without a host permutation of tiles or logits.
+ * d4 in 0..7: bit 0 mirrors columns, bit 1 mirrors rows, bit 2 transposes, the transpose applied last.  For an upright tile
+ * X[c,p,q] the view is Xd[c,i,j] = X[c,p,q] with (a,b) = (d4 & 4) ? (j,i) : (i,j), p = (d4 & 2) ? T-1-a : a,
+ * q = (d4 & 1) ? T-1-b : b.  Any other d4 is an error reported before any HIP call; d4 == 0 gives the bits of the entries above.
+ * The other arguments and their checks are those of stcd_scene_gather / stcd_scene_stitch.
+ * gather_d4: x1, x2 = view d4 of the tiles stcd_scene_gather writes, bit-equal to that entry followed by the index permutation
+ * (reflection past the edges and the value arithmetic are unchanged).
+ * stitch_d4: logits are the network's outputs FOR view d4 of the tiles; the logit of the upright tile pixel (p,q) is read at
+ * Ld[c,i,j] with a = (d4 & 2) ? T-1-p : p, b = (d4 & 1) ? T-1-q : q, (i,j) = (d4 & 4) ? (b,a) : (a,b).  The weight is
+ * window[p] * window[q] in upright coordinates, and tile order and the chain acc = fmaf(w, logit, acc), wsum += w are those of
+ * stcd_scene_stitch: the result is bit-equal to un-transforming the logits and calling that entry.  Views and models are
+ * therefore further links of one chain: stitch every view of every model into the same acc / wsum (each view's tiles in
+ * ascending order) and stcd_scene_finalize blends the wsum-weighted mean; the bits depend on the order of views and models
+ * but not on how a view's tiles were split into calls.  No float atomics. */
+int stcd_scene_gather_d4(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                         int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, int d4,
+                         void* hip_stream);
+int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                         int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, void* hip_stream);
 
 /* ---- the self-training round: K checkpoints of one network score the same pairs.  Replaces, per pair and checkpoint, the sigmoid,
  *      the compare, the .int(), the .cpu() and the host bincount of train_stcd.py:111-125 (reliability split) and :155-177

@@ -614,6 +614,23 @@ void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, 
                          const float* window, float* acc, float* wsum, hipStream_t s);
 void launch_scene_finalize(const float* acc, const float* wsum, int classes, int H, int W, float threshold, const uint8_t* label,
                            uint8_t* mask, float* prob, int64_t* cm, hipStream_t s);
+// the D4 views of the two (d4 in 0..7: bit 0 mirrors columns, bit 1 rows, bit 2 transposes, last); d4 == 0 is the launch above
+void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                            const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s);
+void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
+                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s);
+// the tile-grid checks shared by every stcd_scene_* entry (engine.hip, ops_abi.hip); tiles per axis: max(0, ceil((L - T) / S)) + 1
+inline int scene_tiles(int L, int T, int S) { return (L > T ? (int)(((int64_t)L - T + S - 1) / S) : 0) + 1; }
+inline int check_scene_grid(int height, int width, int tile, int stride, int tiles_x, int tiles_y, int first_tile, int n_tiles) {
+    STCD_CHECK(height >= 1 && width >= 1 && tile >= 1, "bad shape");
+    STCD_CHECK(stride >= 1 && stride <= tile, "stride must be in [1, tile]");
+    STCD_CHECK(tiles_x == scene_tiles(width, tile, stride), "tiles_x is not max(0, ceil((width - tile) / stride)) + 1");
+    STCD_CHECK(tiles_y == scene_tiles(height, tile, stride), "tiles_y is not max(0, ceil((height - tile) / stride)) + 1");
+    STCD_CHECK((int64_t)tiles_x * tiles_y < ((int64_t)1 << 31), "more than 2^31 tiles");
+    STCD_CHECK(first_tile >= 0 && n_tiles >= 0 && (int64_t)first_tile + n_tiles <= (int64_t)tiles_x * tiles_y,
+               "tile range outside [0, tiles_x * tiles_y)");
+    return 0;
+}
 // the self-training round (kernels_selftrain.hip): the caller has validated every argument; the device pointers of the checkpoints'
 // logits travel by value as a kernel argument
 struct SelftrainPtrs { const float* p[STCD_SELFTRAIN_MAX_MODELS]; };

@@ -3545,18 +3545,6 @@ int stcd_augment(const float* x, const float* params, int n_images, int height, 
     return 0;
 }
 
-// tiles per axis of the regular grid: max(0, ceil((L - T) / S)) + 1
-static int scene_tiles(int L, int T, int S) { return (L > T ? (int)(((int64_t)L - T + S - 1) / S) : 0) + 1; }
-static int check_scene_grid(int height, int width, int tile, int stride, int tiles_x, int tiles_y, int first_tile, int n_tiles) {
-    STCD_CHECK(height >= 1 && width >= 1 && tile >= 1, "bad shape");
-    STCD_CHECK(stride >= 1 && stride <= tile, "stride must be in [1, tile]");
-    STCD_CHECK(tiles_x == scene_tiles(width, tile, stride), "tiles_x is not max(0, ceil((width - tile) / stride)) + 1");
-    STCD_CHECK(tiles_y == scene_tiles(height, tile, stride), "tiles_y is not max(0, ceil((height - tile) / stride)) + 1");
-    STCD_CHECK((int64_t)tiles_x * tiles_y < ((int64_t)1 << 31), "more than 2^31 tiles");
-    STCD_CHECK(first_tile >= 0 && n_tiles >= 0 && (int64_t)first_tile + n_tiles <= (int64_t)tiles_x * tiles_y,
-               "tile range outside [0, tiles_x * tiles_y)");
-    return 0;
-}
 int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
                       int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, void* hip_stream) {
     STCD_CHECK(scene_a && scene_b && mean3 && std3 && x1 && x2, "null pointer argument");

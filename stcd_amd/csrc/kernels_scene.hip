@@ -13,6 +13,14 @@
 // 16-byte loads and stores whenever the row pitch allows it, pixel indices are 64-bit.  The stitch is a GATHER over scene
 // pixels: a thread adds the tiles that cover its pixels in ascending tile index, so there are no float atomics, the bits
 // do not depend on the run, and splitting the tiles into calls (in ascending order) continues the same chain of fmaf.
+//
+// The D4 views (stcd_scene_gather_d4 / stcd_scene_stitch_d4; d4 bit 0 mirrors columns, bit 1 mirrors rows, bit 2 transposes, the
+// transpose last): the gather writes view d4 of each tile, the stitch reads logits that are in view d4 through the inverse, and
+// weights, tile order and the fmaf chain stay in upright coordinates, so more views are more links in the same chain.  The mirror
+// views (1..3) are the upright kernels with the 4-pixel group reversed in registers (template MIR; MIR == 0 is the upright code).
+// The transposing views (4..7) go through LDS so that both global sides run along their own fast axis: k_scene_gather_t stages a
+// 64 x 64 patch of scene rows and writes tile rows whose fast axis is the scene's y; k_scene_stitch_t owns a 64 x 64 scene patch
+// and, per covering tile, stages the logit sub-block with lanes along the logits' fast axis and reads it back transposed.
 #include <algorithm>
 
 #include "common.h"
@@ -46,7 +54,8 @@ __device__ __forceinline__ void scene_load12(const uint8_t* __restrict__ p, floa
     }
 }
 
-template <bool VEC>
+// MIR: bit 0 mirrors the tile's columns, bit 1 its rows (d4 in 0..3); the values are those of MIR == 0, only the address moves
+template <bool VEC, int MIR>
 __global__ void __launch_bounds__(256)
 k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int H, int W, int T, int S, int tiles_x, int first_tile,
                int gpr, int64_t total, float m0, float m1, float m2, float is0, float is1, float is2, float* __restrict__ x1,
@@ -83,13 +92,109 @@ k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int
                 va[j] = (ua[3 * j + c] * (1.f / 255.f) - mean[c]) * istd[c];
                 vb[j] = (ub[3 * j + c] * (1.f / 255.f) - mean[c]) * istd[c];
             }
-            const int64_t o = ((n * 3 + c) * T + ty) * T + tx0;
-            if (VEC) {
-                *reinterpret_cast<float4*>(x1 + o) = make_float4(va[0], va[1], va[2], va[3]);
-                *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+            if (MIR == 0) {
+                const int64_t o = ((n * 3 + c) * T + ty) * T + tx0;
+                if (VEC) {
+                    *reinterpret_cast<float4*>(x1 + o) = make_float4(va[0], va[1], va[2], va[3]);
+                    *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                } else {
+                    for (int j = 0; j < 4; ++j)
+                        if (tx0 + j < T) { x1[o + j] = va[j]; x2[o + j] = vb[j]; }
+                }
             } else {
-                for (int j = 0; j < 4; ++j)
-                    if (tx0 + j < T) { x1[o + j] = va[j]; x2[o + j] = vb[j]; }
+                const int64_t o = ((n * 3 + c) * T + ((MIR & 2) ? T - 1 - ty : ty)) * T;
+                if (VEC && (MIR & 1)) {                               // T % 4 == 0: the mirrored group starts at a multiple of 4
+                    *reinterpret_cast<float4*>(x1 + o + (T - 4 - tx0)) = make_float4(va[3], va[2], va[1], va[0]);
+                    *reinterpret_cast<float4*>(x2 + o + (T - 4 - tx0)) = make_float4(vb[3], vb[2], vb[1], vb[0]);
+                } else if (VEC) {
+                    *reinterpret_cast<float4*>(x1 + o + tx0) = make_float4(va[0], va[1], va[2], va[3]);
+                    *reinterpret_cast<float4*>(x2 + o + tx0) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                } else {
+                    for (int j = 0; j < 4; ++j)
+                        if (tx0 + j < T) {
+                            const int ox = (MIR & 1) ? T - 1 - tx0 - j : tx0 + j;
+                            x1[o + ox] = va[j]; x2[o + ox] = vb[j];
+                        }
+                }
+            }
+        }
+    }
+}
+
+// ---- transposing views of the gather (d4 & 4): Xd[c,i,j] = X[c,p,q] with p = (d4 & 2) ? T-1-j : j, q = (d4 & 1) ? T-1-i : i.
+// A block owns the upright patch [p0, p0 + 64) x [q0, q0 + 64) of one tile.  Staging: a thread reads 4 consecutive scene pixels
+// of one row (scene_load12's three dwords when the address allows it) and keeps them as bytes, rows of 64 * 3 bytes at a pitch of
+// 49 dwords.  Writing: 16 lanes cover 64 consecutive j of one output row i (256 contiguous bytes), each lane converting the four
+// bytes of its four p with the upright kernel's arithmetic.
+#define SCENE_PATCH 64
+#define SCENE_GPITCH 49            // dwords per staged row: 48 hold the 192 bytes, + 1 makes the pitch odd
+
+// the 12 bytes of 4 consecutive tile pixels starting at scene column gx0 (reflected past the right edge) as three little-endian dwords
+__device__ __forceinline__ void scene_load12_raw(const uint8_t* __restrict__ row, int64_t gx0, int W, uint32_t* __restrict__ w) {
+    const uint8_t* p = row + gx0 * 3;
+    if (gx0 + 3 < W && ((uintptr_t)p & 3) == 0) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        w[0] = q[0]; w[1] = q[1]; w[2] = q[2];
+        return;
+    }
+    uint32_t v[3] = {0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t x = gx0 + 3 < W ? gx0 + j : scene_reflect(gx0 + j, W);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[(3 * j + c) >> 2] |= (uint32_t)row[x * 3 + c] << (8 * ((3 * j + c) & 3));
+    }
+    w[0] = v[0]; w[1] = v[1]; w[2] = v[2];
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(256)
+k_scene_gather_t(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int H, int W, int T, int S, int tiles_x, int first_tile,
+                 int ppa, int64_t n_patches, int d4, float m0, float m1, float m2, float is0, float is1, float is2, float* __restrict__ x1,
+                 float* __restrict__ x2) {
+    __shared__ uint32_t lds[2][SCENE_PATCH][SCENE_GPITCH];
+    const float mean[3] = {m0, m1, m2}, istd[3] = {is0, is1, is2};
+    const int t4 = (threadIdx.x & 15) * 4, tr = threadIdx.x >> 4;
+    for (int64_t blk = blockIdx.x; blk < n_patches; blk += gridDim.x) {   // uniform per block: the barriers are safe
+        const int q0 = (int)(blk % ppa) * SCENE_PATCH;
+        const int64_t r = blk / ppa;
+        const int p0 = (int)(r % ppa) * SCENE_PATCH;
+        const int64_t n = r / ppa;
+        const int64_t k = first_tile + n;
+        const int64_t ky = k / tiles_x, kx = k - ky * tiles_x;
+        const int pn = min(SCENE_PATCH, T - p0), qn = min(SCENE_PATCH, T - q0);
+        __syncthreads();                                              // the previous patch has been read
+        if (t4 < qn)
+            for (int pl = tr; pl < pn; pl += 16) {
+                const int64_t y = scene_reflect(ky * S + p0 + pl, H), gx0 = kx * S + q0 + t4;
+                scene_load12_raw(A + y * W * 3, gx0, W, &lds[0][pl][3 * (t4 >> 2)]);
+                scene_load12_raw(B + y * W * 3, gx0, W, &lds[1][pl][3 * (t4 >> 2)]);
+            }
+        __syncthreads();
+        if (t4 >= pn) continue;                                       // no barrier below
+        const int jb = (d4 & 2) ? T - p0 - pn : p0, ib = (d4 & 1) ? T - q0 - qn : q0;   // where the patch lands in the view
+        for (int il = tr; il < qn; il += 16) {
+            const int ql = (d4 & 1) ? qn - 1 - il : il;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float va[4], vb[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int pl = min(t4 + j, pn - 1);               // past the patch (T % 4 != 0): computed, not stored
+                    const int ps = (d4 & 2) ? pn - 1 - pl : pl;
+                    const float ua = (float)reinterpret_cast<const uint8_t*>(&lds[0][ps][0])[ql * 3 + c];
+                    const float ub = (float)reinterpret_cast<const uint8_t*>(&lds[1][ps][0])[ql * 3 + c];
+                    va[j] = (ua * (1.f / 255.f) - mean[c]) * istd[c];  // k_scene_gather's arithmetic, to the operation
+                    vb[j] = (ub * (1.f / 255.f) - mean[c]) * istd[c];
+                }
+                const int64_t o = ((n * 3 + c) * T + ib + il) * T + jb + t4;
+                if (VEC) {                                            // T % 4 == 0: pn and jb are multiples of 4
+                    *reinterpret_cast<float4*>(x1 + o) = make_float4(va[0], va[1], va[2], va[3]);
+                    *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                } else {
+                    for (int j = 0; j < 4; ++j)
+                        if (t4 + j < pn) { x1[o + j] = va[j]; x2[o + j] = vb[j]; }
+                }
             }
         }
     }
@@ -98,25 +203,55 @@ k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int
 static inline unsigned scene_blocks(int64_t threads) { return (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, (threads + 255) / 256); }
 static inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
-                         const float* mean, const float* std_, float* x1, float* x2, hipStream_t s) {
+template <int MIR>
+static void scene_gather_rows(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                              const float* mean, const float* std_, float* x1, float* x2, hipStream_t s) {
     const int gpr = (T + 3) / 4;
     const int64_t total = (int64_t)n_tiles * T * gpr;
-    if (total == 0) return;
     const float is0 = 1.f / std_[0], is1 = 1.f / std_[1], is2 = 1.f / std_[2];
     if (T % 4 == 0 && aligned_to(x1, 16) && aligned_to(x2, 16))
-        k_scene_gather<true><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1], mean[2],
-                                                                 is0, is1, is2, x1, x2);
+        k_scene_gather<true, MIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1],
+                                                                      mean[2], is0, is1, is2, x1, x2);
     else
-        k_scene_gather<false><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1], mean[2],
-                                                                  is0, is1, is2, x1, x2);
+        k_scene_gather<false, MIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1],
+                                                                       mean[2], is0, is1, is2, x1, x2);
+}
+
+void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                            const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s) {
+    if (n_tiles == 0) return;
+    if (d4 & 4) {
+        const int ppa = (T + SCENE_PATCH - 1) / SCENE_PATCH;
+        const int64_t n_patches = (int64_t)n_tiles * ppa * ppa;
+        const unsigned blocks = (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, n_patches);
+        const float is0 = 1.f / std_[0], is1 = 1.f / std_[1], is2 = 1.f / std_[2];
+        if (T % 4 == 0 && aligned_to(x1, 16) && aligned_to(x2, 16))
+            k_scene_gather_t<true><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1], mean[2],
+                                                         is0, is1, is2, x1, x2);
+        else
+            k_scene_gather_t<false><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1], mean[2],
+                                                          is0, is1, is2, x1, x2);
+        return;
+    }
+    switch (d4) {
+        case 0: scene_gather_rows<0>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        case 1: scene_gather_rows<1>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        case 2: scene_gather_rows<2>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        default: scene_gather_rows<3>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+    }
+}
+
+void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                         const float* mean, const float* std_, float* x1, float* x2, hipStream_t s) {
+    launch_scene_gather_d4(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, 0, s);
 }
 
 // ------------------------------------------------------------------ stitch: acc += w * logit, wsum += w, per scene pixel
 // The launch covers the rectangle [y0, y0 + rows) x [x0, x0 + 4 * gpr) of the scene that this call's tiles can reach (x0 a
 // multiple of 4).  Tiles covering row y: ky * S <= y < ky * S + T, i.e. ky in [y < T ? 0 : (y - T) / S + 1, min(y / S, tiles_y - 1)];
 // likewise along x.  A thread walks ky then kx upwards, which is ascending tile index for each of its four pixels.
-template <int CLS>
+// MIR as in k_scene_gather: the logits are in view MIR of the tile, weights and order stay upright
+template <int CLS, int MIR>
 __global__ void __launch_bounds__(256)
 k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
                const float* __restrict__ window, float* __restrict__ acc, float* __restrict__ wsum, int y0, int x0, int gpr, int64_t total,
@@ -159,7 +294,7 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
                     }
                 }
                 const int tx0 = xs - kx * S;
-                const float* lp = logits + (k * CLS * T + ty) * T;    // class 0 row of this tile; class c is c * T * T further
+                const float* lp = logits + (k * CLS * T + ((MIR & 2) ? T - 1 - ty : ty)) * T;   // class 0 row of this tile; class c is c * T * T further
                 if (vec_l && tx0 >= 0 && tx0 + 3 < T) {               // xs, S and T are multiples of 4 here, so tx0 is one too
                     float wx[4] = {1.f, 1.f, 1.f, 1.f};
                     if (window) {
@@ -169,8 +304,9 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
                     float l[CLS][4];
 #pragma unroll
                     for (int c = 0; c < CLS; ++c) {
-                        const float4 l4 = *reinterpret_cast<const float4*>(lp + (int64_t)c * T * T + tx0);
-                        l[c][0] = l4.x; l[c][1] = l4.y; l[c][2] = l4.z; l[c][3] = l4.w;
+                        const float4 l4 = *reinterpret_cast<const float4*>(lp + (int64_t)c * T * T + ((MIR & 1) ? T - 4 - tx0 : tx0));
+                        if (MIR & 1) { l[c][0] = l4.w; l[c][1] = l4.z; l[c][2] = l4.y; l[c][3] = l4.x; }
+                        else { l[c][0] = l4.x; l[c][1] = l4.y; l[c][2] = l4.z; l[c][3] = l4.w; }
                     }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -186,7 +322,7 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
                         if (tx < 0 || tx >= T || xs + j >= W) continue;
                         const float w = wy * (window ? window[tx] : 1.f);
 #pragma unroll
-                        for (int c = 0; c < CLS; ++c) a[c][j] = fmaf(w, lp[(int64_t)c * T * T + tx], a[c][j]);
+                        for (int c = 0; c < CLS; ++c) a[c][j] = fmaf(w, lp[(int64_t)c * T * T + ((MIR & 1) ? T - 1 - tx : tx)], a[c][j]);
                         ws[j] += w;
                     }
                 }
@@ -209,8 +345,125 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
     }
 }
 
-void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
-                         const float* window, float* acc, float* wsum, hipStream_t s) {
+// ---- transposing views of the stitch (d4 & 4): the logit of the upright tile pixel (ty, tx) is Ld[c, i, j] with
+// i = (d4 & 1) ? T-1-tx : tx and j = (d4 & 2) ? T-1-ty : ty, so the logits' fast axis runs along the scene's y.  A block owns a
+// 64 x 64 scene patch, a thread 4 rows of 4 consecutive x (16 register chains per class).  The tile loop runs over the union of
+// the patch's covering ranges and is uniform per block; a pixel joins a tile by the predicate that defines its own covering range,
+// so every pixel sees its tiles in ascending index exactly as in k_scene_stitch.  Per tile: a wave stages 64 consecutive j of one
+// logit row (256 contiguous bytes) into lds[c][x][y], rows of 65 dwords, and after the barrier a thread reads lds[c][x][y] for its
+// pixels: 16 lanes 4 rows of 65 apart and 4 neighbouring y, two lanes per bank, which is the floor for 64 lanes.
+#define SCENE_SPITCH (SCENE_PATCH + 1)
+template <int CLS>
+__global__ void __launch_bounds__(256)
+k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
+                 const float* __restrict__ window, float* __restrict__ acc, float* __restrict__ wsum, int y0, int x0, int pcols,
+                 int64_t n_patches, int d4, int vec_a) {
+    __shared__ float lds[CLS][SCENE_PATCH][SCENE_SPITCH];
+    const int64_t HW = (int64_t)H * W;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t4 = (threadIdx.x & 15) * 4, tr = threadIdx.x >> 4;
+    for (int64_t blk = blockIdx.x; blk < n_patches; blk += gridDim.x) {   // uniform per block, and so is everything around a barrier
+        const int py = y0 + (int)(blk / pcols) * SCENE_PATCH, px = x0 + (int)(blk % pcols) * SCENE_PATCH;
+        const int ye = min(py + SCENE_PATCH - 1, H - 1), xe = min(px + SCENE_PATCH - 1, W - 1);
+        const int ky_lo = py < T ? 0 : (py - T) / S + 1, ky_hi = min(ye / S, tiles_y - 1);
+        const int kx_lo = px < T ? 0 : (px - T) / S + 1, kx_hi = min(xe / S, tiles_x - 1);
+        const int xs = px + t4;
+        float a[CLS][4][4], ws[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {                                 // the chain continues from what earlier calls left
+            const int y = py + tr + 16 * r;
+            const int64_t pix = (int64_t)y * W + xs;
+            if (vec_a && y < H && xs < W) {
+                const float4 w4 = *reinterpret_cast<const float4*>(wsum + pix);
+                ws[r][0] = w4.x; ws[r][1] = w4.y; ws[r][2] = w4.z; ws[r][3] = w4.w;
+#pragma unroll
+                for (int c = 0; c < CLS; ++c) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(acc + c * HW + pix);
+                    a[c][r][0] = a4.x; a[c][r][1] = a4.y; a[c][r][2] = a4.z; a[c][r][3] = a4.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool ok = y < H && xs + j < W;
+                    ws[r][j] = ok ? wsum[pix + j] : 0.f;
+#pragma unroll
+                    for (int c = 0; c < CLS; ++c) a[c][r][j] = ok ? acc[c * HW + pix + j] : 0.f;
+                }
+            }
+        }
+        bool touched = false;
+        for (int ky = ky_lo; ky <= ky_hi; ++ky)
+            for (int kx = kx_lo; kx <= kx_hi; ++kx) {
+                const int64_t k = (int64_t)ky * tiles_x + kx - first_tile;
+                if (k < 0 || k >= n_tiles) continue;                  // another call's tile (uniform)
+                const int ty0 = py - ky * S, tx0 = px - kx * S;       // tile coordinates of the patch origin: may be negative
+                __syncthreads();                                      // the previous tile has been read
+                {
+                    const int ty = ty0 + lane;
+                    if (ty >= 0 && ty < T) {
+                        const int j = (d4 & 2) ? T - 1 - ty : ty;
+                        for (int xl = wv; xl < SCENE_PATCH; xl += 4) {
+                            const int tx = tx0 + xl;
+                            if (tx < 0 || tx >= T) continue;
+                            const int i = (d4 & 1) ? T - 1 - tx : tx;
+                            const float* lp = logits + ((k * CLS * T + i) * T + j);
+#pragma unroll
+                            for (int c = 0; c < CLS; ++c) lds[c][xl][lane] = lp[(int64_t)c * T * T];
+                        }
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int yl = tr + 16 * r, ty = ty0 + yl;
+                    if (py + yl >= H || ty < 0 || ty >= T) continue;
+                    const float wy = window ? window[ty] : 1.f;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int tx = tx0 + t4 + j;
+                        if (tx < 0 || tx >= T || xs + j >= W) continue;
+                        const float w = wy * (window ? window[tx] : 1.f);
+#pragma unroll
+                        for (int c = 0; c < CLS; ++c) a[c][r][j] = fmaf(w, lds[c][t4 + j][yl], a[c][r][j]);
+                        ws[r][j] += w;
+                        touched = true;
+                    }
+                }
+            }
+        if (!touched) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int y = py + tr + 16 * r;
+            const int64_t pix = (int64_t)y * W + xs;
+            if (y >= H || xs >= W) continue;
+            if (vec_a) {
+                *reinterpret_cast<float4*>(wsum + pix) = make_float4(ws[r][0], ws[r][1], ws[r][2], ws[r][3]);
+#pragma unroll
+                for (int c = 0; c < CLS; ++c)
+                    *reinterpret_cast<float4*>(acc + c * HW + pix) = make_float4(a[c][r][0], a[c][r][1], a[c][r][2], a[c][r][3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (xs + j >= W) continue;
+                    wsum[pix + j] = ws[r][j];
+#pragma unroll
+                    for (int c = 0; c < CLS; ++c) acc[c * HW + pix + j] = a[c][r][j];
+                }
+            }
+        }
+    }
+}
+
+template <int CLS, int MIR>
+static void scene_stitch_rows(const float* logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
+                              const float* window, float* acc, float* wsum, int y0, int x0, int gpr, int64_t total, int vec_l, int vec_a,
+                              hipStream_t s) {
+    k_scene_stitch<CLS, MIR><<<scene_blocks(total), 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
+                                                                 y0, x0, gpr, total, vec_l, vec_a);
+}
+
+void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
+                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s) {
     if (n_tiles == 0) return;
     const int last = first_tile + n_tiles - 1;
     const int ky0 = first_tile / tiles_x, ky1 = last / tiles_x;
@@ -220,17 +473,41 @@ void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, 
         x0 = ((first_tile % tiles_x) * S) & ~3;
         x1 = (int)std::min<int64_t>(W, (int64_t)(last % tiles_x) * S + T);
     }
+    if (y1 <= y0 || x1 <= x0) return;
+    const int vec_a = W % 4 == 0 && aligned_to(acc, 16) && aligned_to(wsum, 16);
+    if (d4 & 4) {
+        const int pcols = (x1 - x0 + SCENE_PATCH - 1) / SCENE_PATCH;
+        const int64_t n_patches = (int64_t)((y1 - y0 + SCENE_PATCH - 1) / SCENE_PATCH) * pcols;
+        const unsigned blocks = (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, n_patches);
+        if (classes == 2)
+            k_scene_stitch_t<2><<<blocks, 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, pcols,
+                                                      n_patches, d4, vec_a);
+        else
+            k_scene_stitch_t<1><<<blocks, 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, pcols,
+                                                      n_patches, d4, vec_a);
+        return;
+    }
     const int gpr = (x1 - x0 + 3) / 4;
     const int64_t total = (int64_t)(y1 - y0) * gpr;
-    if (total <= 0) return;
     const int vec_l = T % 4 == 0 && S % 4 == 0 && aligned_to(logits, 16) && (!window || aligned_to(window, 16));
-    const int vec_a = W % 4 == 0 && aligned_to(acc, 16) && aligned_to(wsum, 16);
-    if (classes == 2)
-        k_scene_stitch<2><<<scene_blocks(total), 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0,
-                                                              gpr, total, vec_l, vec_a);
-    else
-        k_scene_stitch<1><<<scene_blocks(total), 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0,
-                                                              gpr, total, vec_l, vec_a);
+#define STCD_STITCH_ROWS(CLS, MIR) \
+    scene_stitch_rows<CLS, MIR>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, gpr, total, vec_l, vec_a, s)
+    switch (2 * d4 + (classes == 2)) {
+        case 0: STCD_STITCH_ROWS(1, 0); break;
+        case 1: STCD_STITCH_ROWS(2, 0); break;
+        case 2: STCD_STITCH_ROWS(1, 1); break;
+        case 3: STCD_STITCH_ROWS(2, 1); break;
+        case 4: STCD_STITCH_ROWS(1, 2); break;
+        case 5: STCD_STITCH_ROWS(2, 2); break;
+        case 6: STCD_STITCH_ROWS(1, 3); break;
+        default: STCD_STITCH_ROWS(2, 3); break;
+    }
+#undef STCD_STITCH_ROWS
+}
+
+void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
+                         const float* window, float* acc, float* wsum, hipStream_t s) {
+    launch_scene_stitch_d4(logits, classes, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, 0, s);
 }
 
 // ------------------------------------------------------------------ finalize: mask, optional probability, optional confusion matrix

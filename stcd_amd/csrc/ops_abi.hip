@@ -231,4 +231,31 @@ int stcd_op_skip_bwd(int dtype, int mode, const stcd_map_geom* g, const void* a,
     return 0;
 }
 
+// ---- the D4 views of the whole-scene gather and stitch (kernels_scene.hip): test-time augmentation without a host permutation.
+//      d4 is checked first; the other checks are those of stcd_scene_gather / stcd_scene_stitch (engine.hip).
+int stcd_scene_gather_d4(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                         int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, int d4,
+                         void* hip_stream) {
+    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK(scene_a && scene_b && mean3 && std3 && x1 && x2, "null pointer argument");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
+        return 1;
+    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
+    launch_scene_gather_d4(scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2, d4,
+                           (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                         int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, void* hip_stream) {
+    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK(logits && acc && wsum, "null pointer argument");
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
+    launch_scene_stitch_d4(logits, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, d4,
+                           (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"
