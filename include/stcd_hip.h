@@ -418,6 +418,31 @@ int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width
 int stcd_selftrain_score(const float* const* logits, int n_models, int batch, int classes, int64_t hw, float threshold,
                          const uint8_t* label, int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, void* hip_stream);
 
+/* ---- the self-training round on whole scenes: the stitched masks of K checkpoints (stcd_scene_finalize) become a reliability
+ *      grid and a cleaned pseudo-label without leaving the device.  All outputs are integers or bytes: pure functions of the
+ *      inputs, no float arithmetic, no float atomics, 64-bit indices inside (height * width may pass 2^31).  Arguments are
+ *      checked before any HIP call. */
+/* Replaces metric.addBatch(preds[i], preds[-1]) per pre-cut crop and checkpoint, train_stcd.py:118-125, by one launch over the
+ * scene.  masks: HOST array of n_models device pointers (1 <= n_models <= STCD_SELFTRAIN_MAX_MODELS, taken by value), each uint8
+ * [height,width]; any non-zero byte is change; the LAST mask plays the label (preds[-1], :119-122).
+ * Cells: cell >= 1, cells_x == ceil(width / cell), cells_y == ceil(height / cell) (anything else is an error); non-overlapping
+ * cell x cell squares, c = cy * cells_x + cx; edge cells are cut off at the scene border and counted over their real pixels.
+ * agree: int64 [cells][n_models-1][4] on the device, agree[c][i][2*last + pred_i] += count over the pixels of cell c; NULL iff
+ * n_models == 1.  label / cm: both or neither; label uint8 [height,width] (>= 1 is change, 255 is ignored), cm int64 [cells][4],
+ * cm[c][2*label + pred_last] += count.  n_models == 1 without a label computes nothing: an error.  Counts are ADDED to what the
+ * buffers hold, reduced per wave and block before one 64-bit integer atomic per block and counter.  16-byte loads when
+ * width % 16 == 0, cell % 16 == 0 and every pointer is 16-byte aligned, a scalar path otherwise.  height == 0 or width == 0
+ * launches nothing. */
+int stcd_scene_cell_agree(const uint8_t* const* masks, int n_models, int height, int width, int cell, int cells_x, int cells_y,
+                          const uint8_t* label, int64_t* agree, int64_t* cm, void* hip_stream);
+/* Binary morphological closing with the (2*radius+1)^2 square, dilation then erosion: at radius 2 the
+ * cv2.morphologyEx(img, cv2.MORPH_CLOSE, np.ones((5, 5))) of train_stcd.py:186-188.  in: uint8 [height,width], any non-zero byte
+ * is set; out: uint8 [height,width], mask_value (1..255) where set, else 0; radius in 1..4.  out must not overlap in.
+ * Border rule (OpenCV's default): a pixel outside the scene never contributes -- the dilation reads it as unset, the erosion
+ * reads every position outside the scene as set.  One launch: a block stages a 64 x 256 window as bits, runs the four separable
+ * passes in LDS and writes its 48 x 240 tile; no alignment is required of in, out or width. */
+int stcd_mask_close(const uint8_t* in, int height, int width, int radius, int mask_value, uint8_t* out, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

@@ -144,6 +144,8 @@ _PROTOS = {
     "stcd_scene_gather_d4": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _i, _vp]),
     "stcd_scene_stitch_d4": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "stcd_selftrain_score": (_i, [C.POINTER(_vp), _i, _i, _i, _i64, _f, _vp, _i, _vp, _vp, _vp, _vp]),
+    "stcd_scene_cell_agree": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "stcd_mask_close": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_scratch_bytes": (_i64, [C.POINTER(ConvGeom)]),

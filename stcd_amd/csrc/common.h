@@ -636,6 +636,12 @@ inline int check_scene_grid(int height, int width, int tile, int stride, int til
 struct SelftrainPtrs { const float* p[STCD_SELFTRAIN_MAX_MODELS]; };
 void launch_selftrain_score(const SelftrainPtrs& lg, int n_models, int batch, int classes, int64_t hw, float threshold, const uint8_t* label,
                             int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, hipStream_t s);
+// the round on whole scenes (kernels_scene_round.hip): the caller has validated every argument; the masks' device pointers travel by value
+struct SceneMaskPtrs { const uint8_t* p[STCD_SELFTRAIN_MAX_MODELS]; };
+void launch_scene_cell_agree(const SceneMaskPtrs& mk, int n_models, int height, int width, int cell, int cells_x, int cells_y,
+                             const uint8_t* label, int64_t* agree, int64_t* cm, hipStream_t s);
+int64_t mask_close_tiles(int height, int width);                      // blocks of one stcd_mask_close launch
+void launch_mask_close(const uint8_t* in, int height, int width, int radius, int mask_value, uint8_t* out, hipStream_t s);
 
 // ---- BIT token path (kernels_bit.hip): tokenizer, token encoder, folded cross-attention decoder.  NI = 2 * batch images (date-major),
 //      n = pixel rows per image, every map [NI, n, 32] with pixel stride 32; tokens, folded matrices and partial sums are fp32.

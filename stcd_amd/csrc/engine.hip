@@ -3597,6 +3597,42 @@ int stcd_selftrain_score(const float* const* logits, int n_models, int batch, in
     return 0;
 }
 
+int stcd_scene_cell_agree(const uint8_t* const* masks, int n_models, int height, int width, int cell, int cells_x, int cells_y,
+                          const uint8_t* label, int64_t* agree, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(masks != nullptr, "null pointer argument");
+    STCD_CHECK(n_models >= 1 && n_models <= STCD_SELFTRAIN_MAX_MODELS, "n_models must be in [1, 8]");
+    SceneMaskPtrs mk{};
+    for (int k = 0; k < n_models; ++k) {
+        STCD_CHECK(masks[k] != nullptr, "a mask pointer is null");
+        mk.p[k] = masks[k];
+    }
+    STCD_CHECK(height >= 0 && width >= 0, "bad shape");
+    STCD_CHECK(cell >= 1, "cell must be >= 1");
+    STCD_CHECK(cells_x == (int)(((int64_t)width + cell - 1) / cell), "cells_x is not ceil(width / cell)");
+    STCD_CHECK(cells_y == (int)(((int64_t)height + cell - 1) / cell), "cells_y is not ceil(height / cell)");
+    STCD_CHECK((agree == nullptr) == (n_models == 1), "agree is NULL if and only if n_models == 1");
+    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
+    STCD_CHECK(n_models > 1 || label != nullptr, "one model and no label: nothing to compute");
+    if (height == 0 || width == 0) return 0;
+    launch_scene_cell_agree(mk, n_models, height, width, cell, cells_x, cells_y, label, agree, cm, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
+int stcd_mask_close(const uint8_t* in, int height, int width, int radius, int mask_value, uint8_t* out, void* hip_stream) {
+    STCD_CHECK(in && out, "null pointer argument");
+    STCD_CHECK(height >= 0 && width >= 0, "bad shape");
+    STCD_CHECK(radius >= 1 && radius <= 4, "radius must be in [1, 4]");
+    STCD_CHECK(mask_value >= 1 && mask_value <= 255, "mask_value must be in [1, 255]");
+    const uint64_t bytes = (uint64_t)height * (uint64_t)width, a = (uint64_t)(uintptr_t)in, b = (uint64_t)(uintptr_t)out;
+    STCD_CHECK(a != b && (a < b ? b - a >= bytes : a - b >= bytes), "out must not overlap in (the passes read neighbours)");
+    STCD_CHECK(mask_close_tiles(height, width) < ((int64_t)1 << 31), "more than 2^31 tiles");
+    if (height == 0 || width == 0) return 0;
+    launch_mask_close(in, height, width, radius, mask_value, out, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
 static int check_geom(const stcd_conv_geom* g) {
     STCD_CHECK(g != nullptr, "geometry is null");
     STCD_CHECK(g->ntaps >= 1 && g->ntaps <= 9, "ntaps must be in [1,9]");

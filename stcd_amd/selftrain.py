@@ -9,7 +9,11 @@ sigmoid, a compare, an ``.int()``, a ``.cpu()`` and a host ``bincount``; here on
 (include/stcd_hip.h) takes the raw outputs of all checkpoints and leaves the mask and integer counts on the device, and the
 drivers copy back once per ``flush`` batches.
 
-``reliability``, ``split_reliable`` and ``write_lists`` are host-only and need no GPU.
+``scene_round`` is the same round over one pair of whole scenes instead of pre-cut crops: every checkpoint goes through
+``scene.predict_scene``, ``stcd_scene_cell_agree`` counts the agreement per cell of the scene, ``stcd_mask_close`` is the 5 x 5 closing of
+the pseudo-label (train_stcd.py:186-188), and ``export_cells`` writes the tile set and the two lists.
+
+``reliability``, ``split_reliable``, ``write_lists`` and ``cell_grid`` are host-only and need no GPU.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ import torch
 from . import _lib
 from ._lib import StcdError
 from .metrics import scores_from_cm
-from .scene import _change_logits
+from .scene import _change_logits, predict_scene
 
 MAX_MODELS = 8
 
@@ -312,3 +316,192 @@ def generate_pseudo_labels(model, batches: Iterable, out_dir: Optional[str], thr
     if cm is None:
         return None
     return scores_from_cm(cm.cpu().numpy().reshape(2, 2))
+
+
+# ------------------------------------------------------------------------------------------------ the round on whole scenes
+class SceneRound(NamedTuple):
+    masks: List[torch.Tensor]           # K uint8 [H,W] on the device: predict_scene's mask of every checkpoint, 1 is change
+    pseudo: torch.Tensor                # uint8 [H,W] on the device: the last checkpoint's mask, 0 / 255, closed if close_radius > 0
+    agree: Optional[np.ndarray]         # int64 [cells_y,cells_x,K-1,2,2], agree[cy, cx, i, last, pred_i]; None for one model
+    reliability: np.ndarray             # float64 [cells_y,cells_x]; all ones for one model
+    cell_cm: Optional[np.ndarray]       # int64 [cells_y,cells_x,2,2], cm[cy, cx, label, pseudo] (label given)
+    cm: Optional[np.ndarray]            # int64 [2,2]: the sum of cell_cm
+    scores: Optional[dict]              # metrics.scores_from_cm(cm)
+    names: List[str]                    # f"{stem}_{cy:04d}_{cx:04d}.png" of every cell, row-major
+    full: np.ndarray                    # bool [cells_y,cells_x]: the cell is a whole cell x cell square
+    reliable: List[str]                 # split_reliable over the full cells only
+    unreliable: List[str]
+    cell: int                           # the cell edge the grid was cut with
+
+
+def cell_grid(height: int, width: int, cell: int) -> Tuple[int, int]:
+    """``(cells_y, cells_x) = (ceil(height / cell), ceil(width / cell))``: non-overlapping squares, the last ones cut off at the border."""
+    height, width, cell = int(height), int(width), int(cell)
+    if height < 0 or width < 0 or cell < 1:
+        raise StcdError(f"cell_grid: bad sizes {height} x {width}, cell {cell}")
+    return -(-height // cell), -(-width // cell)
+
+
+def _check_mask(t, name: str, shape=None, dev=None) -> None:
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() != 2 or not t.is_cuda or not t.is_contiguous():
+        raise StcdError(f"{name} must be a contiguous uint8 [H,W] tensor on the GPU")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise StcdError(f"{name} is {tuple(t.shape)}, expected {tuple(shape)}")
+    if dev is not None and t.device != dev:
+        raise StcdError(f"{name} is on {t.device}, expected {dev}")
+
+
+def scene_cell_agree(masks: Sequence[torch.Tensor], cell: int, label: Optional[torch.Tensor] = None, agree: Optional[torch.Tensor] = None,
+                     cm: Optional[torch.Tensor] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """One ``stcd_scene_cell_agree`` launch over K (1..8) contiguous uint8 ``[H,W]`` masks on one GPU (non-zero is change; the last
+    plays the label): ``(agree, cm)`` on the device, ``agree`` int64 ``[cells_y,cells_x,K-1,2,2]`` (None for one mask) and, with a
+    ``label`` (uint8 ``[H,W]``, >= 1 is change, 255 is ignored), ``cm`` int64 ``[cells_y,cells_x,2,2]`` of the last mask.  Buffers
+    passed in are added to.  Nothing synchronises."""
+    masks = list(masks)
+    if not 1 <= len(masks) <= MAX_MODELS:
+        raise StcdError(f"between 1 and {MAX_MODELS} masks, got {len(masks)}")
+    _check_mask(masks[0], "masks[0]")
+    dev, (H, W) = masks[0].device, masks[0].shape
+    for k, m in enumerate(masks[1:], 1):
+        _check_mask(m, f"masks[{k}]", (H, W), dev)
+    cells_y, cells_x = cell_grid(H, W, cell)
+    K = len(masks)
+    if label is not None:
+        _check_mask(label, "label", (H, W), dev)
+    elif K == 1:
+        raise StcdError("one mask and no label: nothing to compute")
+    for name, buf, want, on in (("agree", agree, (cells_y, cells_x, K - 1, 2, 2), K > 1), ("cm", cm, (cells_y, cells_x, 2, 2), label is not None)):
+        if buf is None:
+            continue
+        if not on:
+            raise StcdError(f"{name} was passed but there is nothing to count into it")
+        if not torch.is_tensor(buf) or buf.dtype != torch.int64 or tuple(buf.shape) != want or buf.device != dev or not buf.is_contiguous():
+            raise StcdError(f"{name} must be a contiguous int64 {list(want)} tensor on {dev}")
+    with torch.cuda.device(dev):
+        if agree is None and K > 1:
+            agree = torch.zeros((cells_y, cells_x, K - 1, 2, 2), dtype=torch.int64, device=dev)
+        if cm is None and label is not None:
+            cm = torch.zeros((cells_y, cells_x, 2, 2), dtype=torch.int64, device=dev)
+        ptrs = (C.c_void_p * K)(*[m.data_ptr() for m in masks])
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(_lib.lib().stcd_scene_cell_agree(ptrs, K, int(H), int(W), int(cell), cells_x, cells_y, _ptr(label), _ptr(agree), _ptr(cm), stream))
+    return agree, cm
+
+
+def mask_close(mask: torch.Tensor, radius: int = 2, mask_value: int = 255) -> torch.Tensor:
+    """One ``stcd_mask_close`` launch: the binary closing of a contiguous uint8 ``[H,W]`` mask on the GPU (non-zero is set) with the
+    ``(2 * radius + 1)``-square, ``radius`` in 1..4, as a new tensor holding ``mask_value`` where set.  ``radius=2`` is the
+    reference's ``cv2.morphologyEx(img, cv2.MORPH_CLOSE, np.ones((5, 5)))`` (train_stcd.py:186-188)."""
+    _check_mask(mask, "mask")
+    if not 1 <= int(radius) <= 4:
+        raise StcdError(f"radius must be in [1, 4], got {radius}")
+    if not 1 <= int(mask_value) <= 255:
+        raise StcdError(f"mask_value must be in [1, 255], got {mask_value}")
+    H, W = mask.shape
+    with torch.cuda.device(mask.device):
+        out = torch.empty_like(mask)
+        if H and W:                                             # an empty mask has one address for both: nothing to close
+            stream = C.c_void_p(torch.cuda.current_stream(mask.device).cuda_stream)
+            _lib.check(_lib.lib().stcd_mask_close(_ptr(mask), int(H), int(W), int(radius), int(mask_value), _ptr(out), stream))
+    return out
+
+
+def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stride: Optional[int] = None, batch: int = 16,
+                window: str = "flat", tta=None, threshold: float = 0.0, close_radius: int = 0, label=None, cumulative: bool = False,
+                stem: str = "scene") -> SceneRound:
+    """The round of train_stcd.py:96-204 over one pair of whole uint8 ``[H,W,3]`` scenes instead of pre-cut crops.
+
+    Each of the K ``models`` (1..8 modules on one GPU, earlier checkpoints first) goes through ``scene.predict_scene`` alone, in the
+    given order, with ``tile``, ``stride``, ``batch``, ``window``, ``tta`` and ``threshold`` as given: ``masks[k]`` is bit-equal to
+    ``predict_scene(models[k], ...).mask``.  One ``stcd_scene_cell_agree`` launch then counts, per ``cell`` x ``cell`` square of the
+    scene, the agreement of every earlier checkpoint with the last; ``reliability(agree, cumulative)`` runs over the cells in
+    row-major order.  ``pseudo`` is the last checkpoint's mask as 0 / 255, closed by ``stcd_mask_close`` if ``close_radius`` > 0
+    (2 is the reference's 5 x 5 closing).  With a ``label`` (uint8 ``[H,W]``, >= 1 is change, 255 is ignored) a second launch gives
+    the confusion matrix of ``pseudo`` per cell; ``cm`` is their sum and ``scores`` its ``scores_from_cm``.
+
+    Cells at the right and bottom edge that are no whole square are scored and reported (``full`` is False there) but never
+    listed: ``reliable`` / ``unreliable`` are ``split_reliable`` over the full cells.  The counts come back in one copy.  Every
+    argument error is raised before the first launch."""
+    from . import scene as _scene
+
+    models = _model_list(models)
+    dev = _device_of(models)
+    a, b = _scene._scene_tensor(scene_a, "scene_a"), _scene._scene_tensor(scene_b, "scene_b")
+    if a.shape != b.shape:
+        raise StcdError(f"the scenes differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    if H < 1 or W < 1:
+        raise StcdError(f"an empty scene: {H} x {W}")
+    _scene.plan_tiles(H, W, tile, stride)
+    _scene.window_table(tile, window)
+    _scene.parse_tta(tta)
+    if int(batch) < 1:
+        raise StcdError(f"batch must be >= 1, got {batch}")
+    cells_y, cells_x = cell_grid(H, W, cell)
+    cell = int(cell)
+    if not 0 <= int(close_radius) <= 4:
+        raise StcdError(f"close_radius must be in [0, 4] (0: no closing), got {close_radius}")
+    if not isinstance(stem, str) or not stem:
+        raise StcdError(f"stem must be a non-empty string, got {stem!r}")
+    lab = None
+    if label is not None:
+        lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
+        if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
+            raise StcdError(f"label must be uint8 [{H},{W}]")
+    # everything is checked: from here on the device works
+    a, b = a.to(dev).contiguous(), b.to(dev).contiguous()       # once, not once per checkpoint
+    lab = None if lab is None else lab.to(dev).contiguous()
+    K = len(models)
+    masks = [predict_scene(m, a, b, tile=tile, stride=stride, batch=batch, window=window, threshold=threshold, tta=tta).mask for m in models]
+    agree_dev = scene_cell_agree(masks, cell)[0] if K > 1 else None
+    pseudo = mask_close(masks[-1], int(close_radius), 255) if int(close_radius) > 0 else masks[-1] * 255
+    cm_dev = scene_cell_agree([pseudo], cell, label=lab)[1] if lab is not None else None
+    # the only wait for the device: the counts
+    agree = None if agree_dev is None else agree_dev.cpu().numpy().reshape(cells_y, cells_x, K - 1, 2, 2)
+    cell_cm = None if cm_dev is None else cm_dev.cpu().numpy().reshape(cells_y, cells_x, 2, 2)
+    n = cells_y * cells_x
+    rel = reliability(agree.reshape(n, K - 1, 2, 2), cumulative) if K > 1 else np.ones(n, np.float64)
+    names = [f"{stem}_{cy:04d}_{cx:04d}.png" for cy in range(cells_y) for cx in range(cells_x)]
+    full = np.zeros((cells_y, cells_x), bool)
+    full[:H // cell, :W // cell] = True
+    listed = [int(i) for i in np.flatnonzero(full)]
+    reliable, unreliable = split_reliable([names[i] for i in listed], rel[listed])
+    cm = None if cell_cm is None else cell_cm.sum(axis=(0, 1))
+    return SceneRound(masks, pseudo, agree, rel.reshape(cells_y, cells_x), cell_cm, cm, None if cm is None else scores_from_cm(cm), names, full,
+                      reliable, unreliable, cell)
+
+
+def export_cells(round: SceneRound, scene_a, scene_b, root: str, label=None) -> None:
+    """The full cells of a ``scene_round`` as the tile set the reference's ``CD_Dataset`` reads (data/dataset.py:169-212, :337-344):
+    ``A/<name>`` and ``B/<name>`` (RGB PNG) cut from the uint8 ``[H,W,3]`` scenes, ``pseudo_label/<name>`` (mode L, 0 / 255) from
+    ``round.pseudo``, ``label/<name>`` (mode L) when a ``label`` (uint8 ``[H,W]``) is given, and ``list/reliable_ids.txt`` /
+    ``list/unreliable_ids.txt``.  A crop is a slice of the tensor where it lives (GPU or CPU) and one copy to the host; the PNG
+    encoding is host work.  Partial edge cells are not written."""
+    from PIL import Image
+
+    from .scene import _scene_tensor
+    a, b = _scene_tensor(scene_a, "scene_a"), _scene_tensor(scene_b, "scene_b")
+    H, W = (int(v) for v in round.pseudo.shape)
+    if tuple(a.shape) != (H, W, 3) or tuple(b.shape) != (H, W, 3):
+        raise StcdError(f"the scenes must be [{H},{W},3] as the round's pseudo-label: {tuple(a.shape)} and {tuple(b.shape)}")
+    lab = None
+    if label is not None:
+        lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
+        if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
+            raise StcdError(f"label must be uint8 [{H},{W}]")
+    cell = int(round.cell)
+    cells_y, cells_x = cell_grid(H, W, cell)
+    if tuple(round.full.shape) != (cells_y, cells_x) or len(round.names) != cells_y * cells_x:
+        raise StcdError("the round's cell grid does not fit its pseudo-label")
+    layers = [("A", a), ("B", b), ("pseudo_label", round.pseudo)] + ([("label", lab)] if lab is not None else [])
+    for sub, _ in layers:
+        os.makedirs(os.path.join(root, sub), exist_ok=True)
+    for cy in range(cells_y):
+        for cx in range(cells_x):
+            if not round.full[cy, cx]:
+                continue
+            name = round.names[cy * cells_x + cx]
+            for sub, src in layers:
+                crop = src[cy * cell:(cy + 1) * cell, cx * cell:(cx + 1) * cell].contiguous().cpu().numpy()
+                Image.fromarray(crop).save(os.path.join(root, sub, name), format="PNG")
+    write_lists(os.path.join(root, "list"), round.reliable, round.unreliable)
