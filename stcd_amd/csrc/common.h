@@ -262,6 +262,7 @@ void launch_pack_frag(const stcd_conv_geom& g, const ConvMfmaPlan& p, const floa
                       hipStream_t s);
 int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const void* in, const void* wf, const float* bias,
                      void* out, bool out_nchw_f32, hipStream_t s);
+bool conv_mfma_x4_ok(const stcd_conv_geom g[4], const ConvMfmaPlan p[4]);      // the four phases share one launch shape
 int launch_conv_mfma_x4(const stcd_conv_geom g[4], const ConvMfmaPlan p[4], const void* in, const void* const wf[4],
                         const float* bias, void* out, hipStream_t s);
 // resident-filter persistent kernel for 3x3 stride-1 convs with Ci % 32 == 0 (uses the mode-A fragment image)
@@ -285,6 +286,7 @@ int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvRe
                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
                     float s1_scale = BN_FS1, float s2_scale = BN_FS2, const XfSrc* xf = nullptr, const BwdSum* bs = nullptr);
 bool conv_res_bwdsum_ok(const stcd_conv_geom& g, const ConvResPlan& rp);
+bool conv_res_xf_ok(const stcd_conv_geom& g, const ConvResPlan& rp, int groups, const XfSrc& xf);      // a virtual input on this plan
 // k_conv_res's tile and epilogue for 3x3 stride-1 convs with Ci % 64 == 0, Co % 16 == 0 on SMALL maps, staged by LDS-DMA: the filter
 // slice once per block and the 18 x 18 halo in 64-channel parts, all K of a tile requested before its first MFMA (Ci <= 128; two
 // parts in flight for Ci = 256); kernels_conv_tile.hip.  Reads the CiB = 64 fragment image; outputs bit-identical to k_conv_res's.
@@ -350,6 +352,7 @@ int conv_small_blocks(const stcd_conv_geom& g, int groups);
 int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_modeB, const float* bias, void* out,
                       bool out_nchw_f32, int groups, long long* stat_acc, int cpad, hipStream_t s, const XfSrc* xf = nullptr,
                       const BwdSum* bs = nullptr);
+bool conv_small_call_ok(const stcd_conv_geom& g, int groups, const XfSrc* xf);      // what a call's groups / virtual input add to conv_small_ok
 bool conv_small_bwdsum_ok(const stcd_conv_geom& g);      // shapes the fused form handles (16 channels out, whole 8 x 16 tiles, 3 / 5 k-steps)
 struct WgradMfmaPlan {
     int WCI = 1, NTW = 1, gx = 1, gy = 1, gz = 1;

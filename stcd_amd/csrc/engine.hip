@@ -291,7 +291,7 @@ struct stcd_engine_impl {
     int64_t final_bias_acc = -1;
     std::vector<BiasJob> bias_jobs; int64_t bias_jobs_off = -1;
     int64_t masks = -1, dwe_begin = -1, dwe_end = -1, scratch8 = -1;
-    int use_mfma = 1, use_small = 1, use_wgroup = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, use_bwdsum = 1, use_bwdsum_res = 0, use_tile = 1;
+    int use_mfma = 1, use_small = 1, use_wgroup = 1, use_res = 1, use_skip_fused = 1, use_act_fuse = 1, use_gemm = 1, use_skip_recompute = 1, use_bwdsum = 1, use_bwdsum_res = 0, use_tile = 1, use_halo = 0;
     // FC-Siam backward: the decoder's grouped weight gradients (+ slab reduce, bias finish) run on a low-priority side stream beside
     // the encoder's backward chain on the caller's stream; their grids get 1 / WG_SIDE_DIV of the planner's block budget so that the
     // chain's blocks find free slots (wgrad_side_stream)
@@ -559,22 +559,18 @@ static void conv_work(const stcd_engine& e, const stcd_conv_geom& g, int kreal, 
 // the tap-list GEMM kernel takes what the resident-filter kernel cannot, and -- for ChangeFormer -- what the resident kernel would
 // run in 16-channel output slices, i.e. re-read X once per 16 output channels
 static void pick_gemm_or_res(const stcd_engine& e, ConvOp& op, const stcd_conv_geom& g, int groups) {
-    op.gemm = ConvGemmPlan();
-    op.tile = ConvTilePlan();
     if (!e.use_gemm || op.small) return;
     // (ChangeFormer's 256-channel decoder convolutions get 16-channel output slices from the resident-filter kernel, i.e. X is
     //  re-read 16 times through L2: the GEMM kernel's 128 x 128 tile measured 8.3 vs 9.5 ms per step there; a tie elsewhere)
     if (op.res.ok && !(e.cf && op.res.NT == 1)) return;
     op.gemm = conv_gemm_plan(g, op.plan, groups);
-    if (op.gemm.ok) op.res = ConvResPlan();
+    if (!op.gemm.ok) return;
+    op.res = ConvResPlan();
+    // the LDS-DMA kernel takes the layers it fits once they fill the chip with 256-position tiles (ChangeFormer's decoder head)
+    if ((int64_t)g.n * g.hm * g.wm >= 256 * 192) op.dma = conv_dma_plan(g, op.plan);
     // opt-in (measured 0.93 - 1.03 of k_conv_gemm on ChangeFormer's 256 -> 256 layers): layers that take the GEMM kernel,
     // carry no fused BatchNorm statistics (groups == 1 callers that pass none) and fill the chip with 16 x 16 tiles
-    static const bool halo_on = env_flag("STCD_HALO_KERNEL", false);
-    op.halo = ConvHaloPlan();
-    // the LDS-DMA kernel takes the layers it fits once they fill the chip with 256-position tiles (ChangeFormer's decoder head)
-    op.dma = ConvDmaPlan();
-    if (op.gemm.ok && (int64_t)g.n * g.hm * g.wm >= 256 * 192) op.dma = conv_dma_plan(g, op.plan);
-    if (halo_on && op.gemm.ok && (int64_t)g.n * ((g.hm + 15) / 16) * ((g.wm + 15) / 16) >= 512) op.halo = conv_halo_plan(g, op.plan);
+    if (e.use_halo && (int64_t)g.n * ((g.hm + 15) / 16) * ((g.wm + 15) / 16) >= 512) op.halo = conv_halo_plan(g, op.plan);
 }
 
 // The LDS-DMA tile kernel takes a resident-filter layer (same tile, same results) where the launch is a short chain of steps per
@@ -582,7 +578,6 @@ static void pick_gemm_or_res(const stcd_engine& e, ConvOp& op, const stcd_conv_g
 // steps and wait out a memory round trip in each.  Measured per shape in DESIGN.md section 4; STCD_NO_TILE_KERNEL=1 turns it off.
 constexpr int TILE_MAX_TILES = 512;
 static void pick_tile(const stcd_engine& e, ConvOp& op, const stcd_conv_geom& g, int groups) {
-    op.tile = ConvTilePlan();
     if (!e.use_tile || !op.res.ok || op.gemm.ok || op.small) return;
     const ConvTilePlan tp = conv_tile_plan(g, op.plan, groups);
     if (tp.ok && tp.ntiles <= TILE_MAX_TILES) op.tile = tp;
@@ -604,6 +599,68 @@ static WgradMfmaPlan pick_wgrad_plan(const stcd_engine& e, const stcd_conv_geom&
         if (p.ok) return p;
     }
     return wgrad_mfma_plan(g, kpad, wld, is_snunet(e.arch) || (e.cf && g.ntaps == 9));
+}
+
+// plans of every kernel that may take the bf16 launch op.g (conv_kernel chooses among them per call); with_tile: FC-Siam alone
+static void plan_conv(const stcd_engine& e, ConvOp& op, int groups, bool with_tile) {
+    op.plan = conv_mfma_plan(op.g);
+    op.small = conv_small_ok(op.g, op.plan);
+    if (e.use_res && !op.small) op.res = conv_res_plan(op.g, op.plan, groups);
+    pick_gemm_or_res(e, op, op.g, groups);
+    if (with_tile) pick_tile(e, op, op.g, groups);
+}
+// the launches of the reference kernel: no bf16 MFMA plan, or no fragment image.  build_pack_jobs packs the fp32 filter image for
+// exactly these, and conv_kernel sends exactly these there.
+static bool conv_on_ref(bool mfma, const ConvOp& op) { return !(mfma && op.plan.ok && op.wf >= 0); }
+// ---- the binder: every conv-shaped launch and every weight gradient of every family is bound here, at configure time.  Both start
+//      from a value-initialised op (a re-configure at another shape reuses the objects) and keep only what the caller passes.
+struct Binder {
+    stcd_engine& e; Bump& ws;
+    bool with_tile = false;      // k_conv_tile is a candidate (FC-Siam)
+    void conv(ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) const {
+        op = ConvOp();
+        op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal; op.res_groups = groups;
+        if (e.dt == BF16) plan_conv(e, op, groups, with_tile);
+        if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
+        e.conv_ops.push_back(&op);
+    }
+    // the 7x7 stem's forward with its plan forced: the tap-list GEMM kernel over 8-pixel rows (g.ci = 64 "channels" = 8 pixels x 8
+    // padded channels), or not bound at all -- the dedicated fp32 kernel then runs it
+    void stem(ConvOp& op, const stcd_conv_geom& g, int conv, int groups) const {
+        op = ConvOp();
+        op.g = g; op.conv = conv; op.kreal = e.convs[conv].cin; op.nreal = g.co; op.res_groups = groups;
+        op.plan = conv_mfma_plan(g);
+        if (g.ldi == 8 && g.co % 64 == 0) op.gemm = conv_gemm_plan(g, op.plan, groups);
+        op.gemm.pix_chunks = 1;
+        if (!op.gemm.ok) return;
+        op.wf = ws.take(op.plan.wf_elems * 2);
+        e.conv_ops.push_back(&op);
+    }
+    // own_ky / own_kx: the filter taps of this launch given here instead of conv.fwd.ky / kx[tap0 + t] (the 7x7 stem)
+    void wgrad(WgradOp& op, const stcd_conv_geom& g, int conv, int64_t in_off, int64_t dout_off, int stage = 0, int tap0 = 0,
+               int wi_valid = 0, const int8_t* own_ky = nullptr, const int8_t* own_kx = nullptr) const {
+        const ConvW& cv = e.convs[conv];
+        op = WgradOp();
+        op.g = g; op.conv = conv; op.tap0 = tap0; op.kreal = cv.cin; op.nreal = cv.cout;
+        op.in_off = in_off; op.dout_off = dout_off; op.stage = stage;
+        op.own_taps = own_ky != nullptr;
+        for (int t = 0; t < g.ntaps && op.own_taps; ++t) { op.oky[t] = own_ky[t]; op.okx[t] = own_kx[t]; }
+        if (e.dt == BF16) { op.plan = pick_wgrad_plan(e, g, cv.fwd.kpad, cv.fwd.wld); op.plan.wi_valid = wi_valid; }
+        e.wgrad_ops.push_back(&op);
+    }
+};
+// the fp32 filter images of the reference kernels and the fp64 accumulators of the reference weight-gradient path
+static void take_ref_images(stcd_engine& e, Bump& ws, bool with_dwe = true) {
+    for (auto& c : e.convs) {
+        c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
+        if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
+    }
+    e.dwe_begin = ws.cur;
+    for (auto& c : e.convs) {
+        c.dwe_floats = (int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld;
+        c.dwe = with_dwe ? ws.take(c.dwe_floats * 8) : -1;
+    }
+    e.dwe_end = ws.cur;
 }
 
 // the grouped launch a weight gradient belongs to: same kernel variant (one LDS-DMA group per stage, whatever the tap count)
@@ -787,12 +844,12 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
                     push(j);
                     continue;
                 }
-                if (op->plan.ok && op->wf >= 0) {
+                if (!conv_on_ref(true, *op)) {
                     j.kind = 1; j.dst_off = op->wf;
                     j.count = op->plan.modeB ? op->plan.wf_elems : op->plan.wf_elems / op->g.ntaps;      // mode A: one thread per (ci, co), all taps
                     j.Ci = op->g.ci; j.Co = op->g.co; j.CiB = op->plan.CiB; j.nchunks = op->plan.nchunks; j.KS = op->plan.KS;
                     j.NTtot = op->plan.NTtot; j.modeB = op->plan.modeB;
-                } else {   // no MFMA plan for this launch: it runs on the reference kernel and needs the fp32 image
+                } else {   // no MFMA plan for this launch: it runs on the reference kernel (conv_kernel) and needs the fp32 image
                     j.kind = 0;
                     j.dst_off = (op->dgrad ? cv.wpk_dgrad : cv.wpk_fwd) + (int64_t)op->tap0 * full.kpad * full.wld * 4;
                     j.count = (int64_t)j.ps.ntaps * full.kpad * full.wld;
@@ -950,50 +1007,20 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
     if (za.cur > e.zero_end) { set_error("internal: zero arena overflow"); return 1; }
     e.scratch8 = ws.take(256);
     e.masks = ws.take(e.drop_floats * 4);
-    for (auto& c : e.convs) {
-        c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
-        if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
-    }
-    e.dwe_begin = ws.cur;
-    for (auto& c : e.convs) {
-        c.dwe_floats = (int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld;
-        c.dwe = ws.take(c.dwe_floats * 8);     // fp64 accumulators of the reference weight-gradient path
-    }
-    e.dwe_end = ws.cur;
+    take_ref_images(e, ws);
 
     // ---- bind every conv-shaped launch (geometry, filter, MFMA plan); the layer vectors are final from here on
     e.conv_ops.clear();
     e.wgrad_ops.clear();
     e.slab_floats = 0;
-    auto bind_conv = [&](ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) {
-        op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.plan = ConvMfmaPlan(); op.wf = -1; op.res = ConvResPlan(); op.res_groups = groups;
-        if (e.dt == BF16) {
-            op.plan = conv_mfma_plan(g);
-            if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
-            op.small = conv_small_ok(g, op.plan);
-            if (e.use_res && !op.small) op.res = conv_res_plan(g, op.plan, groups);
-            pick_gemm_or_res(e, op, g, groups);
-            pick_tile(e, op, g, groups);
-        }
-        e.conv_ops.push_back(&op);
-    };
-    auto bind_wgrad = [&](WgradOp& op, const stcd_conv_geom& g, int conv, int tap0, int kreal, int nreal, int64_t in_off,
-                          int64_t dout_off) {
-        op.g = g; op.conv = conv; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.in_off = in_off; op.dout_off = dout_off; op.grouped = false;
-        op.xf_stat_off = op.xf_mask_off = -1; op.xf_C = 0; op.xf_groups = op.xf_npg = 1;
-        op.plan = WgradMfmaPlan(); op.slab = -1;
-        op.stage = e.convs[conv].w_off < e.enc_param_end ? 1 : 0;     // encoder filters are finalised by stage 1
-        if (e.dt == BF16) op.plan = pick_wgrad_plan(e, g, e.convs[conv].fwd.kpad, e.convs[conv].fwd.wld);
-        e.wgrad_ops.push_back(&op);
-    };
+    const Binder bind{e, ws, true};
+    auto wg_stage = [&](int conv) { return e.convs[conv].w_off < e.enc_param_end ? 1 : 0; };     // encoder filters are finalised by stage 1
     auto bind_cbrd = [&](Cbrd& L) {
         const ConvW& cv = e.convs[L.conv];
-        bind_conv(L.fwd, geom3(L.N, L.H, L.W, L.K, L.in.ld, cv.cout, L.Y.ld), L.conv, false, 0, cv.cin, cv.cout, L.groups);
-        bind_wgrad(L.wg, geom3(L.N, L.H, L.W, L.K, L.in.ld, cv.cout, L.dY.ld), L.conv, 0, cv.cin, cv.cout, L.in.off, L.dY.off);
+        bind.conv(L.fwd, geom3(L.N, L.H, L.W, L.K, L.in.ld, cv.cout, L.Y.ld), L.conv, false, 0, cv.cin, cv.cout, L.groups);
+        bind.wgrad(L.wg, geom3(L.N, L.H, L.W, L.K, L.in.ld, cv.cout, L.dY.ld), L.conv, L.in.off, L.dY.off, wg_stage(L.conv));
         if (L.has_dIn)      // (tiles partitioned by the layer's BatchNorm groups: its data gradient may carry the previous layer's backward sums)
-            bind_conv(L.dgr, geom3(L.N, L.H, L.W, cv.dgrad.kpad, L.dY.ld, cv.cin, L.dIn.ld), L.conv, true, 0, cv.cout, cv.cin,
+            bind.conv(L.dgr, geom3(L.N, L.H, L.W, cv.dgrad.kpad, L.dY.ld, cv.cin, L.dIn.ld), L.conv, true, 0, cv.cout, cv.cin,
                       (e.use_bwdsum && e.use_bwdsum_res) ? L.groups : 1);
     };
     for (auto& L : e.enc) bind_cbrd(L);
@@ -1004,8 +1031,8 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
         for (int ph = 0; ph < 4; ++ph) {
             int tap0;
             stcd_conv_geom g = geom_up_phase(U, ph >> 1, ph & 1, U.in.ld, U.out.ld, &tap0);
-            bind_conv(U.fwd[ph], g, U.conv, false, tap0, U.C, U.C);
-            bind_wgrad(U.wg[ph], g, U.conv, tap0, U.C, U.C, U.in.off, U.dOut.off);
+            bind.conv(U.fwd[ph], g, U.conv, false, tap0, U.C, U.C);
+            bind.wgrad(U.wg[ph], g, U.conv, U.in.off, U.dOut.off, wg_stage(U.conv), tap0);
         }
         // data gradient: 3x3 stride-2 conv over dOut.  (hi,wi) are the BUFFER dims (row pitch); taps reach at most
         // row 2h-1 / col 2w-1, so replication-padded rows/cols are never read.
@@ -1017,13 +1044,13 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
         gd.co = U.C; gd.ldo = U.dIn.ld;
         gd.ntaps = 9;
         for (int t = 0; t < 9; ++t) { gd.dy[t] = (int8_t)(t / 3 - 1); gd.dx[t] = (int8_t)(t % 3 - 1); }
-        bind_conv(U.dgr, gd, U.conv, true, 0, U.C, U.C);
+        bind.conv(U.dgr, gd, U.conv, true, 0, U.C, U.C);
     }
     {
         const ConvW& cv = e.convs[e.final_conv];
-        bind_conv(e.final_fwd, geom3(B, H, W, cv.kin_p, e.finalIn.ld, e.label, e.label), e.final_conv, false, 0, cv.cin, e.label);
-        bind_wgrad(e.final_wg, geom3(B, H, W, cv.kin_p, e.finalIn.ld, e.label, 8), e.final_conv, 0, cv.cin, e.label, e.finalIn.off, e.G.off);
-        bind_conv(e.final_dgr, geom3(B, H, W, cv.dgrad.kpad, 8, cv.cin, e.dFinalIn.ld), e.final_conv, true, 0, e.label, cv.cin);
+        bind.conv(e.final_fwd, geom3(B, H, W, cv.kin_p, e.finalIn.ld, e.label, e.label), e.final_conv, false, 0, cv.cin, e.label);
+        bind.wgrad(e.final_wg, geom3(B, H, W, cv.kin_p, e.finalIn.ld, e.label, 8), e.final_conv, e.finalIn.off, e.G.off, wg_stage(e.final_conv));
+        bind.conv(e.final_dgr, geom3(B, H, W, cv.dgrad.kpad, 8, cv.cin, e.dFinalIn.ld), e.final_conv, true, 0, e.label, cv.cin);
     }
     e.slab = ws.take(e.slab_floats * 4);
 
@@ -1213,100 +1240,144 @@ static bool mfma_on(const stcd_engine& e) { return e.dt == BF16 && e.use_mfma; }
 // A request for per-channel sums of the launch's output, fused into the conv's epilogue: BatchNorm statistics of a forward
 // conv (all channels, sum and sum of squares) or the sum of a channel slice of a data gradient (a bias gradient).
 struct StatReq { long long* acc = nullptr; int groups = 1; int c0 = 0; int C = 0; float s1 = BN_FS1, s2 = BN_FS2; };
-// *fused receives 1 when the kernel delivered the sums, 0 when the caller must run the separate pass.
+
+// ---- which kernel a conv-shaped launch runs on.  Decided HERE and nowhere else: exec_conv and the per-op ABI (stcd_op_conv impl 1)
+//      ask conv_kernel once per call and dispatch on the answer; a launcher that then rejects is an error, not a reason to try the
+//      next kernel.  The plans it reads were made by plan_conv at configure time; the precedence below is the table in DESIGN.md
+//      section 3.  Without statistics (eval, data gradients) k_conv_dma / k_conv_halo come before k_conv_gemm; with them they cannot.
+enum class ConvKernel { REF, MFMA, SMALL, RES, TILE, GEMM, HALO, DMA };
+constexpr unsigned conv_kernel_bit(ConvKernel k) { return 1u << (int)k; }
+struct ConvCall {                         // the facts about one call that the choice consults
+    bool nchw = false;                    // fp32 NCHW output (a network output)
+    int stat_groups = 0;                  // fused per-channel sums requested: their group count (0: none) ...
+    bool bn_form = false;                 // ... and whether they are BatchNorm statistics of all channels (k_conv_small sums nothing else)
+    const XfSrc* xf = nullptr;            // virtual-activation input (active when xf->on)
+    bool bwd = false;                     // BwdSum: the launch also forms BatchNorm-backward sums
+    unsigned allowed = ~0u;               // conv_kernel_bit mask of the kernels the caller can run
+    // (a ConvEpi does not steer the choice: kernels without the fused epilogue report epi_fused = 0 and the caller runs it element-wise)
+};
+// tile groups of a k_conv_small launch: a virtual input partitions the tiles by the PRODUCER's BatchNorm groups, statistics or not
+// (eval mode has none); else the groups of the BatchNorm statistics it sums
+static int conv_small_groups(const ConvCall& k) {
+    return (k.xf && k.xf->on) ? k.xf->groups : (k.stat_groups > 0 && k.bn_form) ? k.stat_groups : 1;
+}
+static ConvKernel conv_kernel(bool mfma, bool use_small, const ConvOp& op, const ConvCall& k) {
+    auto may = [&](ConvKernel x) { return (k.allowed & conv_kernel_bit(x)) != 0; };
+    if (conv_on_ref(mfma, op)) return ConvKernel::REF;
+    const bool xf_on = k.xf && k.xf->on, stats = k.stat_groups > 0;
+    const bool small = op.small && use_small;
+    if (k.bwd) return small ? ConvKernel::SMALL : ConvKernel::RES;
+    if (op.gemm.ok && !k.nchw) {
+        if (op.dma.ok && op.res_groups == 1 && !stats && may(ConvKernel::DMA)) return ConvKernel::DMA;
+        if (op.halo.ok && !stats && may(ConvKernel::HALO)) return ConvKernel::HALO;
+        return ConvKernel::GEMM;
+    }
+    if (small && conv_small_call_ok(op.g, conv_small_groups(k), k.xf)) return ConvKernel::SMALL;
+    if (op.res.ok && !k.nchw && !small) {
+        if (op.tile.ok && !xf_on && may(ConvKernel::TILE)) return ConvKernel::TILE;
+        if (!xf_on || conv_res_xf_ok(op.g, op.res, op.res_groups, *k.xf)) return ConvKernel::RES;
+    }
+    return ConvKernel::MFMA;
+}
+// the name rocprofv3 prints for the choice (bench.py and the committed profile tables key on these strings)
+static void conv_kernel_name(ConvKernel kern, const ConvOp& op, bool bwd, char (&kname)[64]) {
+    switch (kern) {
+        case ConvKernel::DMA: snprintf(kname, sizeof(kname), "k_conv_dma"); break;
+        case ConvKernel::HALO: snprintf(kname, sizeof(kname), "k_conv_halo"); break;
+        case ConvKernel::GEMM: snprintf(kname, sizeof(kname), "k_conv_gemm<%d>", op.gemm.W); break;
+        case ConvKernel::TILE: snprintf(kname, sizeof(kname), "k_conv_tile<%d>", op.tile.NT); break;
+        case ConvKernel::RES:
+            if (bwd) snprintf(kname, sizeof(kname), "k_conv_res<bwd>");
+            else snprintf(kname, sizeof(kname), "k_conv_res<%d, %d, %s>", op.res.NT, op.res.CW, op.res.single_halo ? "true" : "false");
+            break;
+        case ConvKernel::SMALL:
+            if (bwd) snprintf(kname, sizeof(kname), "k_conv_small<bwd>");
+            else snprintf(kname, sizeof(kname), "k_conv_small<1, %d>", (op.g.ntaps * op.g.ci + 31) / 32 <= 5 ? 5 : 9);
+            break;
+        case ConvKernel::MFMA: snprintf(kname, sizeof(kname), "k_conv_mfma<%d>", op.plan.NT); break;
+        case ConvKernel::REF: snprintf(kname, sizeof(kname), "k_conv_ref"); break;
+    }
+}
+
+// *stat_chunks receives 1 when the kernel delivered the sums, 0 when the caller must run the separate pass; *epi_fused likewise
 static void exec_conv(const Ctx& c, const ConvOp& op, const void* in, const float* bias, void* out, bool nchw,
                       const StatReq* sr = nullptr, int* stat_chunks = nullptr, const ConvEpi* epi = nullptr, int* epi_fused = nullptr,
                       const XfSrc* xf = nullptr, const BwdSum* bs = nullptr) {
-    const int stat_groups = (sr && sr->acc) ? sr->groups : 0;
-    long long* stat_acc = sr ? sr->acc : nullptr;
-    const bool bn_form = sr && sr->c0 == 0 && sr->C == op.g.co && sr->s1 == BN_FS1 && sr->s2 == BN_FS2;
     const ConvW& cv = c.e.convs[op.conv];
-    const PackSpec& ps = op.dgrad ? cv.dgrad : cv.fwd;
+    long long* stat_acc = sr ? sr->acc : nullptr;
+    ConvCall call;
+    call.nchw = nchw; call.xf = xf; call.bwd = bs != nullptr;
+    call.stat_groups = stat_acc ? sr->groups : 0;
+    call.bn_form = sr && sr->c0 == 0 && sr->C == op.g.co && sr->s1 == BN_FS1 && sr->s2 == BN_FS2;
+    const ConvKernel kern = conv_kernel(mfma_on(c.e), c.e.use_small, op, call);
     double fl, by;
     conv_work(c.e, op.g, op.kreal, op.nreal, &fl, &by);
+    if (bs) by += (double)op.g.n * op.g.ho * op.g.wo * op.g.co * 2.0;
     char kname[64];
-    const bool gemm_path = mfma_on(c.e) && op.gemm.ok && op.wf >= 0 && !nchw;
-    const bool small_path = !gemm_path && mfma_on(c.e) && op.small && op.wf >= 0 && c.e.use_small;
-    const bool res_path = !gemm_path && !small_path && mfma_on(c.e) && op.res.ok && op.wf >= 0 && !nchw;
-    const bool mfma_path = !small_path && !res_path && mfma_on(c.e) && op.plan.ok && op.wf >= 0;
-    const bool tile_path = res_path && op.tile.ok && !(xf && xf->on) && !bs;
-    const bool dma_path = gemm_path && op.dma.ok && op.res_groups == 1 && !(stat_groups > 0 && stat_acc);
-    if (dma_path) snprintf(kname, sizeof(kname), "k_conv_dma");
-    else if (gemm_path && op.halo.ok && !(stat_groups > 0 && stat_acc)) snprintf(kname, sizeof(kname), "k_conv_halo");
-    else if (gemm_path) snprintf(kname, sizeof(kname), "k_conv_gemm<%d>", op.gemm.W);
-    else if (tile_path) snprintf(kname, sizeof(kname), "k_conv_tile<%d>", op.tile.NT);
-    else if (res_path) snprintf(kname, sizeof(kname), "k_conv_res<%d, %d, %s>", op.res.NT, op.res.CW, op.res.single_halo ? "true" : "false");
-    else if (small_path) snprintf(kname, sizeof(kname), "k_conv_small<1, %d>", (op.g.ntaps * op.g.ci + 31) / 32 <= 5 ? 5 : 9);
-    else if (mfma_path) snprintf(kname, sizeof(kname), "k_conv_mfma<%d>", op.plan.NT);
-    else snprintf(kname, sizeof(kname), "k_conv_ref");
-    if (bs) {      // planned at configure time for exactly this kernel (dest_ok): anything else is a plan error
-        ProfScope ps2(c, PC_CONV, fl, by + (double)op.g.n * op.g.ho * op.g.wo * op.g.co * 2.0, small_path ? "k_conv_small<bwd>" : "k_conv_res<bwd>");
-        const int rc = small_path ? launch_conv_small(op.g, in, c.at(op.wf), bias, out, nchw, bs->groups, nullptr, op.g.co, c.s, nullptr, bs)
-                                  : launch_conv_res(op.g, op.plan, op.res, in, c.at(op.wf), bias, out, op.res_groups, nullptr, op.g.co, c.s, 0,
-                                                    BN_BS, BN_BS, nullptr, bs);
-        if (rc != 0) set_error("fused BatchNorm-backward sums: the data-gradient launch does not fit its BWD kernel");
-        return;
-    }
+    conv_kernel_name(kern, op, bs != nullptr, kname);
     ProfScope prof(c, PC_CONV, fl, by, kname);
     if (stat_chunks) *stat_chunks = 0;
     if (epi_fused) *epi_fused = 0;
-    if (dma_path && launch_conv_dma(op.g, op.plan, op.dma, in, c.at(op.wf), bias, out, c.s, epi) == 0) {
-        if (epi_fused && epi) *epi_fused = 1;
-        return;
-    }
-    if (gemm_path && op.halo.ok && !(stat_groups > 0 && stat_acc)) {
-        if (launch_conv_halo(op.g, op.plan, op.halo, in, c.at(op.wf), bias, out, c.s, epi) == 0) {
-            if (epi_fused && epi) *epi_fused = 1;
-            return;
-        }
-    }
-    if (gemm_path) {
-        const bool want = stat_groups > 0 && stat_groups == op.res_groups && stat_acc;
-        long long* sp = want ? stat_acc : nullptr;
-        if (launch_conv_gemm(op.g, op.plan, op.gemm, in, c.at(op.wf), bias, out, op.res_groups, sp, want ? sr->C : op.g.co, c.s,
-                           want ? sr->c0 : 0, want ? sr->s1 : BN_FS1, want ? sr->s2 : BN_FS2, epi) == 0) {
-            if (stat_chunks && want) *stat_chunks = 1;
-            if (epi_fused && epi) *epi_fused = 1;      // (the other kernels have no fused epilogue: the caller runs it element-wise)
-            return;
-        }
-    }
-    const bool xf_on = xf && xf->on;
-    if (mfma_on(c.e) && op.small && op.wf >= 0 && c.e.use_small) {
-        // (a virtual input partitions the tiles by the PRODUCER's BatchNorm groups, statistics or not: eval mode has none)
-        const int groups = xf_on ? xf->groups : (stat_groups > 0 && bn_form) ? stat_groups : 1;
-        long long* sp = (stat_groups > 0 && bn_form && stat_groups == groups) ? stat_acc : nullptr;
-        if (launch_conv_small(op.g, in, c.at(op.wf), bias, out, nchw, groups, sp, op.g.co, c.s, xf) == 0) {
-            if (stat_chunks && sp) *stat_chunks = 1;
-            return;
-        }
-    }
-    if (tile_path) {
-        const bool want = stat_groups > 0 && stat_groups == op.res_groups && stat_acc;
-        long long* sp = want ? stat_acc : nullptr;
-        if (launch_conv_tile(op.g, op.plan, op.tile, in, c.at(op.wf), bias, out, op.res_groups, sp, want ? sr->C : op.g.co, c.s,
-                             want ? sr->c0 : 0, want ? sr->s1 : BN_FS1, want ? sr->s2 : BN_FS2) == 0) {
-            if (stat_chunks && want) *stat_chunks = 1;
-            return;
-        }
-    }
-    if (res_path) {
-        const bool want = stat_groups > 0 && stat_groups == op.res_groups && stat_acc;
-        long long* sp = want ? stat_acc : nullptr;
-        if (launch_conv_res(op.g, op.plan, op.res, in, c.at(op.wf), bias, out, op.res_groups, sp, want ? sr->C : op.g.co, c.s,
-                            want ? sr->c0 : 0, want ? sr->s1 : BN_FS1, want ? sr->s2 : BN_FS2, xf) == 0) {
-            if (stat_chunks && want) *stat_chunks = 1;
-            return;
-        }
-    }
-    if (xf_on) {     // planned at configure time for a kernel that applies the transform: nothing below can (and must not run on raw Y)
+    if (xf && xf->on && kern != ConvKernel::SMALL && kern != ConvKernel::RES) {
+        // planned at configure time for a kernel that applies the transform: no other can (and none may run on raw Y)
         set_error("internal: a virtual-activation input reached a convolution kernel without the staging transform");
         return;
     }
-    if (mfma_on(c.e) && op.plan.ok && op.wf >= 0 &&
-        launch_conv_mfma(op.g, op.plan, in, c.at(op.wf), bias, out, nchw, c.s) == 0)
-        return;
-    const float* w = c.at<float>(op.dgrad ? cv.wpk_dgrad : cv.wpk_fwd) + (int64_t)op.tap0 * ps.kpad * ps.wld;
-    launch_conv_ref(c.e.dt, op.g, in, w, ps.kpad, ps.wld, bias, out, nchw, c.s);
+    const void* wf = op.wf >= 0 ? c.at(op.wf) : nullptr;
+    // statistics as the resident-filter family sums them: any channel slice, partitioned by the launch's own groups
+    const bool want = call.stat_groups > 0 && call.stat_groups == op.res_groups;
+    long long* sp = want ? stat_acc : nullptr;
+    const int sC = want ? sr->C : op.g.co, sc0 = want ? sr->c0 : 0;
+    const float s1 = want ? sr->s1 : BN_FS1, s2 = want ? sr->s2 : BN_FS2;
+    int rc = 0;
+    switch (kern) {
+        case ConvKernel::DMA:
+        case ConvKernel::HALO:
+            rc = kern == ConvKernel::DMA ? launch_conv_dma(op.g, op.plan, op.dma, in, wf, bias, out, c.s, epi)
+                                         : launch_conv_halo(op.g, op.plan, op.halo, in, wf, bias, out, c.s, epi);
+            if (epi_fused && epi) *epi_fused = 1;
+            break;
+        case ConvKernel::GEMM:
+            rc = launch_conv_gemm(op.g, op.plan, op.gemm, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2, epi);
+            if (stat_chunks && want) *stat_chunks = 1;
+            if (epi_fused && epi) *epi_fused = 1;
+            break;
+        case ConvKernel::SMALL:
+            if (bs) {
+                rc = launch_conv_small(op.g, in, wf, bias, out, nchw, bs->groups, nullptr, op.g.co, c.s, nullptr, bs);
+            } else {
+                const int groups = conv_small_groups(call);
+                long long* ssp = (call.stat_groups > 0 && call.bn_form && call.stat_groups == groups) ? stat_acc : nullptr;
+                rc = launch_conv_small(op.g, in, wf, bias, out, nchw, groups, ssp, op.g.co, c.s, xf);
+                if (stat_chunks && ssp) *stat_chunks = 1;
+            }
+            break;
+        case ConvKernel::TILE:
+            rc = launch_conv_tile(op.g, op.plan, op.tile, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2);
+            if (stat_chunks && want) *stat_chunks = 1;
+            break;
+        case ConvKernel::RES:
+            if (bs) {
+                rc = launch_conv_res(op.g, op.plan, op.res, in, wf, bias, out, op.res_groups, nullptr, op.g.co, c.s, 0, BN_BS, BN_BS, nullptr, bs);
+            } else {
+                rc = launch_conv_res(op.g, op.plan, op.res, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2, xf);
+                if (stat_chunks && want) *stat_chunks = 1;
+            }
+            break;
+        case ConvKernel::MFMA:
+            rc = launch_conv_mfma(op.g, op.plan, in, wf, bias, out, nchw, c.s);
+            break;
+        case ConvKernel::REF: {
+            const PackSpec& ps = op.dgrad ? cv.dgrad : cv.fwd;
+            const float* w = c.at<float>(op.dgrad ? cv.wpk_dgrad : cv.wpk_fwd) + (int64_t)op.tap0 * ps.kpad * ps.wld;
+            launch_conv_ref(c.e.dt, op.g, in, w, ps.kpad, ps.wld, bias, out, nchw, c.s);
+            break;
+        }
+    }
+    if (rc != 0)
+        set_error(bs ? std::string("fused BatchNorm-backward sums: the data-gradient launch of ") + cv.name + " does not fit " + kname
+                     : std::string("internal: ") + kname + " rejected the " + (op.dgrad ? "data-gradient" : "forward") + " launch of " +
+                           cv.name + " it was chosen for");
 }
 
 // the four sub-pixel phases of a stride-2 transposed convolution as one launch; false: not applicable (caller loops)
@@ -1321,10 +1392,12 @@ static bool exec_conv_x4(const Ctx& c, const ConvOp ops[4], const void* in, cons
         conv_work(c.e, ops[k].g, ops[k].kreal, ops[k].nreal, &f1, &b1);
         fl += f1; by += b1;
     }
+    if (!conv_mfma_x4_ok(g, p)) return false;
     char kname[64];
     snprintf(kname, sizeof(kname), "k_conv_mfma_x4<%d>", p[0].NT);
     ProfScope prof(c, PC_CONV, fl, by, kname);
-    return launch_conv_mfma_x4(g, p, in, wf, bias, out, c.s) == 0;
+    if (launch_conv_mfma_x4(g, p, in, wf, bias, out, c.s) != 0) set_error(std::string("internal: ") + kname + " rejected the launch it was chosen for");
+    return true;
 }
 
 // weight gradient of one launch, delivered straight into the reference-layout gradient tensor
@@ -2023,46 +2096,18 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         e.sn_sums = ws.take((int64_t)B * 2 * c4 * 4); e.sn_dpool = ws.take((int64_t)B * 4 * c4 * 4);
         e.sn_part = ws.take(ecam_part_floats(B, c4) * 4);
     }
-    for (auto& c : e.convs) {
-        c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
-        if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
-    }
-    e.dwe_begin = ws.cur;
-    for (auto& c : e.convs) {
-        c.dwe_floats = (int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld;
-        c.dwe = ws.take(c.dwe_floats * 8);     // fp64 accumulators of the reference weight-gradient path
-    }
-    e.dwe_end = ws.cur;
+    take_ref_images(e, ws);
 
-    auto bind_conv = [&](ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) {
-        op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.plan = ConvMfmaPlan(); op.wf = -1; op.small = false; op.res = ConvResPlan(); op.res_groups = groups;
-        if (e.dt == BF16) {
-            op.plan = conv_mfma_plan(g);
-            if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
-            op.small = conv_small_ok(g, op.plan);
-            if (e.use_res && !op.small) op.res = conv_res_plan(g, op.plan, groups);
-            pick_gemm_or_res(e, op, g, groups);
-        }
-        e.conv_ops.push_back(&op);
-    };
-    auto bind_wgrad = [&](WgradOp& op, const stcd_conv_geom& g, int conv, int tap0, int kreal, int nreal, int64_t in_off,
-                          int64_t dout_off) {
-        op.g = g; op.conv = conv; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.in_off = in_off; op.dout_off = dout_off; op.grouped = false;
-        op.plan = WgradMfmaPlan(); op.slab = -1; op.stage = 0;
-        if (e.dt == BF16) op.plan = pick_wgrad_plan(e, g, e.convs[conv].fwd.kpad, e.convs[conv].fwd.wld);
-        e.wgrad_ops.push_back(&op);
-    };
+    const Binder bind{e, ws};
     for (auto& b : e.sn_blocks) {
         const ConvW& c1 = e.convs[b.c1];
         const ConvW& c2 = e.convs[b.c2];
-        bind_conv(b.f1, geom3(b.N, b.H, b.W, b.Cin, b.in.ld, b.C, b.Y1.ld), b.c1, false, 0, c1.cin, b.C, b.groups);
-        bind_wgrad(b.w1, geom3(b.N, b.H, b.W, b.Cin, b.in.ld, b.C, b.dA1.ld), b.c1, 0, c1.cin, b.C, b.in.off, b.dA1.off);
-        if (b.dIn.off >= 0) bind_conv(b.d1, geom3(b.N, b.H, b.W, c1.dgrad.kpad, b.dA1.ld, c1.cin, b.dIn.ld), b.c1, true, 0, b.C, c1.cin);
-        bind_conv(b.f2, geom3(b.N, b.H, b.W, b.C, b.A1.ld, b.C, b.Y2.ld), b.c2, false, 0, b.C, b.C, b.groups);
-        bind_wgrad(b.w2, geom3(b.N, b.H, b.W, b.C, b.A1.ld, b.C, b.dOut.ld), b.c2, 0, b.C, b.C, b.A1.off, b.dOut.off);
-        bind_conv(b.d2, geom3(b.N, b.H, b.W, c2.dgrad.kpad, b.dOut.ld, b.C, b.dA1.ld), b.c2, true, 0, b.C, b.C);
+        bind.conv(b.f1, geom3(b.N, b.H, b.W, b.Cin, b.in.ld, b.C, b.Y1.ld), b.c1, false, 0, c1.cin, b.C, b.groups);
+        bind.wgrad(b.w1, geom3(b.N, b.H, b.W, b.Cin, b.in.ld, b.C, b.dA1.ld), b.c1, b.in.off, b.dA1.off);
+        if (b.dIn.off >= 0) bind.conv(b.d1, geom3(b.N, b.H, b.W, c1.dgrad.kpad, b.dA1.ld, c1.cin, b.dIn.ld), b.c1, true, 0, b.C, c1.cin);
+        bind.conv(b.f2, geom3(b.N, b.H, b.W, b.C, b.A1.ld, b.C, b.Y2.ld), b.c2, false, 0, b.C, b.C, b.groups);
+        bind.wgrad(b.w2, geom3(b.N, b.H, b.W, b.C, b.A1.ld, b.C, b.dOut.ld), b.c2, b.A1.off, b.dOut.off);
+        bind.conv(b.d2, geom3(b.N, b.H, b.W, c2.dgrad.kpad, b.dOut.ld, b.C, b.dA1.ld), b.c2, true, 0, b.C, b.C);
     }
     for (auto& u : e.sn_ups) {
         if (u.N == 0) continue;
@@ -2075,8 +2120,8 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
             g.ho = 2 * u.h; g.wo = 2 * u.w; g.out_stride = 2; g.oy0 = ph >> 1; g.ox0 = ph & 1;
             g.co = u.C; g.ldo = u.out.ld;
             g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0;
-            bind_conv(u.fwd[ph], g, u.conv, false, ph, u.C, u.C);
-            bind_wgrad(u.wg[ph], g, u.conv, ph, u.C, u.C, u.src.off, u.dOut.off);
+            bind.conv(u.fwd[ph], g, u.conv, false, ph, u.C, u.C);
+            bind.wgrad(u.wg[ph], g, u.conv, u.src.off, u.dOut.off, 0, ph);
         }
         stcd_conv_geom gd;
         memset(&gd, 0, sizeof(gd));
@@ -2086,13 +2131,13 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         gd.co = u.C; gd.ldo = u.tmp.ld;
         gd.ntaps = 4;
         for (int t = 0; t < 4; ++t) { gd.dy[t] = (int8_t)(t >> 1); gd.dx[t] = (int8_t)(t & 1); }
-        bind_conv(u.dgr, gd, u.conv, true, 0, u.C, u.C);
+        bind.conv(u.dgr, gd, u.conv, true, 0, u.C, u.C);
     }
     if (!conc) {
         const ConvW& cv = e.convs[e.sn_final];
-        bind_conv(e.sn_final_fwd, geom1(B, H, W, c4, e.snZ.ld, e.label, e.label), e.sn_final, false, 0, c4, e.label);
-        bind_wgrad(e.sn_final_wg, geom1(B, H, W, c4, e.snZ.ld, e.label, 8), e.sn_final, 0, c4, e.label, e.snZ.off, e.G.off);
-        bind_conv(e.sn_final_dgr, geom1(B, H, W, cv.dgrad.kpad, 8, c4, e.sndZ.ld), e.sn_final, true, 0, e.label, c4);
+        bind.conv(e.sn_final_fwd, geom1(B, H, W, c4, e.snZ.ld, e.label, e.label), e.sn_final, false, 0, c4, e.label);
+        bind.wgrad(e.sn_final_wg, geom1(B, H, W, c4, e.snZ.ld, e.label, 8), e.sn_final, e.snZ.off, e.G.off);
+        bind.conv(e.sn_final_dgr, geom1(B, H, W, cv.dgrad.kpad, 8, c4, e.sndZ.ld), e.sn_final, true, 0, e.label, c4);
     }
     e.slab = ws.take(e.slab_floats * 4);
     // bias gradients of the transposed convs: summed by the consumer block's conv1 data gradient (see configure_fcsiam)
@@ -2660,37 +2705,9 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     e.zero_end = ws.cur;
     e.scratch8 = ws.take(256);
     e.masks = ws.take(256);
-    for (auto& c : e.convs) {
-        c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
-        if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
-    }
-    e.dwe_begin = ws.cur;
-    for (auto& c : e.convs) {
-        c.dwe_floats = (int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld;
-        c.dwe = ws.take(c.dwe_floats * 8);
-    }
-    e.dwe_end = ws.cur;
+    take_ref_images(e, ws);
     // ---- bind every conv-shaped launch
-    auto bind_conv = [&](ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) {
-        op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.plan = ConvMfmaPlan(); op.wf = -1; op.small = false; op.res = ConvResPlan(); op.res_groups = groups;
-        if (e.dt == BF16) {
-            op.plan = conv_mfma_plan(g);
-            if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
-            op.small = conv_small_ok(g, op.plan);
-            if (e.use_res && !op.small) op.res = conv_res_plan(g, op.plan, groups);
-            pick_gemm_or_res(e, op, g, groups);
-        }
-        e.conv_ops.push_back(&op);
-    };
-    auto bind_wgrad = [&](WgradOp& op, const stcd_conv_geom& g, int conv, int64_t in_off, int64_t dout_off, int tap0 = 0, int wi_valid = 0) {
-        const ConvW& cv = e.convs[conv];
-        op.g = g; op.conv = conv; op.tap0 = tap0; op.kreal = cv.cin; op.nreal = cv.cout;
-        op.in_off = in_off; op.dout_off = dout_off; op.grouped = false;
-        op.plan = WgradMfmaPlan(); op.slab = -1; op.stage = 0;
-        if (e.dt == BF16) { op.plan = pick_wgrad_plan(e, g, cv.fwd.kpad, cv.fwd.wld); op.plan.wi_valid = wi_valid; }
-        e.wgrad_ops.push_back(&op);
-    };
+    const Binder bind{e, ws};
     for (auto& L : e.g_layers) {
         if (L.kind == K_STEM7) {
             // 7x7 stride-2 weight gradient on the MFMA path: row 2y + ky - 3 lies in parity plane py = (ky + 1) & 1 at plane row
@@ -2707,12 +2724,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
                 gs.hm = L.Ho; gs.wm = L.Wo; gs.in_stride = 2; gs.ho = L.Ho; gs.wo = L.Wo; gs.out_stride = 1;
                 gs.co = e.convs[L.conv].cout; gs.ldo = L.Y.ld; gs.ntaps = 7;
                 for (int t = 0; t < 7; ++t) { gs.dy[t] = (int8_t)(t - 3); gs.dx[t] = -3; }
-                ConvOp& op = L.fwd;
-                op.g = gs; op.conv = L.conv; op.dgrad = false; op.tap0 = 0; op.kreal = e.convs[L.conv].cin; op.nreal = gs.co;
-                op.plan = conv_mfma_plan(gs); op.res_groups = L.groups;
-                op.gemm = (L.in.ld == 8 && gs.co % 64 == 0) ? conv_gemm_plan(gs, op.plan, L.groups) : ConvGemmPlan();
-                op.gemm.pix_chunks = 1;
-                if (op.gemm.ok) { op.wf = ws.take(op.plan.wf_elems * 2); e.conv_ops.push_back(&op); }
+                bind.stem(L.fwd, gs, L.conv, L.groups);
             }
             if (!(e.dt == BF16 && e.use_mfma && e.use_wgroup)) continue;
             const ConvW& cv = e.convs[L.conv];
@@ -2732,15 +2744,14 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
                     gw.n = L.N; gw.hi = L.Hi / 2; gw.wi = L.Wi; gw.ci = 8; gw.ldi = 2 * L.in.ld;
                     gw.hm = L.Ho; gw.wm = L.Wo; gw.in_stride = 1; gw.ho = L.Ho; gw.wo = L.Wo; gw.out_stride = 1;
                     gw.co = cv.cout; gw.ldo = L.dA.ld; gw.ntaps = nt;
-                    WgradOp& op = L.wg[nops];
+                    int8_t oky[9], okx[9];
                     for (int t = 0; t < nt; ++t) {
                         const int ky = taps[c0 + t].first, kx = taps[c0 + t].second;
                         gw.dy[t] = (int8_t)((ky - 3 - py) / 2); gw.dx[t] = (int8_t)((kx - 3 - px) / 2);
-                        op.oky[t] = (int8_t)ky; op.okx[t] = (int8_t)kx;
+                        oky[t] = (int8_t)ky; okx[t] = (int8_t)kx;
                     }
-                    bind_wgrad(op, gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, 0, L.Wi / 2);
-                    op.own_taps = true;
-                    all_ok = all_ok && op.plan.ok;
+                    bind.wgrad(L.wg[nops], gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, 0, 0, L.Wi / 2, oky, okx);
+                    all_ok = all_ok && L.wg[nops].plan.ok;
                     ++nops;
                 }
             }
@@ -2761,10 +2772,10 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             if (L.kind == K_CONV3_S2) { g.ntaps = 9; for (int t = 0; t < 9; ++t) { g.dy[t] = (int8_t)(cv.fwd.ky[t] - 1); g.dx[t] = (int8_t)(cv.fwd.kx[t] - 1); } }
             else { g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0; }
         }
-        bind_conv(L.fwd, g, L.conv, false, 0, cv.cin, cv.cout, L.groups);
+        bind.conv(L.fwd, g, L.conv, false, 0, cv.cin, cv.cout, L.groups);
         if (stride == 1) {
             stcd_conv_geom gw = g; gw.ldo = L.dA.ld;
-            bind_wgrad(L.wg[0], gw, L.conv, L.in.off, L.dA.off);
+            bind.wgrad(L.wg[0], gw, L.conv, L.in.off, L.dA.off);
             L.nwg = 1;
         } else {
             // stride 2: input pixel (2m + ky - 1, 2n + kx - 1) lies in parity plane (py, px) at plane coordinates (m + dy, n + dx),
@@ -2784,7 +2795,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
                     const int ky = L.kind == K_CONV3_S2 ? cv.fwd.ky[start[ph] + t] : 1, kx = L.kind == K_CONV3_S2 ? cv.fwd.kx[start[ph] + t] : 1;
                     gw.dy[t] = (int8_t)(ky == 0 ? -1 : 0); gw.dx[t] = (int8_t)(kx == 0 ? -1 : 0);
                 }
-                bind_wgrad(L.wg[ph], gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, start[ph], L.Wi / 2);
+                bind.wgrad(L.wg[ph], gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, 0, start[ph], L.Wi / 2);
             }
             L.nwg = nph;
         }
@@ -2792,7 +2803,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         if (stride == 1) {
             stcd_conv_geom gd = L.kind == K_CONV3 ? geom3(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld)
                                                   : geom1(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld);
-            bind_conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
+            bind.conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
             L.ndgr = 1;
         } else if (L.kind == K_CONV3_S2) {      // d(in)(2m+py, 2n+px) = sum_{dy<=py, dx<=px} dY(m+dy, n+dx) W[.][.][py+1-2dy][px+1-2dx]
             static const int start[4] = {0, 1, 3, 5};
@@ -2806,7 +2817,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
                 int t = 0;
                 for (int dy = 0; dy <= py; ++dy) for (int dx = 0; dx <= px; ++dx) { gd.dy[t] = (int8_t)dy; gd.dx[t] = (int8_t)dx; ++t; }
                 gd.ntaps = t;
-                bind_conv(L.dgr[ph], gd, L.conv, true, start[ph], cv.cout, cv.cin);
+                bind.conv(L.dgr[ph], gd, L.conv, true, start[ph], cv.cout, cv.cin);
             }
             L.ndgr = 4;
         } else {                                // 1x1 stride 2: only the even positions receive a gradient (the rest is zeroed)
@@ -2815,23 +2826,23 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             gd.n = L.N; gd.hi = L.Ho; gd.wi = L.Wo; gd.ci = cv.dgrad.kpad; gd.ldi = L.dA.ld;
             gd.hm = L.Ho; gd.wm = L.Wo; gd.in_stride = 1; gd.ho = L.Hi; gd.wo = L.Wi; gd.out_stride = 2;
             gd.co = cv.cin; gd.ldo = L.dIn.ld; gd.ntaps = 1;
-            bind_conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
+            bind.conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
             L.ndgr = 1;
         }
     }
     {
         const ConvW& cv = e.convs[e.g_head_conv];
         const int nhead = (D == 2 && !e.bres) ? 3 * B : B, hc = e.g_head_c;
-        bind_conv(e.g_head_fwd, geom3(nhead, H, W, hc, hc, e.label, e.label), e.g_head_conv, false, 0, hc, e.label);
-        bind_wgrad(e.g_head_wg, geom3(nhead, H, W, hc, hc, e.label, 8), e.g_head_conv, e.gX3.off, e.G.off);
-        bind_conv(e.g_head_dgr, geom3(nhead, H, W, cv.dgrad.kpad, 8, hc, hc), e.g_head_conv, true, 0, e.label, hc);
+        bind.conv(e.g_head_fwd, geom3(nhead, H, W, hc, hc, e.label, e.label), e.g_head_conv, false, 0, hc, e.label);
+        bind.wgrad(e.g_head_wg, geom3(nhead, H, W, hc, hc, e.label, 8), e.g_head_conv, e.gX3.off, e.G.off);
+        bind.conv(e.g_head_dgr, geom3(nhead, H, W, cv.dgrad.kpad, 8, hc, hc), e.g_head_conv, true, 0, e.label, hc);
     }
     for (const GStep& st : e.g_fwd) {
         if (st.kind != GS_BCONV) continue;
         const ConvW& cv = e.convs[e.g_pred_conv];
-        bind_conv(e.g_pred_fwd, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.dst.ld), e.g_pred_conv, false, 0, st.C, 32);
-        bind_wgrad(e.g_pred_wg, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.ddst.ld), e.g_pred_conv, st.src.off, st.ddst.off);
-        bind_conv(e.g_pred_dgr, geom3(st.N, st.h, st.w, cv.dgrad.kpad, st.ddst.ld, st.C, st.dsrc.ld), e.g_pred_conv, true, 0, 32, st.C);
+        bind.conv(e.g_pred_fwd, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.dst.ld), e.g_pred_conv, false, 0, st.C, 32);
+        bind.wgrad(e.g_pred_wg, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.ddst.ld), e.g_pred_conv, st.src.off, st.ddst.off);
+        bind.conv(e.g_pred_dgr, geom3(st.N, st.h, st.w, cv.dgrad.kpad, st.ddst.ld, st.C, st.dsrc.ld), e.g_pred_conv, true, 0, 32, st.C);
     }
     e.ws_tensors.clear();
     for (const auto& L : e.g_layers) {
@@ -2912,8 +2923,9 @@ static void glayer_forward(const Ctx& c, GLayer& L, float* bn_running, bool trai
     if (L.kind == K_STEM7 && mfma_on(e) && L.fwd.gemm.ok && L.fwd.wf >= 0) {
         ProfScope ps(c, PC_CONV, 2.0 * L.N * L.Ho * L.Wo * 49.0 * cv.cin * cv.cout, 0.0, "k_conv_gemm<stem>");
         long long* sp = training ? c.at<long long>(L.facc) : nullptr;
-        if (launch_conv_gemm(L.fwd.g, L.fwd.plan, L.fwd.gemm, c.at(L.in.off), c.at(L.fwd.wf), nullptr, c.at(L.Y.off), L.groups, sp, L.C, c.s) == 0)
-            fused = sp ? 1 : 0;
+        if (launch_conv_gemm(L.fwd.g, L.fwd.plan, L.fwd.gemm, c.at(L.in.off), c.at(L.fwd.wf), nullptr, c.at(L.Y.off), L.groups, sp, L.C, c.s) != 0)
+            set_error("internal: k_conv_gemm<stem> rejected the stem it was bound for");
+        fused = sp ? 1 : 0;
     } else if (L.kind == K_STEM7) {
         ProfScope ps(c, PC_CONV, 2.0 * L.N * L.Ho * L.Wo * 49.0 * cv.cin * cv.cout, 0.0, "k_stem_fwd");
         launch_stem_fwd(e.dt, c.at(L.in.off), c.params + cv.w_off, c.at(L.Y.off), L.N, L.Hi, L.Wi, cv.cin, cv.cout, c.s);
@@ -3137,6 +3149,7 @@ static void engine_env_switches(stcd_engine* e) {       // read at every stcd_cr
     e->use_small = !env_flag("STCD_NO_SMALL_KERNEL", false);
     e->use_gemm = !env_flag("STCD_NO_GEMM_KERNEL", false);
     e->use_res = !env_flag("STCD_NO_RES_KERNEL", false);
+    e->use_halo = env_flag("STCD_HALO_KERNEL", false);                      // 1: k_conv_halo where it fits (opt-in, pick_gemm_or_res)
     e->use_tile = !env_flag("STCD_NO_TILE_KERNEL", false);                  // 1: the small-map Ci % 64 == 0 layers of FC-Siam stay on k_conv_res
     e->use_wgroup = !env_flag("STCD_NO_WGRAD_GROUPS", false);
     e->use_act_fuse = !env_flag("STCD_NO_ACT_FUSE", false);
@@ -3688,25 +3701,29 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
             STCD_HIP(hipGetLastError());
             return 0;
         }
-        if (impl == 1 && conv_small_ok(*g, p)) {
-            STCD_CHECK(launch_conv_small(*g, in, scratch, bias, out, false, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0,
-                       "small-channel kernel rejected the geometry");
+        if (impl == 1) {
+            // the engine's plans and the engine's choice (one group, no statistics, no epilogue, NHWC) with a fresh engine's switches;
+            // the kernels with an impl number of their own (3 halo, 6 dma, 8 tile) stay behind those numbers
+            stcd_engine sw;
+            sw.dt = BF16;
+            engine_env_switches(&sw);
+            ConvOp op;
+            op.g = *g;
+            plan_conv(sw, op, 1, false);
+            op.wf = 0;      // (the image is `scratch`)
+            ConvCall call;
+            call.allowed = ~(conv_kernel_bit(ConvKernel::DMA) | conv_kernel_bit(ConvKernel::HALO) | conv_kernel_bit(ConvKernel::TILE));
+            int rc = 1;
+            switch (conv_kernel(true, sw.use_small, op, call)) {
+                case ConvKernel::SMALL: rc = launch_conv_small(*g, in, scratch, bias, out, false, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
+                case ConvKernel::RES: rc = launch_conv_res(*g, p, op.res, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
+                case ConvKernel::GEMM: rc = launch_conv_gemm(*g, p, op.gemm, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
+                case ConvKernel::MFMA: rc = launch_conv_mfma(*g, p, in, scratch, bias, out, false, (hipStream_t)hip_stream); break;
+                default: break;
+            }
+            STCD_CHECK(rc == 0, "the chosen kernel rejected the geometry");
             STCD_HIP(hipGetLastError());
             return 0;
-        }
-        if (impl == 1 && !env_flag("STCD_NO_RES_KERNEL", false)) {
-            const ConvResPlan rp = conv_res_plan(*g, p, 1);
-            if (rp.ok && launch_conv_res(*g, p, rp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0) {
-                STCD_HIP(hipGetLastError());
-                return 0;
-            }
-        }
-        if (impl == 1 && !env_flag("STCD_NO_GEMM_KERNEL", false)) {
-            const ConvGemmPlan gp = conv_gemm_plan(*g, p, 1);
-            if (gp.ok && launch_conv_gemm(*g, p, gp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0) {
-                STCD_HIP(hipGetLastError());
-                return 0;
-            }
         }
         STCD_CHECK(launch_conv_mfma(*g, p, in, scratch, bias, out, false, (hipStream_t)hip_stream) == 0, "LDS budget exceeded");
         STCD_HIP(hipGetLastError());

@@ -264,42 +264,23 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
         P.cj_blocks[stage] += j.nblocks; P.cj_fin[stage] += (C + 7) / 8; cpart_floats[stage] += (int64_t)j.nblocks * C;
         P.cjobs[stage].push_back(j);
     };
-    auto bind_conv = [&](ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) {
-        op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal;
-        op.plan = ConvMfmaPlan(); op.wf = -1; op.small = false; op.res = ConvResPlan(); op.res_groups = groups; op.gemm = ConvGemmPlan();
-        if (e.dt == BF16) {
-            op.plan = conv_mfma_plan(g);
-            if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
-            op.small = conv_small_ok(g, op.plan);
-            if (e.use_res && !op.small) op.res = conv_res_plan(g, op.plan, groups);
-            pick_gemm_or_res(e, op, g, groups);
-        }
-        e.conv_ops.push_back(&op);
-    };
-    auto bind_wgrad = [&](WgradOp& op, const stcd_conv_geom& g, int conv, int64_t in_off, int64_t dout_off, int stage, int tap0 = 0) {
-        const ConvW& cv = e.convs[conv];
-        op.g = g; op.conv = conv; op.tap0 = tap0; op.kreal = cv.cin; op.nreal = cv.cout;
-        op.in_off = in_off; op.dout_off = dout_off; op.grouped = false; op.own_taps = false;
-        op.plan = WgradMfmaPlan(); op.slab = -1; op.stage = stage;
-        if (e.dt == BF16) op.plan = pick_wgrad_plan(e, g, cv.fwd.kpad, cv.fwd.wld);
-        e.wgrad_ops.push_back(&op);
-    };
+    const Binder bind{e, ws};
     // a 1x1-geometry GEMM over an [n, h, w, K] map (x.ld may exceed K: a slice)
     auto bind_linear = [&](CfGemm& G, const TRef& x, const TRef& dx, int n, int h, int w, const TRef& y, const TRef& dy, int stage, bool bias_grad = true) {
         const ConvW& cv = e.convs[G.conv];
         G.x = x; G.y = y; G.dy = dy; G.dx = dx; G.has_dgr = dx.off >= 0 && cv.dgrad.ntaps > 0;
         if (bias_grad && cv.b_off >= 0) add_colsum(stage, dy, (int64_t)n * h * w, cv.cout, cv.b_off);
-        bind_conv(G.fwd, geom1(n, h, w, cv.kin_p, x.ld, cv.cout, y.ld), G.conv, false, 0, cv.cin, cv.cout);
-        bind_wgrad(G.wg, geom1(n, h, w, cv.kin_p, x.ld, cv.cout, dy.ld), G.conv, x.off, dy.off, stage);
-        if (G.has_dgr) bind_conv(G.dgr, geom1(n, h, w, cv.dgrad.kpad, dy.ld, cv.cin, dx.ld), G.conv, true, 0, cv.cout, cv.cin);
+        bind.conv(G.fwd, geom1(n, h, w, cv.kin_p, x.ld, cv.cout, y.ld), G.conv, false, 0, cv.cin, cv.cout);
+        bind.wgrad(G.wg, geom1(n, h, w, cv.kin_p, x.ld, cv.cout, dy.ld), G.conv, x.off, dy.off, stage);
+        if (G.has_dgr) bind.conv(G.dgr, geom1(n, h, w, cv.dgrad.kpad, dy.ld, cv.cin, dx.ld), G.conv, true, 0, cv.cout, cv.cin);
     };
-    auto bind_conv3 = [&](CfGemm& G, const TRef& x, const TRef& dx, int K, int n, int h, int w, const TRef& y, const TRef& dy, int stage) {
+    auto bind_3x3 = [&](CfGemm& G, const TRef& x, const TRef& dx, int K, int n, int h, int w, const TRef& y, const TRef& dy, int stage) {
         const ConvW& cv = e.convs[G.conv];
         G.x = x; G.y = y; G.dy = dy; G.dx = dx; G.has_dgr = dx.off >= 0;
         if (cv.b_off >= 0) add_colsum(stage, dy, (int64_t)n * h * w, cv.cout, cv.b_off);
-        bind_conv(G.fwd, geom3(n, h, w, K, x.ld, cv.cout, y.ld), G.conv, false, 0, cv.cin, cv.cout);
-        bind_wgrad(G.wg, geom3(n, h, w, K, x.ld, cv.cout, dy.ld), G.conv, x.off, dy.off, stage);
-        if (G.has_dgr) bind_conv(G.dgr, geom3(n, h, w, cv.dgrad.kpad, dy.ld, cv.cin, dx.ld), G.conv, true, 0, cv.cout, cv.cin);
+        bind.conv(G.fwd, geom3(n, h, w, K, x.ld, cv.cout, y.ld), G.conv, false, 0, cv.cin, cv.cout);
+        bind.wgrad(G.wg, geom3(n, h, w, K, x.ld, cv.cout, dy.ld), G.conv, x.off, dy.off, stage);
+        if (G.has_dgr) bind.conv(G.dgr, geom3(n, h, w, cv.dgrad.kpad, dy.ld, cv.cin, dx.ld), G.conv, true, 0, cv.cout, cv.cin);
     };
     auto add_site = [&](const std::string& name, std::initializer_list<int> dims, float p) {
         CfPlan::Site s; s.name = name; s.p = p; s.nd = 0;
@@ -401,9 +382,9 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
         bind_linear(F.lin, S.out.v, S.out.g, N2, F.h, F.w, F.lo.v, F.lo.g, 0);
         F.cat = mk(B, F.h, F.w, 2 * D);
         F.ya = mk(B, F.h, F.w, D); F.za = mk(B, F.h, F.w, D); F.ba = mk(B, F.h, F.w, D); F.aa = mk(B, F.h, F.w, D);
-        bind_conv3(F.ca, F.cat.v, F.cat.g, 2 * D, B, F.h, F.w, F.ya.v, F.ya.g, 0);
+        bind_3x3(F.ca, F.cat.v, F.cat.g, 2 * D, B, F.h, F.w, F.ya.v, F.ya.g, 0);
         F.yb = mk(B, F.h, F.w, D); F.zb = mk(B, F.h, F.w, D); F.bb = mk(B, F.h, F.w, D);
-        bind_conv3(F.cb, F.aa.v, F.aa.g, D, B, F.h, F.w, F.yb.v, F.yb.g, 0);
+        bind_3x3(F.cb, F.aa.v, F.aa.g, D, B, F.h, F.w, F.yb.v, F.yb.g, 0);
         if (F.s == 1) {       // c1 lives in the last channel slice of the fusion concat (cat((_c4_up, _c3_up, _c2_up, _c1)) :1609)
             F.c.n = B; F.c.h = F.h; F.c.w = F.w; F.c.c = D;
             F.c.v = P.fcat.v; F.c.v.off += (int64_t)3 * D * T; F.c.g = P.fcat.g; F.c.g.off += (int64_t)3 * D * T;
@@ -414,7 +395,7 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
         // auxiliary head: conv(D -> label) straight to fp32 NCHW, then ReLU - BN - conv on the small maps
         F.aux_y = ws.take((int64_t)B * e.label * F.h * F.w * 4);
         F.aux_stat = ws.take(64 * 4);
-        bind_conv(F.aux_fwd, geom3(B, F.h, F.w, D, F.c.v.ld, e.label, e.label), F.aux_conv0, false, 0, D, e.label);
+        bind.conv(F.aux_fwd, geom3(B, F.h, F.w, D, F.c.v.ld, e.label, e.label), F.aux_conv0, false, 0, D, e.label);
         if (P.aux_bwd) {       // backward of the head: planned only with stcd_cf_set_aux_backward (multi_scale_train)
             const ConvW& cv0 = e.convs[F.aux_conv0];
             F.aux_dz = ws.take((int64_t)B * e.label * F.h * F.w * 4); F.aux_dy = ws.take((int64_t)B * e.label * F.h * F.w * 4);
@@ -446,8 +427,8 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
             g.n = B; g.hi = h; g.wi = w; g.ci = D; g.ldi = in.v.ld; g.hm = h; g.wm = w; g.in_stride = 1;
             g.ho = 2 * h; g.wo = 2 * w; g.out_stride = 2; g.oy0 = py; g.ox0 = px; g.co = D; g.ldo = D; g.ntaps = 4;
             for (int t = 0; t < 4; ++t) { g.dy[t] = (int8_t)((py + 1 - cv.fwd.ky[t]) / 2); g.dx[t] = (int8_t)((px + 1 - cv.fwd.kx[t]) / 2); }
-            bind_conv(U.fwd[ph], g, U.conv[ph], false, 0, D, D);
-            bind_wgrad(U.wg[ph], g, U.conv[ph], in.v.off, U.out.g.off, 0);
+            bind.conv(U.fwd[ph], g, U.conv[ph], false, 0, D, D);
+            bind.wgrad(U.wg[ph], g, U.conv[ph], in.v.off, U.out.g.off, 0);
         }
         for (int k = 0; k < 2; ++k) {
             const ConvW& cv = e.convs[U.conv[k]];
@@ -456,15 +437,15 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
             g.n = B; g.hi = 2 * h; g.wi = 2 * w; g.ci = cv.dgrad.kpad; g.ldi = D; g.hm = h; g.wm = w; g.in_stride = 2;
             g.ho = h; g.wo = w; g.out_stride = 1; g.co = D; g.ldo = D; g.ntaps = 8;
             for (int t = 0; t < 8; ++t) { g.dy[t] = (int8_t)(cv.dgrad.ky[t] - 1); g.dx[t] = (int8_t)(cv.dgrad.kx[t] - 1); }
-            bind_conv(U.dgr[k], g, U.conv[k], true, 0, D, D);
+            bind.conv(U.dgr[k], g, U.conv[k], true, 0, D, D);
         }
     };
     auto bind_res = [&](CfRes& R, const CfT& x, int h, int w) {
         R.x = x;
         R.r1 = mk(B, h, w, D); R.y2 = mk(B, h, w, D); R.out = mk(B, h, w, D);
         R.dtmp = TRef(); R.dtmp.off = ws.take((int64_t)B * h * w * D * T); R.dtmp.ld = D;
-        bind_conv3(R.c1, x.v, R.dtmp, D, B, h, w, R.r1.v, R.r1.g, 0);
-        bind_conv3(R.c2, R.r1.v, R.r1.g, D, B, h, w, R.y2.v, R.y2.g, 0);
+        bind_3x3(R.c1, x.v, R.dtmp, D, B, h, w, R.r1.v, R.r1.g, 0);
+        bind_3x3(R.c2, R.r1.v, R.r1.g, D, B, h, w, R.y2.v, R.y2.g, 0);
     };
     bind_up(P.up2, P.fa, h1, w1);
     bind_res(P.res2, P.up2.out, 2 * h1, 2 * w1);
@@ -476,9 +457,9 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
     e.G = TRef(); e.G.off = ws.take((int64_t)B * H * W * 8 * T); e.G.ld = 8;
     {
         const ConvW& cv = e.convs[P.head_conv];
-        bind_conv(P.head_fwd, geom3(B, H, W, D, D, e.label, e.label), P.head_conv, false, 0, D, e.label);
-        bind_wgrad(P.head_wg, geom3(B, H, W, D, D, e.label, 8), P.head_conv, P.res1.out.v.off, e.G.off, 0);
-        bind_conv(P.head_dgr, geom3(B, H, W, cv.dgrad.kpad, 8, D, D), P.head_conv, true, 0, e.label, D);
+        bind.conv(P.head_fwd, geom3(B, H, W, D, D, e.label, e.label), P.head_conv, false, 0, D, e.label);
+        bind.wgrad(P.head_wg, geom3(B, H, W, D, D, e.label, 8), P.head_conv, P.res1.out.v.off, e.G.off, 0);
+        bind.conv(P.head_dgr, geom3(B, H, W, cv.dgrad.kpad, 8, D, D), P.head_conv, true, 0, e.label, D);
     }
     // ---- zero arena (BatchNorm accumulators, the head's bias accumulator): one memset per training forward
     e.zero_begin = ws.cur;
@@ -491,24 +472,15 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
     for (CfDiff* Fp : aux_pending) {       // (bound OUTSIDE the arena: bind_conv carves the launch's fragment-order filter image from `ws`)
         CfDiff& F = *Fp;
         const ConvW& cv0 = e.convs[F.aux_conv0];
-        bind_wgrad(F.aux_wg, geom3(B, F.h, F.w, D, F.c.v.ld, e.label, 8), F.aux_conv0, F.c.v.off, F.aux_G, 0);
-        bind_conv(F.aux_dgr, geom3(B, F.h, F.w, cv0.dgrad.kpad, 8, D, D), F.aux_conv0, true, 0, e.label, D);
+        bind.wgrad(F.aux_wg, geom3(B, F.h, F.w, D, F.c.v.ld, e.label, 8), F.aux_conv0, F.c.v.off, F.aux_G, 0);
+        bind.conv(F.aux_dgr, geom3(B, F.h, F.w, cv0.dgrad.kpad, 8, D, D), F.aux_conv0, true, 0, e.label, D);
     }
     e.scratch8 = ws.take(256);
     e.masks = ws.take(256);
     P.scratch_floats = scratch_floats; P.scratch = ws.take(scratch_floats * 4);
     P.cpart_off = ws.take(std::max(cpart_floats[0], cpart_floats[1]) * 4 + 16);
     for (int st = 0; st < 2; ++st) P.cjobs_off[st] = ws.take((int64_t)P.cjobs[st].size() * sizeof(ColsumJob) + 16);
-    for (auto& c : e.convs) {
-        c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
-        if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
-    }
-    e.dwe_begin = ws.cur;
-    for (auto& c : e.convs) {
-        c.dwe_floats = (int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld;
-        c.dwe = (e.dt == BF16 && e.use_mfma) ? -1 : ws.take(c.dwe_floats * 8);      // fp64 accumulators of the reference weight-gradient path only
-    }
-    e.dwe_end = ws.cur;
+    take_ref_images(e, ws, !(e.dt == BF16 && e.use_mfma));      // (fp64 accumulators: the reference weight-gradient path only)
     e.slab = ws.take(e.slab_floats * 4);
     e.bias_jobs.clear();
     {

@@ -258,6 +258,16 @@ static void taps_extent(const stcd_conv_geom& g, int* dymin, int* dymax, int* dx
     }
 }
 
+// LDS bytes of a k_conv_mfma block: one halo of a CiB-channel chunk + two filter buffers
+static size_t conv_mfma_lds(const stcd_conv_geom& g, const ConvMfmaPlan& p) {
+    int dymin, dymax, dxmin, dxmax;
+    taps_extent(g, &dymin, &dymax, &dxmin, &dxmax);
+    const int HH = 7 * g.in_stride + (dymax - dymin) + 1, HWp = 15 * g.in_stride + (dxmax - dxmin) + 1;
+    const int halo_bytes = (HH * HWp * p.CiB * 2 + 255) & ~255;
+    const int wbuf_bytes = p.modeB ? ((p.KS * p.NT * 1024 + 1) / 2 + 255) & ~255 : (p.KS * p.NT * 1024 + 255) & ~255;
+    return (size_t)halo_bytes + 2 * (size_t)wbuf_bytes + 128;
+}
+
 ConvMfmaPlan conv_mfma_plan(const stcd_conv_geom& g) {
     ConvMfmaPlan p;
     const int Ci = g.ci;
@@ -275,7 +285,9 @@ ConvMfmaPlan conv_mfma_plan(const stcd_conv_geom& g) {
     }
     p.NTtot = ((p.NTtot + p.NT - 1) / p.NT) * p.NT;     // pad the n-tiles to whole blocks
     p.wf_elems = p.modeB ? (int64_t)p.KS * p.NTtot * 512 : (int64_t)p.nchunks * g.ntaps * p.KS * p.NTtot * 512;
-    p.ok = (Ci % 8 == 0) && (p.modeB ? (Ci <= 64 && p.KS <= 24) : true) && g.ldi % 8 == 0;
+    // (the last term: k_conv_mfma is every planned launch's last resort, so a plan it cannot stage is no plan -- the launch then
+    //  runs on the reference kernel, whose fp32 filter image is packed exactly for the launches without a plan)
+    p.ok = (Ci % 8 == 0) && (p.modeB ? (Ci <= 64 && p.KS <= 24) : true) && g.ldi % 8 == 0 && conv_mfma_lds(g, p) <= 160 * 1024;
     return p;
 }
 
@@ -397,14 +409,14 @@ static size_t conv_mfma_args(const stcd_conv_geom& g, const ConvMfmaPlan& p, con
     a.halo_bytes = (a.HH * a.HWp * p.CiB * 2 + 255) & ~255;
     a.wbuf_bytes = p.modeB ? ((p.KS * p.NT * 1024 + 1) / 2 + 255) & ~255 : (p.KS * p.NT * 1024 + 255) & ~255;
     fill_taps(g, a.tap);
-    return (size_t)a.halo_bytes + 2 * (size_t)a.wbuf_bytes + 128;
+    return conv_mfma_lds(g, p);
 }
 
 int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const void* in, const void* wf, const float* bias,
                      void* out, bool out_nchw, hipStream_t s) {
     ConvMfmaArgs a;
     const size_t lds = conv_mfma_args(g, p, in, wf, bias, out, out_nchw, a);
-    if (lds > 160 * 1024) return 1;
+    if (lds > 160 * 1024) return 1;      // (conv_mfma_plan)
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * g.n), (unsigned)(p.NTtot / p.NT));
 #define LAUNCH_NT(N_)                                                                                             \
     do {                                                                                                          \
@@ -425,17 +437,20 @@ int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const void*
     return 0;
 }
 
-// 0 = launched; 1 = the four phases do not share a launch shape (caller falls back to four launches)
+// the four phases share a launch shape (else the caller runs four launches)
+bool conv_mfma_x4_ok(const stcd_conv_geom g[4], const ConvMfmaPlan p[4]) {
+    for (int k = 0; k < 4; ++k)
+        if (!p[k].ok || p[k].NT != p[0].NT || p[k].NTtot != p[0].NTtot || g[k].n != g[0].n || g[k].hm != g[0].hm || g[k].wm != g[0].wm)
+            return false;
+    return true;
+}
 int launch_conv_mfma_x4(const stcd_conv_geom g[4], const ConvMfmaPlan p[4], const void* in, const void* const wf[4],
                         const float* bias, void* out, hipStream_t s) {
+    if (!conv_mfma_x4_ok(g, p)) return 1;
     ConvMfmaArgs4 j;
     size_t lds = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (!p[k].ok || p[k].NT != p[0].NT || p[k].NTtot != p[0].NTtot || g[k].n != g[0].n || g[k].hm != g[0].hm || g[k].wm != g[0].wm)
-            return 1;
-        lds = std::max(lds, conv_mfma_args(g[k], p[k], in, wf[k], bias, out, false, j.a[k]));
-    }
-    if (lds > 160 * 1024) return 1;
+    for (int k = 0; k < 4; ++k) lds = std::max(lds, conv_mfma_args(g[k], p[k], in, wf[k], bias, out, false, j.a[k]));
+    if (lds > 160 * 1024) return 1;      // (conv_mfma_plan)
     dim3 grid((unsigned)(j.a[0].tiles_x * j.a[0].tiles_y * g[0].n), (unsigned)(p[0].NTtot / p[0].NT), 4);
 #define LAUNCH_X4(N_)                                                                                             \
     do {                                                                                                          \
@@ -1388,6 +1403,11 @@ bool conv_small_bwdsum_ok(const stcd_conv_geom& g) {
     return g.co == 16 && g.hm % 8 == 0 && g.wm % 16 == 0 && g.hm == g.ho && g.wm == g.wo && g.out_stride == 1 && g.oy0 == 0 && g.ox0 == 0 &&
            (ks == 3 || ks == 5);
 }
+// what a CALL adds to conv_small_ok: whole images per tile group, and a virtual input of the launch's own channels and groups
+bool conv_small_call_ok(const stcd_conv_geom& g, int groups, const XfSrc* xf) {
+    if (groups < 1 || g.n % groups != 0) return false;
+    return !(xf && xf->on) || (xf->C == g.ci && xf->groups == groups);
+}
 int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_modeB, const float* bias, void* out,
                       bool out_nchw, int groups, long long* stat_acc, int cpad, hipStream_t s, const XfSrc* xf, const BwdSum* bs) {
     ConvSmallArgs a;
@@ -1410,12 +1430,11 @@ int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_mo
     a.stat_acc = stat_acc;
     a.cpad = cpad;
     fill_taps(g, a.tap);
-    if (g.n % groups != 0) return 1;
+    if (!conv_small_call_ok(g, groups, xf)) return 1;
     const int blocks = conv_small_blocks(g, groups);
     size_t lds = std::max<size_t>(2 * (size_t)a.halo_bytes, 4 * 2 * 16 * 2 * 4 * 2);
     const bool use_xf = xf && xf->on;
     if (use_xf) {
-        if (xf->C != g.ci || xf->groups != groups) return 1;
         a.xf = *xf;
         lds = 2 * (size_t)a.halo_bytes + (size_t)xf->groups * 2 * xf->C * 4;
     }
@@ -1913,6 +1932,12 @@ ConvResPlan conv_res_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int gr
 bool conv_res_bwdsum_ok(const stcd_conv_geom& g, const ConvResPlan& rp) {
     return rp.ok && !rp.single_halo && rp.NT <= 2 && g.co % (rp.NT * 16) == 0 && g.out_stride == 1 && g.oy0 == 0 && g.ox0 == 0;
 }
+// a virtual input on this plan: there is an XF instantiation (none of the single-halo variant), the producer's channels and groups
+// are the launch's, and its scale / shift table fits beside the plan's LDS
+bool conv_res_xf_ok(const stcd_conv_geom& g, const ConvResPlan& rp, int groups, const XfSrc& xf) {
+    return rp.ok && !rp.single_halo && xf.C == g.ci && xf.groups == groups &&
+           (size_t)rp.lds_bytes + (size_t)xf.groups * 2 * xf.C * 4 <= 160 * 1024;
+}
 int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvResPlan& rp, const void* in, const void* wf,
                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0, float s1_scale,
                     float s2_scale, const XfSrc* xf, const BwdSum* bs) {
@@ -1936,10 +1961,9 @@ int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvRe
     const bool use_xf = xf && xf->on;
     size_t lds = (size_t)rp.lds_bytes;
     if (use_xf) {
-        if (rp.single_halo || xf->C != g.ci || xf->groups != groups) return 1;     // (the single-halo variant has no XF instantiation)
+        if (!conv_res_xf_ok(g, rp, groups, *xf)) return 1;
         a.xf = *xf;
         lds += (size_t)xf->groups * 2 * xf->C * 4;
-        if (lds > 160 * 1024) return 1;
     }
 #define LAUNCH_RES_V(N_, W_, P_, X_)                                                                              \
     do {                                                                                                          \
