@@ -363,7 +363,7 @@ int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height
  * [classes,height,width] and wsum fp32 [height,width], both zeroed by the caller before the first call.  window: nullable
  * fp32 [T] (NULL = all ones); pixel weight w = window[ty] * window[tx]; tile pixels outside the scene are dropped.
  * A gather over scene pixels, without float atomics: each pixel adds its covering tiles of this call in ASCENDING tile index,
- * acc = fmaf(w, logit, acc), wsum += w.  Hence the same inputs give the same bits on every run, and acc / wsum do not depend
+ * acc = fmaf(w, logit, acc), wsum += w (as one fused multiply-add of the two window factors: the product is not rounded first).  Hence the same inputs give the same bits on every run, and acc / wsum do not depend
  * on how the tiles were split into calls as long as the calls come in ascending first_tile. */
 int stcd_scene_stitch(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
                       int first_tile, int n_tiles, const float* window, float* acc, float* wsum, void* hip_stream);
@@ -397,6 +397,37 @@ int stcd_scene_gather_d4(const uint8_t* scene_a, const uint8_t* scene_b, int hei
                          void* hip_stream);
 int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
                          int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, void* hip_stream);
+/* ---- whole scenes for the models the reference's scripts train: UnetSeg (one image in, train_sup.py:303) and SegCD, whose forward
+ *      returns (mask_t1, mask_t2, change) (decoders/unet/model.py:316-332).  Grid, views and checks are those of the entries above. */
+/* One scene: x fp32 [n_tiles,3,T,T] is bit-equal to the x1 that stcd_scene_gather_d4(scene, scene, ...) writes (same reflection,
+ * same value arithmetic, same views) without reading a second scene or writing a second batch. */
+int stcd_scene_gather_one_d4(const uint8_t* scene, int height, int width, int tile, int stride, int tiles_x, int first_tile,
+                             int n_tiles, const float* mean3, const float* std3, float* x, int d4, void* hip_stream);
+/* Several heads of one forward in one launch.  logits: HOST array of n_heads device pointers (1 <= n_heads <= STCD_SCENE_MAX_HEADS;
+ * the kernel takes them by value, as stcd_selftrain_score takes its models), each fp32 [n_tiles,classes,T,T], classes 1 or 2.
+ * acc: fp32 [n_heads*classes,height,width], head h in planes h*classes ..; ONE wsum fp32 [height,width].  For every head the
+ * planes of acc, and wsum, are bit-equal to what stcd_scene_stitch_d4 leaves when called on that head alone with its own acc and
+ * wsum: ascending tile order per pixel, the same fmaf chain, upright weights, for all eight views and any split of the tiles
+ * into calls.  The covering tiles, the window weight and the read-modify-write of wsum are worked out once per pixel, not once
+ * per head; the transposing views stage one head at a time, so LDS does not grow with n_heads.  No float atomics. */
+#define STCD_SCENE_MAX_HEADS 3
+int stcd_scene_stitch_heads_d4(const float* const* logits, int n_heads, int classes, int height, int width, int tile, int stride,
+                               int tiles_x, int tiles_y, int first_tile, int n_tiles, const float* window, float* acc, float* wsum,
+                               int d4, void* hip_stream);
+/* stcd_scene_finalize for SegCD's three stitched heads in one pass: acc fp32 [3*classes,height,width] in the forward's order
+ * (t1, t2, change) over one wsum.  seg_a, seg_b, change: uint8 [height,width], each bit-equal to stcd_scene_finalize on that head
+ * (classes == 2: acc[1] > acc[0], a tie is class 0; classes == 1: acc > threshold * wsum with seg_threshold for the two building
+ * maps and change_threshold for the change map; NaN is class 0).  gated: nullable uint8 [height,width],
+ * change & (seg_a != seg_b): the decision-level gate min(|pred_B - pred_A|, change_prediction) sketched in train_stcd.py:170-176.
+ * prob: nullable fp32 [3,height,width], each plane bit-equal to that entry's prob.  label_a, label_b, label_c: each nullable
+ * uint8 [height,width] (>= 1 is set, 255 is ignored).  cm: int64 [4][4] on the device, ADDED to; row 0 seg_a vs label_a, row 1
+ * seg_b vs label_b, row 2 change vs label_c, row 3 gated vs label_c, each cm[row][2*label+pred]; required iff any label is given.
+ * The row of an absent label is left untouched, and so is row 3 when gated is NULL.  Counts are integers, reduced per wave and
+ * block before one 64-bit integer atomic per block and counter.  One pass: 3*classes + 1 fp32 planes in, 3 or 4 bytes a pixel out. */
+int stcd_scene_finalize_seg(const float* acc, const float* wsum, int classes, int height, int width, float seg_threshold,
+                            float change_threshold, const uint8_t* label_a, const uint8_t* label_b, const uint8_t* label_c,
+                            uint8_t* seg_a, uint8_t* seg_b, uint8_t* change, uint8_t* gated, float* prob, int64_t* cm,
+                            void* hip_stream);
 
 /* ---- the self-training round: K checkpoints of one network score the same pairs.  Replaces, per pair and checkpoint, the sigmoid,
  *      the compare, the .int(), the .cpu() and the host bincount of train_stcd.py:111-125 (reliability split) and :155-177

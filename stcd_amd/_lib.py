@@ -143,6 +143,9 @@ _PROTOS = {
     "stcd_scene_finalize": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "stcd_scene_gather_d4": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _vp, _i, _vp]),
     "stcd_scene_stitch_d4": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "stcd_scene_gather_one_d4": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp]),
+    "stcd_scene_stitch_heads_d4": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
+    "stcd_scene_finalize_seg": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "stcd_selftrain_score": (_i, [C.POINTER(_vp), _i, _i, _i, _i64, _f, _vp, _i, _vp, _vp, _vp, _vp]),
     "stcd_scene_cell_agree": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "stcd_mask_close": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

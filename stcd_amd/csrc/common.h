@@ -622,6 +622,16 @@ void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, in
                             const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s);
 void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
                             int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s);
+// one scene (UnetSeg) and several heads of one forward (SegCD's three maps): the same kernels, so the same bits per scene and per head;
+// the heads' device pointers travel by value, acc is [n_heads * classes, H, W] over one wsum
+void launch_scene_gather_one_d4(const uint8_t* A, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles, const float* mean,
+                                const float* std_, float* x, int d4, hipStream_t s);
+struct SceneHeadPtrs { const float* p[STCD_SCENE_MAX_HEADS]; };
+void launch_scene_stitch_heads_d4(const SceneHeadPtrs& lg, int n_heads, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y,
+                                  int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s);
+void launch_scene_finalize_seg(const float* acc, const float* wsum, int classes, int H, int W, float seg_threshold, float change_threshold,
+                               const uint8_t* label_a, const uint8_t* label_b, const uint8_t* label_c, uint8_t* seg_a, uint8_t* seg_b,
+                               uint8_t* change, uint8_t* gated, float* prob, int64_t* cm, hipStream_t s);
 // the tile-grid checks shared by every stcd_scene_* entry (engine.hip, ops_abi.hip); tiles per axis: max(0, ceil((L - T) / S)) + 1
 inline int scene_tiles(int L, int T, int S) { return (L > T ? (int)(((int64_t)L - T + S - 1) / S) : 0) + 1; }
 inline int check_scene_grid(int height, int width, int tile, int stride, int tiles_x, int tiles_y, int first_tile, int n_tiles) {

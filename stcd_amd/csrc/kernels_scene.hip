@@ -21,6 +21,12 @@
 // The transposing views (4..7) go through LDS so that both global sides run along their own fast axis: k_scene_gather_t stages a
 // 64 x 64 patch of scene rows and writes tile rows whose fast axis is the scene's y; k_scene_stitch_t owns a 64 x 64 scene patch
 // and, per covering tile, stages the logit sub-block with lanes along the logits' fast axis and reads it back transposed.
+//
+// One scene and several heads (stcd_scene_gather_one_d4 / stcd_scene_stitch_heads_d4 / stcd_scene_finalize_seg; UnetSeg takes one
+// image, train_sup.py:303, and SegCD's forward returns (mask_t1, mask_t2, change), decoders/unet/model.py:316-332): the gather kernels
+// with the second scene compiled out (template PAIR), the stitch kernels with NH heads per launch (NH == 1 is the single-head entry:
+// one code, so the same bits per head by construction), and a finalize of the three heads in one pass that also forms the gate of
+// train_stcd.py:170-176.
 #include <algorithm>
 
 #include "common.h"
@@ -54,8 +60,9 @@ __device__ __forceinline__ void scene_load12(const uint8_t* __restrict__ p, floa
     }
 }
 
-// MIR: bit 0 mirrors the tile's columns, bit 1 its rows (d4 in 0..3); the values are those of MIR == 0, only the address moves
-template <bool VEC, int MIR>
+// MIR: bit 0 mirrors the tile's columns, bit 1 its rows (d4 in 0..3); the values are those of MIR == 0, only the address moves.
+// PAIR == false is stcd_scene_gather_one_d4: B and x2 are not touched, x1 is the same code and so the same bits
+template <bool VEC, int MIR, bool PAIR>
 __global__ void __launch_bounds__(256)
 k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int H, int W, int T, int S, int tiles_x, int first_tile,
                int gpr, int64_t total, float m0, float m1, float m2, float is0, float is1, float is2, float* __restrict__ x1,
@@ -71,17 +78,20 @@ k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int
         const int tx0 = xg * 4;
         const int64_t y = scene_reflect(ky * S + ty, H), gx0 = kx * S + tx0;
         const uint8_t* ra = A + y * W * 3;
-        const uint8_t* rb = B + y * W * 3;
-        float ua[12], ub[12];
+        const uint8_t* rb = PAIR ? B + y * W * 3 : ra;
+        float ua[12], ub[12] = {};
         if (gx0 + 3 < W) {                                            // four scene pixels in a row: no reflection along x
             scene_load12(ra + gx0 * 3, ua);
-            scene_load12(rb + gx0 * 3, ub);
+            if (PAIR) scene_load12(rb + gx0 * 3, ub);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t x = scene_reflect(gx0 + j, W);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) { ua[3 * j + c] = (float)ra[x * 3 + c]; ub[3 * j + c] = (float)rb[x * 3 + c]; }
+                for (int c = 0; c < 3; ++c) {
+                    ua[3 * j + c] = (float)ra[x * 3 + c];
+                    if (PAIR) ub[3 * j + c] = (float)rb[x * 3 + c];
+                }
             }
         }
 #pragma unroll
@@ -96,24 +106,24 @@ k_scene_gather(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int
                 const int64_t o = ((n * 3 + c) * T + ty) * T + tx0;
                 if (VEC) {
                     *reinterpret_cast<float4*>(x1 + o) = make_float4(va[0], va[1], va[2], va[3]);
-                    *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                    if (PAIR) *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
                 } else {
                     for (int j = 0; j < 4; ++j)
-                        if (tx0 + j < T) { x1[o + j] = va[j]; x2[o + j] = vb[j]; }
+                        if (tx0 + j < T) { x1[o + j] = va[j]; if (PAIR) x2[o + j] = vb[j]; }
                 }
             } else {
                 const int64_t o = ((n * 3 + c) * T + ((MIR & 2) ? T - 1 - ty : ty)) * T;
                 if (VEC && (MIR & 1)) {                               // T % 4 == 0: the mirrored group starts at a multiple of 4
                     *reinterpret_cast<float4*>(x1 + o + (T - 4 - tx0)) = make_float4(va[3], va[2], va[1], va[0]);
-                    *reinterpret_cast<float4*>(x2 + o + (T - 4 - tx0)) = make_float4(vb[3], vb[2], vb[1], vb[0]);
+                    if (PAIR) *reinterpret_cast<float4*>(x2 + o + (T - 4 - tx0)) = make_float4(vb[3], vb[2], vb[1], vb[0]);
                 } else if (VEC) {
                     *reinterpret_cast<float4*>(x1 + o + tx0) = make_float4(va[0], va[1], va[2], va[3]);
-                    *reinterpret_cast<float4*>(x2 + o + tx0) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                    if (PAIR) *reinterpret_cast<float4*>(x2 + o + tx0) = make_float4(vb[0], vb[1], vb[2], vb[3]);
                 } else {
                     for (int j = 0; j < 4; ++j)
                         if (tx0 + j < T) {
                             const int ox = (MIR & 1) ? T - 1 - tx0 - j : tx0 + j;
-                            x1[o + ox] = va[j]; x2[o + ox] = vb[j];
+                            x1[o + ox] = va[j]; if (PAIR) x2[o + ox] = vb[j];
                         }
                 }
             }
@@ -147,12 +157,12 @@ __device__ __forceinline__ void scene_load12_raw(const uint8_t* __restrict__ row
     w[0] = v[0]; w[1] = v[1]; w[2] = v[2];
 }
 
-template <bool VEC>
+template <bool VEC, bool PAIR>
 __global__ void __launch_bounds__(256)
 k_scene_gather_t(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, int H, int W, int T, int S, int tiles_x, int first_tile,
                  int ppa, int64_t n_patches, int d4, float m0, float m1, float m2, float is0, float is1, float is2, float* __restrict__ x1,
                  float* __restrict__ x2) {
-    __shared__ uint32_t lds[2][SCENE_PATCH][SCENE_GPITCH];
+    __shared__ uint32_t lds[PAIR ? 2 : 1][SCENE_PATCH][SCENE_GPITCH];  // B's plane is lds[PAIR]: no index past the end when it is absent
     const float mean[3] = {m0, m1, m2}, istd[3] = {is0, is1, is2};
     const int t4 = (threadIdx.x & 15) * 4, tr = threadIdx.x >> 4;
     for (int64_t blk = blockIdx.x; blk < n_patches; blk += gridDim.x) {   // uniform per block: the barriers are safe
@@ -168,7 +178,7 @@ k_scene_gather_t(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, i
             for (int pl = tr; pl < pn; pl += 16) {
                 const int64_t y = scene_reflect(ky * S + p0 + pl, H), gx0 = kx * S + q0 + t4;
                 scene_load12_raw(A + y * W * 3, gx0, W, &lds[0][pl][3 * (t4 >> 2)]);
-                scene_load12_raw(B + y * W * 3, gx0, W, &lds[1][pl][3 * (t4 >> 2)]);
+                if (PAIR) scene_load12_raw(B + y * W * 3, gx0, W, &lds[PAIR][pl][3 * (t4 >> 2)]);
             }
         __syncthreads();
         if (t4 >= pn) continue;                                       // no barrier below
@@ -177,23 +187,25 @@ k_scene_gather_t(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, i
             const int ql = (d4 & 1) ? qn - 1 - il : il;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                float va[4], vb[4];
+                float va[4], vb[4] = {};
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int pl = min(t4 + j, pn - 1);               // past the patch (T % 4 != 0): computed, not stored
                     const int ps = (d4 & 2) ? pn - 1 - pl : pl;
                     const float ua = (float)reinterpret_cast<const uint8_t*>(&lds[0][ps][0])[ql * 3 + c];
-                    const float ub = (float)reinterpret_cast<const uint8_t*>(&lds[1][ps][0])[ql * 3 + c];
                     va[j] = (ua * (1.f / 255.f) - mean[c]) * istd[c];  // k_scene_gather's arithmetic, to the operation
-                    vb[j] = (ub * (1.f / 255.f) - mean[c]) * istd[c];
+                    if (PAIR) {
+                        const float ub = (float)reinterpret_cast<const uint8_t*>(&lds[PAIR][ps][0])[ql * 3 + c];
+                        vb[j] = (ub * (1.f / 255.f) - mean[c]) * istd[c];
+                    }
                 }
                 const int64_t o = ((n * 3 + c) * T + ib + il) * T + jb + t4;
                 if (VEC) {                                            // T % 4 == 0: pn and jb are multiples of 4
                     *reinterpret_cast<float4*>(x1 + o) = make_float4(va[0], va[1], va[2], va[3]);
-                    *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
+                    if (PAIR) *reinterpret_cast<float4*>(x2 + o) = make_float4(vb[0], vb[1], vb[2], vb[3]);
                 } else {
                     for (int j = 0; j < 4; ++j)
-                        if (t4 + j < pn) { x1[o + j] = va[j]; x2[o + j] = vb[j]; }
+                        if (t4 + j < pn) { x1[o + j] = va[j]; if (PAIR) x2[o + j] = vb[j]; }
                 }
             }
         }
@@ -203,21 +215,23 @@ k_scene_gather_t(const uint8_t* __restrict__ A, const uint8_t* __restrict__ B, i
 static inline unsigned scene_blocks(int64_t threads) { return (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, (threads + 255) / 256); }
 static inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-template <int MIR>
+template <int MIR, bool PAIR>
 static void scene_gather_rows(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
                               const float* mean, const float* std_, float* x1, float* x2, hipStream_t s) {
     const int gpr = (T + 3) / 4;
     const int64_t total = (int64_t)n_tiles * T * gpr;
     const float is0 = 1.f / std_[0], is1 = 1.f / std_[1], is2 = 1.f / std_[2];
     if (T % 4 == 0 && aligned_to(x1, 16) && aligned_to(x2, 16))
-        k_scene_gather<true, MIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1],
-                                                                      mean[2], is0, is1, is2, x1, x2);
+        k_scene_gather<true, MIR, PAIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0],
+                                                                            mean[1], mean[2], is0, is1, is2, x1, x2);
     else
-        k_scene_gather<false, MIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0], mean[1],
-                                                                       mean[2], is0, is1, is2, x1, x2);
+        k_scene_gather<false, MIR, PAIR><<<scene_blocks(total), 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, gpr, total, mean[0],
+                                                                             mean[1], mean[2], is0, is1, is2, x1, x2);
 }
 
-void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+// PAIR == false (stcd_scene_gather_one_d4): B and x2 are NULL, which counts as aligned
+template <bool PAIR>
+static void scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
                             const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s) {
     if (n_tiles == 0) return;
     if (d4 & 4) {
@@ -226,19 +240,29 @@ void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, in
         const unsigned blocks = (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, n_patches);
         const float is0 = 1.f / std_[0], is1 = 1.f / std_[1], is2 = 1.f / std_[2];
         if (T % 4 == 0 && aligned_to(x1, 16) && aligned_to(x2, 16))
-            k_scene_gather_t<true><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1], mean[2],
-                                                         is0, is1, is2, x1, x2);
+            k_scene_gather_t<true, PAIR><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1],
+                                                               mean[2], is0, is1, is2, x1, x2);
         else
-            k_scene_gather_t<false><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1], mean[2],
-                                                          is0, is1, is2, x1, x2);
+            k_scene_gather_t<false, PAIR><<<blocks, 256, 0, s>>>(A, B, H, W, T, S, tiles_x, first_tile, ppa, n_patches, d4, mean[0], mean[1],
+                                                                mean[2], is0, is1, is2, x1, x2);
         return;
     }
     switch (d4) {
-        case 0: scene_gather_rows<0>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
-        case 1: scene_gather_rows<1>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
-        case 2: scene_gather_rows<2>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
-        default: scene_gather_rows<3>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        case 0: scene_gather_rows<0, PAIR>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        case 1: scene_gather_rows<1, PAIR>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        case 2: scene_gather_rows<2, PAIR>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
+        default: scene_gather_rows<3, PAIR>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, s); break;
     }
+}
+
+void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
+                            const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s) {
+    scene_gather_d4<true>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, d4, s);
+}
+
+void launch_scene_gather_one_d4(const uint8_t* A, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles, const float* mean,
+                                const float* std_, float* x, int d4, hipStream_t s) {
+    scene_gather_d4<false>(A, nullptr, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x, nullptr, d4, s);
 }
 
 void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
@@ -250,10 +274,15 @@ void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T
 // The launch covers the rectangle [y0, y0 + rows) x [x0, x0 + 4 * gpr) of the scene that this call's tiles can reach (x0 a
 // multiple of 4).  Tiles covering row y: ky * S <= y < ky * S + T, i.e. ky in [y < T ? 0 : (y - T) / S + 1, min(y / S, tiles_y - 1)];
 // likewise along x.  A thread walks ky then kx upwards, which is ascending tile index for each of its four pixels.
-// MIR as in k_scene_gather: the logits are in view MIR of the tile, weights and order stay upright
-template <int CLS, int MIR>
+// MIR as in k_scene_gather: the logits are in view MIR of the tile, weights and order stay upright.
+// wsum takes the weight as ONE fused multiply-add, wsum = fmaf(window[ty], window[tx], wsum), while acc takes the rounded product,
+// acc = fmaf(w, logit, acc) with w = window[ty] * window[tx]: that is what `ws += w` has always compiled to here (the compiler
+// contracts it), and it is written out so that every instantiation gives the same bits whatever the vectoriser does with it.
+// NH heads (stcd_scene_stitch_heads_d4; NH == 1 is stcd_scene_stitch_d4): head h adds lg.p[h] into the planes h * CLS .. of acc with
+// the chain it would run alone; the covering ranges, the window weight and wsum are worked out once per pixel for all of them
+template <int NH, int CLS, int MIR>
 __global__ void __launch_bounds__(256)
-k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
+k_scene_stitch(const SceneHeadPtrs lg, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
                const float* __restrict__ window, float* __restrict__ acc, float* __restrict__ wsum, int y0, int x0, int gpr, int64_t total,
                int vec_l, int vec_a) {
     const int64_t HW = (int64_t)H * W;
@@ -265,7 +294,7 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
         const int ky_lo = y < T ? 0 : (y - T) / S + 1, ky_hi = min(y / S, tiles_y - 1);
         const int kx_lo = xs < T ? 0 : (xs - T) / S + 1, kx_hi = min(xe / S, tiles_x - 1);
         const int64_t pix = (int64_t)y * W + xs;
-        float a[CLS][4], ws[4];
+        float a[NH * CLS][4], ws[4];
         bool touched = false;
         for (int ky = ky_lo; ky <= ky_hi; ++ky) {
             const int ty = y - ky * S;
@@ -279,7 +308,7 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
                         const float4 w4 = *reinterpret_cast<const float4*>(wsum + pix);
                         ws[0] = w4.x; ws[1] = w4.y; ws[2] = w4.z; ws[3] = w4.w;
 #pragma unroll
-                        for (int c = 0; c < CLS; ++c) {
+                        for (int c = 0; c < NH * CLS; ++c) {
                             const float4 a4 = *reinterpret_cast<const float4*>(acc + c * HW + pix);
                             a[c][0] = a4.x; a[c][1] = a4.y; a[c][2] = a4.z; a[c][3] = a4.w;
                         }
@@ -289,41 +318,47 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
                             const bool ok = xs + j < W;
                             ws[j] = ok ? wsum[pix + j] : 0.f;
 #pragma unroll
-                            for (int c = 0; c < CLS; ++c) a[c][j] = ok ? acc[c * HW + pix + j] : 0.f;
+                            for (int c = 0; c < NH * CLS; ++c) a[c][j] = ok ? acc[c * HW + pix + j] : 0.f;
                         }
                     }
                 }
                 const int tx0 = xs - kx * S;
-                const float* lp = logits + (k * CLS * T + ((MIR & 2) ? T - 1 - ty : ty)) * T;   // class 0 row of this tile; class c is c * T * T further
+                const int64_t lo = (k * CLS * T + ((MIR & 2) ? T - 1 - ty : ty)) * T;   // class 0 row of this tile; class c is c * T * T further
                 if (vec_l && tx0 >= 0 && tx0 + 3 < T) {               // xs, S and T are multiples of 4 here, so tx0 is one too
                     float wx[4] = {1.f, 1.f, 1.f, 1.f};
                     if (window) {
                         const float4 w4 = *reinterpret_cast<const float4*>(window + tx0);
                         wx[0] = w4.x; wx[1] = w4.y; wx[2] = w4.z; wx[3] = w4.w;
                     }
-                    float l[CLS][4];
+                    float l[NH * CLS][4];
 #pragma unroll
-                    for (int c = 0; c < CLS; ++c) {
-                        const float4 l4 = *reinterpret_cast<const float4*>(lp + (int64_t)c * T * T + ((MIR & 1) ? T - 4 - tx0 : tx0));
-                        if (MIR & 1) { l[c][0] = l4.w; l[c][1] = l4.z; l[c][2] = l4.y; l[c][3] = l4.x; }
-                        else { l[c][0] = l4.x; l[c][1] = l4.y; l[c][2] = l4.z; l[c][3] = l4.w; }
-                    }
+                    for (int h = 0; h < NH; ++h)
+#pragma unroll
+                        for (int c = 0; c < CLS; ++c) {
+                            const float4 l4 = *reinterpret_cast<const float4*>(lg.p[h] + lo + (int64_t)c * T * T + ((MIR & 1) ? T - 4 - tx0 : tx0));
+                            float* lc = l[h * CLS + c];
+                            if (MIR & 1) { lc[0] = l4.w; lc[1] = l4.z; lc[2] = l4.y; lc[3] = l4.x; }
+                            else { lc[0] = l4.x; lc[1] = l4.y; lc[2] = l4.z; lc[3] = l4.w; }
+                        }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float w = wy * wx[j];
 #pragma unroll
-                        for (int c = 0; c < CLS; ++c) a[c][j] = fmaf(w, l[c][j], a[c][j]);
-                        ws[j] += w;
+                        for (int c = 0; c < NH * CLS; ++c) a[c][j] = fmaf(w, l[c][j], a[c][j]);
+                        ws[j] = fmaf(wy, wx[j], ws[j]);               // see the note on wsum above the kernel
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int tx = tx0 + j;
                         if (tx < 0 || tx >= T || xs + j >= W) continue;
-                        const float w = wy * (window ? window[tx] : 1.f);
+                        const float wxj = window ? window[tx] : 1.f, w = wy * wxj;
 #pragma unroll
-                        for (int c = 0; c < CLS; ++c) a[c][j] = fmaf(w, lp[(int64_t)c * T * T + ((MIR & 1) ? T - 1 - tx : tx)], a[c][j]);
-                        ws[j] += w;
+                        for (int h = 0; h < NH; ++h)
+#pragma unroll
+                            for (int c = 0; c < CLS; ++c)
+                                a[h * CLS + c][j] = fmaf(w, lg.p[h][lo + (int64_t)c * T * T + ((MIR & 1) ? T - 1 - tx : tx)], a[h * CLS + c][j]);
+                        ws[j] = fmaf(wy, wxj, ws[j]);
                     }
                 }
             }
@@ -332,14 +367,14 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
         if (vec_a) {
             *reinterpret_cast<float4*>(wsum + pix) = make_float4(ws[0], ws[1], ws[2], ws[3]);
 #pragma unroll
-            for (int c = 0; c < CLS; ++c) *reinterpret_cast<float4*>(acc + c * HW + pix) = make_float4(a[c][0], a[c][1], a[c][2], a[c][3]);
+            for (int c = 0; c < NH * CLS; ++c) *reinterpret_cast<float4*>(acc + c * HW + pix) = make_float4(a[c][0], a[c][1], a[c][2], a[c][3]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (xs + j >= W) continue;
                 wsum[pix + j] = ws[j];
 #pragma unroll
-                for (int c = 0; c < CLS; ++c) acc[c * HW + pix + j] = a[c][j];
+                for (int c = 0; c < NH * CLS; ++c) acc[c * HW + pix + j] = a[c][j];
             }
         }
     }
@@ -347,15 +382,16 @@ k_scene_stitch(const float* __restrict__ logits, int H, int W, int T, int S, int
 
 // ---- transposing views of the stitch (d4 & 4): the logit of the upright tile pixel (ty, tx) is Ld[c, i, j] with
 // i = (d4 & 1) ? T-1-tx : tx and j = (d4 & 2) ? T-1-ty : ty, so the logits' fast axis runs along the scene's y.  A block owns a
-// 64 x 64 scene patch, a thread 4 rows of 4 consecutive x (16 register chains per class).  The tile loop runs over the union of
-// the patch's covering ranges and is uniform per block; a pixel joins a tile by the predicate that defines its own covering range,
-// so every pixel sees its tiles in ascending index exactly as in k_scene_stitch.  Per tile: a wave stages 64 consecutive j of one
-// logit row (256 contiguous bytes) into lds[c][x][y], rows of 65 dwords, and after the barrier a thread reads lds[c][x][y] for its
-// pixels: 16 lanes 4 rows of 65 apart and 4 neighbouring y, two lanes per bank, which is the floor for 64 lanes.
+// 64 x 64 scene patch, a thread 4 rows of 4 consecutive x (16 register chains per head and class).  The tile loop runs over the
+// union of the patch's covering ranges and is uniform per block; a pixel joins a tile by the predicate that defines its own covering
+// range, so every pixel sees its tiles in ascending index exactly as in k_scene_stitch.  Per tile the thread works out the weights of
+// its 16 pixels once; then, one head at a time (so that LDS stays float[CLS][64][65] for any NH): a wave stages 64 consecutive j of
+// one logit row (256 contiguous bytes) into lds[c][x][y], rows of 65 dwords, and after the barrier a thread reads lds[c][x][y] for
+// its pixels: 16 lanes 4 rows of 65 apart and 4 neighbouring y, two lanes per bank, which is the floor for 64 lanes.
 #define SCENE_SPITCH (SCENE_PATCH + 1)
-template <int CLS>
+template <int NH, int CLS>
 __global__ void __launch_bounds__(256)
-k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
+k_scene_stitch_t(const SceneHeadPtrs lg, int H, int W, int T, int S, int tiles_x, int tiles_y, int64_t first_tile, int64_t n_tiles,
                  const float* __restrict__ window, float* __restrict__ acc, float* __restrict__ wsum, int y0, int x0, int pcols,
                  int64_t n_patches, int d4, int vec_a) {
     __shared__ float lds[CLS][SCENE_PATCH][SCENE_SPITCH];
@@ -368,7 +404,7 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
         const int ky_lo = py < T ? 0 : (py - T) / S + 1, ky_hi = min(ye / S, tiles_y - 1);
         const int kx_lo = px < T ? 0 : (px - T) / S + 1, kx_hi = min(xe / S, tiles_x - 1);
         const int xs = px + t4;
-        float a[CLS][4][4], ws[4][4];
+        float a[NH * CLS][4][4], ws[4][4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                 // the chain continues from what earlier calls left
             const int y = py + tr + 16 * r;
@@ -377,7 +413,7 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
                 const float4 w4 = *reinterpret_cast<const float4*>(wsum + pix);
                 ws[r][0] = w4.x; ws[r][1] = w4.y; ws[r][2] = w4.z; ws[r][3] = w4.w;
 #pragma unroll
-                for (int c = 0; c < CLS; ++c) {
+                for (int c = 0; c < NH * CLS; ++c) {
                     const float4 a4 = *reinterpret_cast<const float4*>(acc + c * HW + pix);
                     a[c][r][0] = a4.x; a[c][r][1] = a4.y; a[c][r][2] = a4.z; a[c][r][3] = a4.w;
                 }
@@ -387,7 +423,7 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
                     const bool ok = y < H && xs + j < W;
                     ws[r][j] = ok ? wsum[pix + j] : 0.f;
 #pragma unroll
-                    for (int c = 0; c < CLS; ++c) a[c][r][j] = ok ? acc[c * HW + pix + j] : 0.f;
+                    for (int c = 0; c < NH * CLS; ++c) a[c][r][j] = ok ? acc[c * HW + pix + j] : 0.f;
                 }
             }
         }
@@ -397,22 +433,8 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
                 const int64_t k = (int64_t)ky * tiles_x + kx - first_tile;
                 if (k < 0 || k >= n_tiles) continue;                  // another call's tile (uniform)
                 const int ty0 = py - ky * S, tx0 = px - kx * S;       // tile coordinates of the patch origin: may be negative
-                __syncthreads();                                      // the previous tile has been read
-                {
-                    const int ty = ty0 + lane;
-                    if (ty >= 0 && ty < T) {
-                        const int j = (d4 & 2) ? T - 1 - ty : ty;
-                        for (int xl = wv; xl < SCENE_PATCH; xl += 4) {
-                            const int tx = tx0 + xl;
-                            if (tx < 0 || tx >= T) continue;
-                            const int i = (d4 & 1) ? T - 1 - tx : tx;
-                            const float* lp = logits + ((k * CLS * T + i) * T + j);
-#pragma unroll
-                            for (int c = 0; c < CLS; ++c) lds[c][xl][lane] = lp[(int64_t)c * T * T];
-                        }
-                    }
-                }
-                __syncthreads();
+                float wgt[4][4] = {};                                 // this tile's weight at the thread's pixels, once for all heads
+                unsigned on = 0;                                      // bit 4 * r + j: the pixel is in the scene and in the tile
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int yl = tr + 16 * r, ty = ty0 + yl;
@@ -422,12 +444,40 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
                     for (int j = 0; j < 4; ++j) {
                         const int tx = tx0 + t4 + j;
                         if (tx < 0 || tx >= T || xs + j >= W) continue;
-                        const float w = wy * (window ? window[tx] : 1.f);
-#pragma unroll
-                        for (int c = 0; c < CLS; ++c) a[c][r][j] = fmaf(w, lds[c][t4 + j][yl], a[c][r][j]);
-                        ws[r][j] += w;
-                        touched = true;
+                        const float wxj = window ? window[tx] : 1.f;
+                        wgt[r][j] = wy * wxj;
+                        ws[r][j] = fmaf(wy, wxj, ws[r][j]);           // as k_scene_stitch
+                        on |= 1u << (4 * r + j);
                     }
+                }
+                touched |= on != 0;
+#pragma unroll
+                for (int h = 0; h < NH; ++h) {
+                    __syncthreads();                                  // the previous tile or head has been read
+                    {
+                        const int ty = ty0 + lane;
+                        if (ty >= 0 && ty < T) {
+                            const int j = (d4 & 2) ? T - 1 - ty : ty;
+                            for (int xl = wv; xl < SCENE_PATCH; xl += 4) {
+                                const int tx = tx0 + xl;
+                                if (tx < 0 || tx >= T) continue;
+                                const int i = (d4 & 1) ? T - 1 - tx : tx;
+                                const float* lp = lg.p[h] + ((k * CLS * T + i) * T + j);
+#pragma unroll
+                                for (int c = 0; c < CLS; ++c) lds[c][xl][lane] = lp[(int64_t)c * T * T];
+                            }
+                        }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            if (!(on & (1u << (4 * r + j)))) continue;
+#pragma unroll
+                            for (int c = 0; c < CLS; ++c)
+                                a[h * CLS + c][r][j] = fmaf(wgt[r][j], lds[c][t4 + j][tr + 16 * r], a[h * CLS + c][r][j]);
+                        }
                 }
             }
         if (!touched) continue;
@@ -439,7 +489,7 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
             if (vec_a) {
                 *reinterpret_cast<float4*>(wsum + pix) = make_float4(ws[r][0], ws[r][1], ws[r][2], ws[r][3]);
 #pragma unroll
-                for (int c = 0; c < CLS; ++c)
+                for (int c = 0; c < NH * CLS; ++c)
                     *reinterpret_cast<float4*>(acc + c * HW + pix) = make_float4(a[c][r][0], a[c][r][1], a[c][r][2], a[c][r][3]);
             } else {
 #pragma unroll
@@ -447,23 +497,26 @@ k_scene_stitch_t(const float* __restrict__ logits, int H, int W, int T, int S, i
                     if (xs + j >= W) continue;
                     wsum[pix + j] = ws[r][j];
 #pragma unroll
-                    for (int c = 0; c < CLS; ++c) acc[c * HW + pix + j] = a[c][r][j];
+                    for (int c = 0; c < NH * CLS; ++c) acc[c * HW + pix + j] = a[c][r][j];
                 }
             }
         }
     }
 }
 
-template <int CLS, int MIR>
-static void scene_stitch_rows(const float* logits, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
-                              const float* window, float* acc, float* wsum, int y0, int x0, int gpr, int64_t total, int vec_l, int vec_a,
-                              hipStream_t s) {
-    k_scene_stitch<CLS, MIR><<<scene_blocks(total), 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
-                                                                 y0, x0, gpr, total, vec_l, vec_a);
-}
+// classes in {1, 2}, n_heads in 1..STCD_SCENE_MAX_HEADS (checked by the callers) -> the template arguments
+#define STCD_STITCH_SHAPES(X) \
+    switch (2 * n_heads + (classes == 2)) { \
+        case 2: X(1, 1); break; \
+        case 3: X(1, 2); break; \
+        case 4: X(2, 1); break; \
+        case 5: X(2, 2); break; \
+        case 6: X(3, 1); break; \
+        default: X(3, 2); break; \
+    }
 
-void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
-                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s) {
+void launch_scene_stitch_heads_d4(const SceneHeadPtrs& lg, int n_heads, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y,
+                                  int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s) {
     if (n_tiles == 0) return;
     const int last = first_tile + n_tiles - 1;
     const int ky0 = first_tile / tiles_x, ky1 = last / tiles_x;
@@ -479,30 +532,38 @@ void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int 
         const int pcols = (x1 - x0 + SCENE_PATCH - 1) / SCENE_PATCH;
         const int64_t n_patches = (int64_t)((y1 - y0 + SCENE_PATCH - 1) / SCENE_PATCH) * pcols;
         const unsigned blocks = (unsigned)std::min<int64_t>(SCENE_MAX_BLOCKS, n_patches);
-        if (classes == 2)
-            k_scene_stitch_t<2><<<blocks, 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, pcols,
-                                                      n_patches, d4, vec_a);
-        else
-            k_scene_stitch_t<1><<<blocks, 256, 0, s>>>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, pcols,
-                                                      n_patches, d4, vec_a);
+#define STCD_STITCH_T(NH, CLS) \
+    k_scene_stitch_t<NH, CLS><<<blocks, 256, 0, s>>>(lg, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, pcols, \
+                                                    n_patches, d4, vec_a)
+        STCD_STITCH_SHAPES(STCD_STITCH_T)
+#undef STCD_STITCH_T
         return;
     }
     const int gpr = (x1 - x0 + 3) / 4;
     const int64_t total = (int64_t)(y1 - y0) * gpr;
-    const int vec_l = T % 4 == 0 && S % 4 == 0 && aligned_to(logits, 16) && (!window || aligned_to(window, 16));
-#define STCD_STITCH_ROWS(CLS, MIR) \
-    scene_stitch_rows<CLS, MIR>(logits, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, y0, x0, gpr, total, vec_l, vec_a, s)
-    switch (2 * d4 + (classes == 2)) {
-        case 0: STCD_STITCH_ROWS(1, 0); break;
-        case 1: STCD_STITCH_ROWS(2, 0); break;
-        case 2: STCD_STITCH_ROWS(1, 1); break;
-        case 3: STCD_STITCH_ROWS(2, 1); break;
-        case 4: STCD_STITCH_ROWS(1, 2); break;
-        case 5: STCD_STITCH_ROWS(2, 2); break;
-        case 6: STCD_STITCH_ROWS(1, 3); break;
-        default: STCD_STITCH_ROWS(2, 3); break;
+    int vec_l = T % 4 == 0 && S % 4 == 0 && (!window || aligned_to(window, 16));
+    for (int h = 0; h < n_heads; ++h) vec_l = vec_l && aligned_to(lg.p[h], 16);
+#define STCD_STITCH_ROWS(NH, CLS) \
+    switch (d4) { \
+        case 0: k_scene_stitch<NH, CLS, 0><<<scene_blocks(total), 256, 0, s>>>(lg, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, \
+                                                                              wsum, y0, x0, gpr, total, vec_l, vec_a); break; \
+        case 1: k_scene_stitch<NH, CLS, 1><<<scene_blocks(total), 256, 0, s>>>(lg, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, \
+                                                                              wsum, y0, x0, gpr, total, vec_l, vec_a); break; \
+        case 2: k_scene_stitch<NH, CLS, 2><<<scene_blocks(total), 256, 0, s>>>(lg, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, \
+                                                                              wsum, y0, x0, gpr, total, vec_l, vec_a); break; \
+        default: k_scene_stitch<NH, CLS, 3><<<scene_blocks(total), 256, 0, s>>>(lg, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, \
+                                                                               wsum, y0, x0, gpr, total, vec_l, vec_a); break; \
     }
+    STCD_STITCH_SHAPES(STCD_STITCH_ROWS)
 #undef STCD_STITCH_ROWS
+}
+#undef STCD_STITCH_SHAPES
+
+void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
+                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s) {
+    SceneHeadPtrs lg{};
+    lg.p[0] = logits;
+    launch_scene_stitch_heads_d4(lg, 1, classes, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, d4, s);
 }
 
 void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
@@ -600,6 +661,137 @@ void launch_scene_finalize(const float* acc, const float* wsum, int classes, int
         k_scene_finalize<2><<<scene_blocks(total), 256, 0, s>>>(acc, wsum, H, W, threshold, lab, mask, prob, cmu, gpr, total, vec);
     else
         k_scene_finalize<1><<<scene_blocks(total), 256, 0, s>>>(acc, wsum, H, W, threshold, lab, mask, prob, cmu, gpr, total, vec);
+}
+
+// ------------------------------------------------------------------ finalize of three stitched heads in one pass (stcd_scene_finalize_seg)
+// acc holds the heads of SegCD's forward in its order, (mask_t1, mask_t2, change), CLS planes each over ONE wsum.  Per head the mask and
+// the probability are k_scene_finalize's expressions, so they are its bits; gated = change & (seg_a != seg_b) is the decision-level gate
+// sketched in train_stcd.py:170-176.  cm: four matrices of four counters, rows seg_a / seg_b / change / gated, counted
+// only where that row's label (and, for row 3, gated) was given; the reduction is k_scene_finalize's, 16 counters instead of 4.
+template <int CLS>
+__global__ void __launch_bounds__(256)
+k_scene_finalize_seg(const float* __restrict__ acc, const float* __restrict__ wsum, int H, int W, float seg_threshold, float change_threshold,
+                     const uint8_t* __restrict__ label_a, const uint8_t* __restrict__ label_b, const uint8_t* __restrict__ label_c,
+                     uint8_t* __restrict__ seg_a, uint8_t* __restrict__ seg_b, uint8_t* __restrict__ change, uint8_t* __restrict__ gated,
+                     float* __restrict__ prob, unsigned long long* __restrict__ cm, int gpr, int64_t total, int vec) {
+    __shared__ unsigned int bins[16];
+    if (threadIdx.x < 16) bins[threadIdx.x] = 0;
+    __syncthreads();
+    unsigned int loc[4][4] = {};
+    const int64_t HW = (int64_t)H * W;
+    const bool need_ws = CLS == 1 || prob != nullptr;
+    const uint8_t* const labels[3] = {label_a, label_b, label_c};
+    uint8_t* const masks[3] = {seg_a, seg_b, change};
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const int xs = (int)(g % gpr) * 4;
+        const int64_t pix = (g / gpr) * W + xs;
+        float ws[4] = {1.f, 1.f, 1.f, 1.f};
+        if (need_ws) {
+            if (vec) {
+                const float4 w4 = *reinterpret_cast<const float4*>(wsum + pix);
+                ws[0] = w4.x; ws[1] = w4.y; ws[2] = w4.z; ws[3] = w4.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (xs + j < W) ws[j] = wsum[pix + j];
+            }
+        }
+        uint8_t pr[3][4], lab[4];
+#pragma unroll
+        for (int h = 0; h < 3; ++h) {
+            const float* ah = acc + (int64_t)h * CLS * HW;
+            const float threshold = h == 2 ? change_threshold : seg_threshold;
+            float a[CLS][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) lab[j] = 255;
+            if (vec) {
+#pragma unroll
+                for (int c = 0; c < CLS; ++c) {
+                    const float4 a4 = *reinterpret_cast<const float4*>(ah + c * HW + pix);
+                    a[c][0] = a4.x; a[c][1] = a4.y; a[c][2] = a4.z; a[c][3] = a4.w;
+                }
+                if (labels[h]) {
+                    const uint32_t l4 = *reinterpret_cast<const uint32_t*>(labels[h] + pix);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lab[j] = (uint8_t)(l4 >> (8 * j));
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool ok = xs + j < W;
+#pragma unroll
+                    for (int c = 0; c < CLS; ++c) a[c][j] = ok ? ah[c * HW + pix + j] : 0.f;
+                    if (labels[h] && ok) lab[j] = labels[h][pix + j];
+                }
+            }
+            float pb[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                             // k_scene_finalize's rules: a tie is class 0, strict >, NaN is class 0
+                pr[h][j] = CLS == 2 ? (a[CLS - 1][j] > a[0][j]) : (a[0][j] > threshold * ws[j]);
+                if (prob) {
+                    const float d = (CLS == 2 ? a[CLS - 1][j] - a[0][j] : a[0][j]) / ws[j];
+                    pb[j] = 1.f / (1.f + expf(-d));
+                }
+                if (lab[j] != 255) loc[h][2 * (lab[j] >= 1) + pr[h][j]]++;   // lanes past the row end carry 255
+            }
+            if (vec) {
+                *reinterpret_cast<uint32_t*>(masks[h] + pix) =
+                    (uint32_t)pr[h][0] | ((uint32_t)pr[h][1] << 8) | ((uint32_t)pr[h][2] << 16) | ((uint32_t)pr[h][3] << 24);
+                if (prob) *reinterpret_cast<float4*>(prob + h * HW + pix) = make_float4(pb[0], pb[1], pb[2], pb[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (xs + j >= W) continue;
+                    masks[h][pix + j] = pr[h][j];
+                    if (prob) prob[h * HW + pix + j] = pb[j];
+                }
+            }
+        }
+        if (gated) {                                                  // lab still holds label_c (h == 2 ran last)
+            uint8_t gt[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                gt[j] = pr[2][j] & (pr[0][j] != pr[1][j]);
+                if (lab[j] != 255) loc[3][2 * (lab[j] >= 1) + gt[j]]++;
+            }
+            if (vec) {
+                *reinterpret_cast<uint32_t*>(gated + pix) = (uint32_t)gt[0] | ((uint32_t)gt[1] << 8) | ((uint32_t)gt[2] << 16) | ((uint32_t)gt[3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (xs + j < W) gated[pix + j] = gt[j];
+            }
+        }
+    }
+    if (!cm) return;                                                  // uniform: no thread skips the barrier alone
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        if (!labels[min(k >> 2, 2)] || (k >= 12 && !gated)) continue; // a row without its label stays untouched (uniform)
+        unsigned int v = loc[k >> 2][k & 3];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(&bins[k], v);
+    }
+    __syncthreads();
+    if (threadIdx.x < 16 && bins[threadIdx.x]) atomicAdd(cm + threadIdx.x, (unsigned long long)bins[threadIdx.x]);
+}
+
+void launch_scene_finalize_seg(const float* acc, const float* wsum, int classes, int H, int W, float seg_threshold, float change_threshold,
+                               const uint8_t* label_a, const uint8_t* label_b, const uint8_t* label_c, uint8_t* seg_a, uint8_t* seg_b,
+                               uint8_t* change, uint8_t* gated, float* prob, int64_t* cm, hipStream_t s) {
+    const int gpr = (W + 3) / 4;
+    const int64_t total = (int64_t)H * gpr;
+    int vec = W % 4 == 0 && aligned_to(acc, 16) && aligned_to(wsum, 16) && (!prob || aligned_to(prob, 16));
+    for (const void* p : {(const void*)label_a, (const void*)label_b, (const void*)label_c, (const void*)seg_a, (const void*)seg_b,
+                          (const void*)change, (const void*)gated})
+        vec = vec && aligned_to(p, 4);                                // NULL counts as aligned
+    unsigned long long* cmu = (unsigned long long*)cm;                // block counts in 32 bits: see launch_scene_finalize
+    if (classes == 2)
+        k_scene_finalize_seg<2><<<scene_blocks(total), 256, 0, s>>>(acc, wsum, H, W, seg_threshold, change_threshold, label_a, label_b, label_c,
+                                                                    seg_a, seg_b, change, gated, prob, cmu, gpr, total, vec);
+    else
+        k_scene_finalize_seg<1><<<scene_blocks(total), 256, 0, s>>>(acc, wsum, H, W, seg_threshold, change_threshold, label_a, label_b, label_c,
+                                                                    seg_a, seg_b, change, gated, prob, cmu, gpr, total, vec);
 }
 
 }  // namespace stcd

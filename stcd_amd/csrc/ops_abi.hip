@@ -258,4 +258,47 @@ int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width
     return 0;
 }
 
+// ---- one scene (UnetSeg) and the three maps of SegCD's forward: the kernels of the entries above with one scene / several heads
+int stcd_scene_gather_one_d4(const uint8_t* scene, int height, int width, int tile, int stride, int tiles_x, int first_tile, int n_tiles,
+                             const float* mean3, const float* std3, float* x, int d4, void* hip_stream) {
+    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK(scene && mean3 && std3 && x, "null pointer argument");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
+        return 1;
+    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
+    launch_scene_gather_one_d4(scene, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x, d4, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_scene_stitch_heads_d4(const float* const* logits, int n_heads, int classes, int height, int width, int tile, int stride, int tiles_x,
+                               int tiles_y, int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4,
+                               void* hip_stream) {
+    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK(logits && acc && wsum, "null pointer argument");
+    STCD_CHECK(n_heads >= 1 && n_heads <= STCD_SCENE_MAX_HEADS, "n_heads must be in [1, 3]");
+    SceneHeadPtrs lg{};
+    for (int h = 0; h < n_heads; ++h) {
+        STCD_CHECK(logits[h] != nullptr, "a logits pointer is null");
+        lg.p[h] = logits[h];
+    }
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
+    launch_scene_stitch_heads_d4(lg, n_heads, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
+                                 d4, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+int stcd_scene_finalize_seg(const float* acc, const float* wsum, int classes, int height, int width, float seg_threshold,
+                            float change_threshold, const uint8_t* label_a, const uint8_t* label_b, const uint8_t* label_c, uint8_t* seg_a,
+                            uint8_t* seg_b, uint8_t* change, uint8_t* gated, float* prob, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(acc && wsum && seg_a && seg_b && change, "null pointer argument");
+    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+    STCD_CHECK(height >= 1 && width >= 1, "bad shape");
+    STCD_CHECK((label_a || label_b || label_c) == (cm != nullptr), "cm goes with at least one label");
+    launch_scene_finalize_seg(acc, wsum, classes, height, width, seg_threshold, change_threshold, label_a, label_b, label_c, seg_a, seg_b,
+                              change, gated, prob, cm, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
 }  // extern "C"

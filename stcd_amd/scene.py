@@ -12,6 +12,10 @@ Test-time augmentation over the eight symmetries of the square and checkpoint en
 ``stcd_scene_gather_d4`` writes a flipped / transposed view of the tiles directly and ``stcd_scene_stitch_d4`` reads the
 network's output for that view back through the inverse, so no tile or logit is permuted on the host.
 
+``predict_scene_heads`` keeps all three maps of ``SegCD`` / ``FFCTLCD`` (``stcd_scene_stitch_heads_d4``, ``stcd_scene_finalize_seg``: the
+two building masks, the change mask and the decision-level gate of train_stcd.py:170-176), and ``predict_scene_seg`` runs a
+one-input network such as ``UnetSeg`` over one scene (``stcd_scene_gather_one_d4``).
+
 ``plan_tiles``, ``window_table`` and ``parse_tta`` are host-only and need no GPU.
 """
 from __future__ import annotations
@@ -229,3 +233,192 @@ def predict_scene(model, scene_a, scene_b, tile: int = 256, stride: Optional[int
             m.train(was)
     cm_host = cm.cpu().numpy().reshape(2, 2) if cm is not None else None
     return SceneResult(mask, prob, cm_host, scores_from_cm(cm_host) if cm_host is not None else None)
+
+
+# ------------------------------------------------------------------------------------------------ one scene, and SegCD's three maps
+class SceneHeads(NamedTuple):
+    seg_a: torch.Tensor                 # uint8 [H,W] on the model's device: 1 is a building in scene A (SegCD's mask_t1)
+    seg_b: torch.Tensor                 # ... in scene B (mask_t2)
+    change: torch.Tensor                # uint8 [H,W]: predict_scene's mask
+    gated: torch.Tensor                 # uint8 [H,W]: change & (seg_a != seg_b), the gate of train_stcd.py:170-176
+    prob: Optional[torch.Tensor]        # fp32 [3,H,W] (return_prob=True): seg_a, seg_b, change
+    cm: dict                            # int64 [2,2] under "seg_a", "seg_b", "change", "gated" where the label was given
+    scores: dict                        # the same keys through metrics.scores_from_cm
+
+
+HEAD_KEYS = ("seg_a", "seg_b", "change", "gated")
+
+
+def _label_tensor(label, name: str, H: int, W: int) -> Optional[torch.Tensor]:
+    if label is None:
+        return None
+    lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
+    if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
+        raise StcdError(f"{name} must be uint8 [{H},{W}]")
+    return lab
+
+
+def _tile_args(H: int, W: int, tile, stride, batch, window, mean, std):
+    """predict_scene's checks of the grid, the batch, the window and the normalisation: ``(plan, batch, window table)``."""
+    plan = plan_tiles(H, W, tile, stride)
+    if int(batch) < 1:
+        raise StcdError(f"batch must be >= 1, got {batch}")
+    win = window_table(plan.tile, window)
+    if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
+        raise StcdError("mean and std hold three values, std positive")
+    return plan, min(int(batch), plan.n), win
+
+
+def _check_map(t, n: int, T: int, what: str) -> None:
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[0] != n or t.shape[1] not in (1, 2) or tuple(t.shape[2:]) != (T, T):
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise StcdError(f"the model returned {what}{got} for {n} tiles of {T} x {T}: expected [{n},1|2,{T},{T}]")
+
+
+def predict_scene_seg(model, scene, tile: int = 256, stride: Optional[int] = None, batch: int = 16, window: str = "flat", label=None,
+                      return_prob: bool = False, threshold: float = 0.0, mean: Sequence[float] = MEAN, std: Sequence[float] = STD,
+                      tta=None) -> SceneResult:
+    """``predict_scene`` for a one-input network: ``model`` is ``UnetSeg`` (the network train_sup.py:303 pre-trains) or any module on
+    a GPU that maps one ``[n,3,tile,tile]`` fp32 batch to ``[n,1|2,tile,tile]`` logits, or a list / tuple of at most 8 of them;
+    ``scene`` is one uint8 ``[H,W,3]`` scene.  ``stcd_scene_gather_one_d4`` writes the tiles, the rest is ``predict_scene``'s
+    pipeline and contract to the letter: eval mode and ``frozen_weights`` with the previous modes restored on exit, models outermost,
+    then views, then tile batches into one ``acc`` / ``wsum`` pair, ``label`` uint8 ``[H,W]`` (>= 1 is set, 255 is ignored), every
+    argument error raised before the first launch, no CPU fallback."""
+    from .modules import frozen_weights
+
+    views = parse_tta(tta)
+    a = _scene_tensor(scene, "scene")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    plan, batch, win = _tile_args(H, W, tile, stride, batch, window, mean, std)
+    lab = _label_tensor(label, "label", H, W)
+    models = _model_list(model)                                               # the device last: the other errors show without a GPU
+    dev = next(iter(models[0].parameters())).device
+    # everything is checked: from here on the device works
+    a = a.to(dev).contiguous()
+    lab = None if lab is None else lab.to(dev).contiguous()
+    win = None if window == "flat" else torch.from_numpy(win).to(dev)         # NULL window: all ones
+
+    l = _lib.lib()
+    T, S = plan.tile, plan.stride
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    was_training = [m.training for m in models]
+    try:
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            x = torch.empty((batch, 3, T, T), dtype=torch.float32, device=dev)        # reused by every batch
+            acc = wsum = None
+            classes = 0
+            for m in models:
+                m.eval()
+                with frozen_weights(m):
+                    for d4 in views:
+                        for first in range(0, plan.n, batch):
+                            n = min(batch, plan.n - first)
+                            _lib.check(l.stcd_scene_gather_one_d4(_ptr(a), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(x), d4, stream))
+                            logits = m(x[:n])
+                            _check_map(logits, n, T, "")
+                            if acc is None:
+                                classes = int(logits.shape[1])
+                                acc = torch.zeros((classes, H, W), dtype=torch.float32, device=dev)
+                                wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
+                            elif logits.shape[1] != classes:
+                                raise StcdError("the number of classes changed between batches, views or models")
+                            logits = logits.float().contiguous()
+                            _lib.check(l.stcd_scene_stitch_d4(_ptr(logits), classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
+                                                              _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
+            mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            prob = torch.empty((H, W), dtype=torch.float32, device=dev) if return_prob else None
+            cm = torch.zeros(4, dtype=torch.int64, device=dev) if lab is not None else None
+            _lib.check(l.stcd_scene_finalize(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(threshold), _ptr(lab), _ptr(mask), _ptr(prob),
+                                             _ptr(cm), stream))
+    finally:
+        for m, was in zip(models, was_training):
+            m.train(was)
+    cm_host = cm.cpu().numpy().reshape(2, 2) if cm is not None else None
+    return SceneResult(mask, prob, cm_host, scores_from_cm(cm_host) if cm_host is not None else None)
+
+
+def predict_scene_heads(model, scene_a, scene_b, tile: int = 256, stride: Optional[int] = None, batch: int = 16, window: str = "flat",
+                        label=None, label_a=None, label_b=None, threshold: float = 0.0, seg_threshold: float = 0.0,
+                        return_prob: bool = False, mean: Sequence[float] = MEAN, std: Sequence[float] = STD, tta=None) -> SceneHeads:
+    """``predict_scene`` that keeps all three maps of ``SegCD`` / ``FFCTLCD``, ``(mask_t1, mask_t2, change)``
+    (decoders/unet/model.py:316-332): every forward must return a tuple or list of exactly three equally shaped
+    ``[n,1|2,tile,tile]`` maps; anything else (a bare tensor, BIT's one-element list, ChangeFormer's five) is a ``StcdError``
+    naming what came back.  One ``stcd_scene_stitch_heads_d4`` launch per batch adds the three maps into one
+    ``acc [3*classes,H,W]`` over one ``wsum``, and one ``stcd_scene_finalize_seg`` turns them into ``seg_a``, ``seg_b``, ``change``
+    and ``gated = change & (seg_a != seg_b)``, the decision-level gate of train_stcd.py:170-176.  ``threshold`` applies to the
+    change map and ``seg_threshold`` to the two building maps of one-class models.  ``label`` (change), ``label_a`` and
+    ``label_b`` (buildings per date) are independent optional uint8 ``[H,W]`` maps (>= 1 is set, 255 is ignored): ``cm`` and
+    ``scores`` hold ``"change"`` and ``"gated"`` with ``label``, ``"seg_a"`` with ``label_a``, ``"seg_b"`` with ``label_b``.
+
+    Everything else is ``predict_scene``'s contract (modes, order of models, views and batches, errors before the first launch, no
+    CPU fallback), and ``change`` is bit-equal to ``predict_scene(...).mask`` for the same arguments."""
+    from .modules import frozen_weights
+
+    views = parse_tta(tta)
+    a, b = _scene_tensor(scene_a, "scene_a"), _scene_tensor(scene_b, "scene_b")
+    if a.shape != b.shape:
+        raise StcdError(f"the scenes differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    plan, batch, win = _tile_args(H, W, tile, stride, batch, window, mean, std)
+    labs = [_label_tensor(t, name, H, W) for t, name in ((label_a, "label_a"), (label_b, "label_b"), (label, "label"))]
+    models = _model_list(model)                                               # the device last: the other errors show without a GPU
+    dev = next(iter(models[0].parameters())).device
+    # everything is checked: from here on the device works
+    a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
+    labs = [None if t is None else t.to(dev).contiguous() for t in labs]
+    win = None if window == "flat" else torch.from_numpy(win).to(dev)         # NULL window: all ones
+
+    l = _lib.lib()
+    T, S = plan.tile, plan.stride
+    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    was_training = [m.training for m in models]
+    try:
+        with torch.cuda.device(dev), torch.no_grad():
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            x1 = torch.empty((batch, 3, T, T), dtype=torch.float32, device=dev)       # reused by every batch
+            x2 = torch.empty_like(x1)
+            acc = wsum = None
+            classes = 0
+            for m in models:
+                m.eval()
+                with frozen_weights(m):
+                    for d4 in views:
+                        for first in range(0, plan.n, batch):
+                            n = min(batch, plan.n - first)
+                            _lib.check(l.stcd_scene_gather_d4(_ptr(a), _ptr(b), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(x1), _ptr(x2),
+                                                              d4, stream))
+                            out = m(x1[:n], x2[:n])
+                            if not isinstance(out, (list, tuple)) or len(out) != 3:
+                                got = f"a {type(out).__name__} of {len(out)}" if isinstance(out, (list, tuple)) else (
+                                    f"one tensor {tuple(out.shape)}" if torch.is_tensor(out) else f"a {type(out).__name__}")
+                                raise StcdError(f"predict_scene_heads needs the three maps (mask_t1, mask_t2, change) of SegCD / FFCTLCD: "
+                                                f"the model returned {got}")
+                            for h, t in enumerate(out):
+                                _check_map(t, n, T, f"map {h} as ")
+                            if len({tuple(t.shape) for t in out}) != 1:
+                                raise StcdError(f"the three maps differ in shape: {[tuple(t.shape) for t in out]}")
+                            if acc is None:
+                                classes = int(out[0].shape[1])
+                                acc = torch.zeros((3 * classes, H, W), dtype=torch.float32, device=dev)
+                                wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
+                            elif out[0].shape[1] != classes:
+                                raise StcdError("the number of classes changed between batches, views or models")
+                            heads = [t.float().contiguous() for t in out]
+                            ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in heads])
+                            _lib.check(l.stcd_scene_stitch_heads_d4(ptrs, 3, classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
+                                                                    _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
+            masks = torch.empty((4, H, W), dtype=torch.uint8, device=dev)
+            prob = torch.empty((3, H, W), dtype=torch.float32, device=dev) if return_prob else None
+            cm = torch.zeros((4, 4), dtype=torch.int64, device=dev) if any(t is not None for t in labs) else None
+            _lib.check(l.stcd_scene_finalize_seg(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(seg_threshold), C.c_float(threshold),
+                                                 _ptr(labs[0]), _ptr(labs[1]), _ptr(labs[2]), _ptr(masks[0]), _ptr(masks[1]), _ptr(masks[2]),
+                                                 _ptr(masks[3]), _ptr(prob), _ptr(cm), stream))
+    finally:
+        for m, was in zip(models, was_training):
+            m.train(was)
+    cms = {}
+    if cm is not None:
+        cm_host = cm.cpu().numpy().reshape(4, 2, 2)
+        cms = {key: cm_host[row] for row, key in enumerate(HEAD_KEYS) if labs[min(row, 2)] is not None}
+    return SceneHeads(masks[0], masks[1], masks[2], masks[3], prob, cms, {key: scores_from_cm(v) for key, v in cms.items()})

@@ -10,8 +10,9 @@ sigmoid, a compare, an ``.int()``, a ``.cpu()`` and a host ``bincount``; here on
 drivers copy back once per ``flush`` batches.
 
 ``scene_round`` is the same round over one pair of whole scenes instead of pre-cut crops: every checkpoint goes through
-``scene.predict_scene``, ``stcd_scene_cell_agree`` counts the agreement per cell of the scene, ``stcd_mask_close`` is the 5 x 5 closing of
-the pseudo-label (train_stcd.py:186-188), and ``export_cells`` writes the tile set and the two lists.
+``scene.predict_scene`` (``gate="seg"``: ``scene.predict_scene_heads`` and its gated mask, train_stcd.py:170-176),
+``stcd_scene_cell_agree`` counts the agreement per cell of the scene, ``stcd_mask_close`` is the 5 x 5 closing of the pseudo-label
+(train_stcd.py:186-188), and ``export_cells`` writes the tile set and the two lists.
 
 ``reliability``, ``split_reliable``, ``write_lists`` and ``cell_grid`` are host-only and need no GPU.
 """
@@ -332,6 +333,8 @@ class SceneRound(NamedTuple):
     reliable: List[str]                 # split_reliable over the full cells only
     unreliable: List[str]
     cell: int                           # the cell edge the grid was cut with
+    seg_a: Optional[torch.Tensor] = None    # gate="seg": the last checkpoint's building mask of scene A, uint8 [H,W], else None
+    seg_b: Optional[torch.Tensor] = None    # ... of scene B
 
 
 def cell_grid(height: int, width: int, cell: int) -> Tuple[int, int]:
@@ -408,7 +411,7 @@ def mask_close(mask: torch.Tensor, radius: int = 2, mask_value: int = 255) -> to
 
 def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stride: Optional[int] = None, batch: int = 16,
                 window: str = "flat", tta=None, threshold: float = 0.0, close_radius: int = 0, label=None, cumulative: bool = False,
-                stem: str = "scene") -> SceneRound:
+                stem: str = "scene", gate: Optional[str] = None) -> SceneRound:
     """The round of train_stcd.py:96-204 over one pair of whole uint8 ``[H,W,3]`` scenes instead of pre-cut crops.
 
     Each of the K ``models`` (1..8 modules on one GPU, earlier checkpoints first) goes through ``scene.predict_scene`` alone, in the
@@ -419,11 +422,19 @@ def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stri
     (2 is the reference's 5 x 5 closing).  With a ``label`` (uint8 ``[H,W]``, >= 1 is change, 255 is ignored) a second launch gives
     the confusion matrix of ``pseudo`` per cell; ``cm`` is their sum and ``scores`` its ``scores_from_cm``.
 
+    ``gate="seg"`` applies the decision-level gate the reference sketches at train_stcd.py:170-176,
+    ``min(|pred_B - pred_A|, change_prediction)``: every checkpoint (``SegCD`` / ``FFCTLCD``, three maps per forward) goes through
+    ``scene.predict_scene_heads`` instead and ``masks[k]`` is its ``gated = change & (seg_a != seg_b)``; agreement, closing and
+    scores then run on those masks as above, and ``seg_a`` / ``seg_b`` hold the last checkpoint's building masks.  ``gate=None``
+    is the round without the gate; any other value is an error.
+
     Cells at the right and bottom edge that are no whole square are scored and reported (``full`` is False there) but never
     listed: ``reliable`` / ``unreliable`` are ``split_reliable`` over the full cells.  The counts come back in one copy.  Every
     argument error is raised before the first launch."""
     from . import scene as _scene
 
+    if gate is not None and gate != "seg":
+        raise StcdError(f"unknown gate {gate!r} (None or 'seg')")
     models = _model_list(models)
     dev = _device_of(models)
     a, b = _scene._scene_tensor(scene_a, "scene_a"), _scene._scene_tensor(scene_b, "scene_b")
@@ -452,7 +463,13 @@ def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stri
     a, b = a.to(dev).contiguous(), b.to(dev).contiguous()       # once, not once per checkpoint
     lab = None if lab is None else lab.to(dev).contiguous()
     K = len(models)
-    masks = [predict_scene(m, a, b, tile=tile, stride=stride, batch=batch, window=window, threshold=threshold, tta=tta).mask for m in models]
+    seg_a = seg_b = None
+    if gate == "seg":
+        heads = [_scene.predict_scene_heads(m, a, b, tile=tile, stride=stride, batch=batch, window=window, threshold=threshold, tta=tta)
+                 for m in models]
+        masks, seg_a, seg_b = [h.gated for h in heads], heads[-1].seg_a, heads[-1].seg_b
+    else:
+        masks = [predict_scene(m, a, b, tile=tile, stride=stride, batch=batch, window=window, threshold=threshold, tta=tta).mask for m in models]
     agree_dev = scene_cell_agree(masks, cell)[0] if K > 1 else None
     pseudo = mask_close(masks[-1], int(close_radius), 255) if int(close_radius) > 0 else masks[-1] * 255
     cm_dev = scene_cell_agree([pseudo], cell, label=lab)[1] if lab is not None else None
@@ -468,7 +485,7 @@ def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stri
     reliable, unreliable = split_reliable([names[i] for i in listed], rel[listed])
     cm = None if cell_cm is None else cell_cm.sum(axis=(0, 1))
     return SceneRound(masks, pseudo, agree, rel.reshape(cells_y, cells_x), cell_cm, cm, None if cm is None else scores_from_cm(cm), names, full,
-                      reliable, unreliable, cell)
+                      reliable, unreliable, cell, seg_a, seg_b)
 
 
 def export_cells(round: SceneRound, scene_a, scene_b, root: str, label=None) -> None:
