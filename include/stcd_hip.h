@@ -497,6 +497,46 @@ typedef struct stcd_conv_geom {
  * outputs bit-identical to impl 1's) */
 int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, const float* w, const float* bias,
                  void* out, void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* One NAMED bf16 conv kernel with the features the engine fuses into it (stcd_op_conv launches the kernels with one group and
+ * none of them): per-channel sums of the rounded output, the ConvEpi epilogue, BatchNorm-backward sums of a data gradient.
+ * The filter is packed as stcd_op_conv packs it and the plan is the kernel's own planner's for `groups`; a combination the named
+ * kernel's planner or launcher does not take is an error -- no other kernel runs in its place, and nothing is launched.
+ * Images are ordered group by group (n % groups == 0: date-0 images first, then date-1 images). */
+enum { STCD_CONV_SMALL = 0, STCD_CONV_RES = 1, STCD_CONV_TILE = 2, STCD_CONV_GEMM = 3, STCD_CONV_HALO = 4, STCD_CONV_DMA = 5 };
+typedef struct stcd_conv_fused {
+    int32_t kernel;                 /* STCD_CONV_*: k_conv_small / _res / _tile / _gemm / _halo / _dma */
+    int32_t groups;                 /* BatchNorm groups the tiles are partitioned by (1 for halo / dma) */
+    /* sums (small, res, tile, gemm), or sum_acc == NULL: int64 [bn_rep][groups][2][sum_c] += sum(y) * sum_scale1 and
+     * sum(y^2) * sum_scale2 of the stored (rounded; gemm: ReLU'd and rounded, before gate / residual) output channels
+     * [sum_c0, sum_c0 + sum_c).  The kernels ADD.  k_conv_small: sum_c0 = 0, sum_c = co, scales 2^26 and 2^18 only. */
+    void* sum_acc;
+    int32_t sum_c0, sum_c;
+    float sum_scale1, sum_scale2;
+    /* epilogue (gemm, halo, dma), or use_epi == 0:  v = conv + bias; relu: v = max(v, 0); v = round_bf16(v);
+     * gate: v = gate > 0 ? v : 0; res: out = round_bf16(alpha * v + beta * res).  gate / res: bf16 tensors of the OUTPUT buffer's
+     * geometry [n][ho][wo] with pixel strides ldg / ldr (multiples of 8, >= co), nullable; without res alpha = beta = 1. */
+    int32_t use_epi, relu;
+    const void* gate;
+    const void* res;
+    int32_t ldg, ldr;
+    float alpha, beta;
+    /* BatchNorm-backward sums (small, res), or bw_acc == NULL: the launch is a data gradient writing dA of a conv -> BN -> ReLU ->
+     * Dropout2d layer whose conv output is bw_y (bf16, output geometry, pixel stride bw_ldy); bw_stat: fp32 [groups][4][co] (mean,
+     * invstd, scale, shift), bw_mask: fp32 [n][co] or NULL.  bw_acc: int64 [bn_rep][groups][2][co] += 2^36 * sum(dz) and
+     * 2^36 * sum(dz * (y - mean) * invstd), dz = round_bf16(dA) * mask * (y * scale + shift > 0). */
+    const void* bw_y;
+    const float* bw_stat;
+    const float* bw_mask;
+    void* bw_acc;
+    int32_t bw_ldy;
+    /* out (filled in as soon as the plan stands, before anything is launched): blocks of the grid; tiles (gemm / dma: M-tiles) one
+     * group walks; blocks that share them, i.e. the adds one accumulator entry receives; replicas of the accumulator */
+    int32_t blocks, tiles_per_group, blocks_per_group, bn_rep;
+    int32_t tile_m;                 /* gemm: positions per M-tile (128 or 64); 0 otherwise */
+} stcd_conv_fused;
+/* w: fp32 [ntaps][ci][co]; bias: fp32 [co] or NULL; scratch: stcd_op_scratch_bytes(g) */
+int stcd_op_conv_fused(const stcd_conv_geom* g, stcd_conv_fused* f, const void* in, const float* w, const float* bias, void* out,
+                       void* scratch, int64_t scratch_bytes, void* hip_stream);
 /* dw: fp32 [ntaps][ci][co], overwritten; impl: 0 = reference FMA kernel, 1 = MFMA tile kernel (4: its 64 x 32-channel tile
  * allowed for Ci >= 64, as the SNUNet engine runs it; 5: its 64 x 64-channel tile, an opt-in variant), 3 = MFMA position-GEMM kernel
  * (one tap, Ci >= 64, Co >= 64: what the engine runs for 1x1 convs and the phases of 2x2 stride-2 transposed convs),

@@ -85,6 +85,20 @@ class MapGeom(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32), ("groups", C.c_int32)]
 
 
+CONV_SMALL, CONV_RES, CONV_TILE, CONV_GEMM, CONV_HALO, CONV_DMA = range(6)      # stcd_conv_fused.kernel (STCD_CONV_*)
+
+
+class ConvFused(C.Structure):
+    """stcd_conv_fused: what stcd_op_conv_fused fuses into the named kernel (NULL pointers / use_epi = 0: not requested)."""
+    _fields_ = [("kernel", C.c_int32), ("groups", C.c_int32),
+                ("sum_acc", C.c_void_p), ("sum_c0", C.c_int32), ("sum_c", C.c_int32), ("sum_scale1", C.c_float), ("sum_scale2", C.c_float),
+                ("use_epi", C.c_int32), ("relu", C.c_int32), ("gate", C.c_void_p), ("res", C.c_void_p), ("ldg", C.c_int32), ("ldr", C.c_int32),
+                ("alpha", C.c_float), ("beta", C.c_float),
+                ("bw_y", C.c_void_p), ("bw_stat", C.c_void_p), ("bw_mask", C.c_void_p), ("bw_acc", C.c_void_p), ("bw_ldy", C.c_int32),
+                ("blocks", C.c_int32), ("tiles_per_group", C.c_int32), ("blocks_per_group", C.c_int32), ("bn_rep", C.c_int32),
+                ("tile_m", C.c_int32)]
+
+
 _vp, _i, _i64, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 _PROTOS = {
     "stcd_last_error": (C.c_char_p, []),
@@ -150,6 +164,7 @@ _PROTOS = {
     "stcd_scene_cell_agree": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "stcd_mask_close": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_op_conv_fused": (_i, [C.POINTER(ConvGeom), C.POINTER(ConvFused), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_scratch_bytes": (_i64, [C.POINTER(ConvGeom)]),
     "stcd_op_ew_scratch_bytes": (_i64, [C.POINTER(MapGeom)]),

@@ -3734,6 +3734,96 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
     STCD_HIP(hipGetLastError());
     return 0;
 }
+// One named kernel with what the engine fuses into it (exec_conv's arguments, spelled out by the caller).  Everything is validated
+// with the kernel's own planner and its launcher's own predicates BEFORE the filter is packed, so a refused combination launches
+// nothing; the out-values are written as soon as the plan stands.
+int stcd_op_conv_fused(const stcd_conv_geom* g, stcd_conv_fused* f, const void* in, const float* w, const float* bias, void* out,
+                       void* scratch, int64_t scratch_bytes, void* hip_stream) {
+    if (check_geom(g)) return 1;
+    STCD_CHECK(f != nullptr, "the fused-features request is null");
+    f->blocks = f->tiles_per_group = f->blocks_per_group = f->tile_m = 0;
+    f->bn_rep = BN_REP;
+    STCD_CHECK(in && w && out, "null pointer argument");
+    STCD_CHECK(f->kernel >= STCD_CONV_SMALL && f->kernel <= STCD_CONV_DMA, "kernel must be one of STCD_CONV_*");
+    const int groups = f->groups;
+    STCD_CHECK(groups >= 1 && g->n % groups == 0, "groups must be >= 1 and divide n (whole images per BatchNorm group)");
+    const bool sums = f->sum_acc != nullptr, epi_on = f->use_epi != 0, bwd = f->bw_acc != nullptr;
+    const bool k_small = f->kernel == STCD_CONV_SMALL, k_res = f->kernel == STCD_CONV_RES, k_tile = f->kernel == STCD_CONV_TILE;
+    const bool k_gemm = f->kernel == STCD_CONV_GEMM, k_halo = f->kernel == STCD_CONV_HALO, k_dma = f->kernel == STCD_CONV_DMA;
+    STCD_CHECK(!sums || k_small || k_res || k_tile || k_gemm, "fused sums: k_conv_small, k_conv_res, k_conv_tile and k_conv_gemm only");
+    STCD_CHECK(!epi_on || k_gemm || k_halo || k_dma, "ConvEpi: k_conv_gemm, k_conv_halo and k_conv_dma only");
+    STCD_CHECK(!bwd || k_small || k_res, "BatchNorm-backward sums: k_conv_small and k_conv_res only");
+    STCD_CHECK(!(k_halo || k_dma) || groups == 1, "k_conv_halo and k_conv_dma know one group");
+    STCD_CHECK(!(bwd && sums), "a data gradient with BatchNorm-backward sums carries no forward sums");
+    if (sums) {
+        STCD_CHECK(f->sum_c0 >= 0 && f->sum_c >= 1 && f->sum_c0 + f->sum_c <= g->co, "the summed channel slice lies outside the output channels");
+        STCD_CHECK(f->sum_scale1 > 0.f && f->sum_scale2 > 0.f, "the sum scales must be positive");
+        STCD_CHECK(!k_small || (f->sum_c0 == 0 && f->sum_c == g->co && f->sum_scale1 == BN_FS1 && f->sum_scale2 == BN_FS2),
+                   "k_conv_small sums all its channels at the BatchNorm scales (2^26, 2^18)");
+    }
+    ConvEpi epi;
+    if (epi_on) {
+        STCD_CHECK(!f->gate || (f->ldg >= g->co && f->ldg % 8 == 0), "gate: the pixel stride must be a multiple of 8 and >= co");
+        STCD_CHECK(!f->res || (f->ldr >= g->co && f->ldr % 8 == 0), "res: the pixel stride must be a multiple of 8 and >= co");
+        STCD_CHECK(f->res || (f->alpha == 1.f && f->beta == 1.f), "alpha / beta combine the output with a residual: without one they must be 1");
+        epi.relu = f->relu ? 1 : 0;
+        epi.gate = f->gate; epi.ldg = f->ldg; epi.res = f->res; epi.ldr = f->ldr; epi.alpha = f->alpha; epi.beta = f->beta;
+    }
+    BwdSum bs;
+    if (bwd) {
+        STCD_CHECK(f->bw_y && f->bw_stat, "BatchNorm-backward sums need the layer's conv output and its statistics");
+        STCD_CHECK(f->bw_ldy >= g->co && f->bw_ldy % 4 == 0, "bw_y: the pixel stride must be a multiple of 4 and >= co");
+        bs.Y = f->bw_y; bs.ldy = f->bw_ldy; bs.stat = f->bw_stat; bs.mask = f->bw_mask; bs.acc = (long long*)f->bw_acc; bs.groups = groups;
+    }
+    const ConvMfmaPlan p = conv_mfma_plan(*g);
+    STCD_CHECK(p.ok, "geometry not supported by the MFMA kernels");
+    STCD_CHECK(scratch && scratch_bytes >= p.wf_elems * 2, "scratch too small for the fragment-order filter");
+    hipStream_t s = (hipStream_t)hip_stream;
+    long long* const acc = (long long*)f->sum_acc;
+    const int sC = sums ? f->sum_c : g->co, sc0 = sums ? f->sum_c0 : 0;
+    const float s1 = sums ? f->sum_scale1 : BN_FS1, s2 = sums ? f->sum_scale2 : BN_FS2;
+    const int64_t tiles16 = (int64_t)g->n * ((g->hm + 15) / 16) * ((g->wm + 15) / 16);
+    ConvResPlan rp; ConvTilePlan tp; ConvGemmPlan gp; ConvHaloPlan hp; ConvDmaPlan dp;
+    if (k_small) {
+        STCD_CHECK(conv_small_ok(*g, p) && conv_small_call_ok(*g, groups, nullptr), "geometry not supported by k_conv_small (one n-tile, <= 5 k-steps)");
+        STCD_CHECK(!bwd || conv_small_bwdsum_ok(*g), "k_conv_small forms BatchNorm-backward sums for 16 channels out, whole 8 x 16 tiles, 3 or 5 k-steps");
+        f->blocks = conv_small_blocks(*g, groups);
+        f->blocks_per_group = f->blocks / groups;
+        f->tiles_per_group = (int)((int64_t)g->n * ((g->hm + 7) / 8) * ((g->wm + 15) / 16) / groups);
+    } else if (k_res) {
+        rp = conv_res_plan(*g, p, groups);
+        STCD_CHECK(rp.ok, "geometry not supported by k_conv_res (3x3 stride 1, Ci % 32 == 0)");
+        STCD_CHECK(!bwd || conv_res_bwdsum_ok(*g, rp), "this k_conv_res plan forms no BatchNorm-backward sums (slices of one or two n-tiles, double halo)");
+        f->blocks = rp.blocks; f->blocks_per_group = rp.P; f->tiles_per_group = (int)(tiles16 / groups);
+    } else if (k_tile) {
+        tp = conv_tile_plan(*g, p, groups);
+        STCD_CHECK(tp.ok, "geometry not supported by k_conv_tile (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
+        f->blocks = tp.blocks; f->blocks_per_group = tp.P; f->tiles_per_group = (int)(tiles16 / groups);
+    } else if (k_gemm) {
+        gp = conv_gemm_plan(*g, p, groups);
+        STCD_CHECK(gp.ok, "geometry not supported by k_conv_gemm (Ci % 64 == 0, Co % 64 == 0)");
+        f->blocks = gp.blocks; f->blocks_per_group = gp.tiles_m; f->tiles_per_group = gp.tiles_m; f->tile_m = 32 * gp.W;
+    } else if (k_halo) {
+        hp = conv_halo_plan(*g, p);
+        STCD_CHECK(hp.ok, "geometry not supported by k_conv_halo (3x3 stride 1, Ci % 128 == 0, Co % 128 == 0)");
+        f->blocks = hp.blocks; f->blocks_per_group = hp.P; f->tiles_per_group = (int)tiles16;
+    } else {
+        dp = conv_dma_plan(*g, p);
+        STCD_CHECK(dp.ok, "geometry not supported by k_conv_dma (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
+        f->blocks = dp.blocks; f->blocks_per_group = std::min(dp.blocks, dp.tiles_m); f->tiles_per_group = dp.tiles_m;
+    }
+    launch_pack_frag(*g, p, w, g->ci, g->co, scratch, s);
+    int rc = 1;
+    if (k_small) rc = launch_conv_small(*g, in, scratch, bias, out, false, groups, acc, sC, s, nullptr, bwd ? &bs : nullptr);
+    else if (k_res) rc = launch_conv_res(*g, p, rp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2, nullptr, bwd ? &bs : nullptr);
+    else if (k_tile) rc = launch_conv_tile(*g, p, tp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2);
+    else if (k_gemm) rc = launch_conv_gemm(*g, p, gp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2, epi_on ? &epi : nullptr);
+    else if (k_halo) rc = launch_conv_halo(*g, p, hp, in, scratch, bias, out, s, epi_on ? &epi : nullptr);
+    else rc = launch_conv_dma(*g, p, dp, in, scratch, bias, out, s, epi_on ? &epi : nullptr);
+    STCD_CHECK(rc == 0, "the named kernel's launcher rejected the combination");
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
 int stcd_op_wgrad(int dtype, int impl, const stcd_conv_geom* g, const void* in, const void* dout, float* dw, void* scratch,
                   int64_t scratch_bytes, void* hip_stream) {
     if (check_geom(g)) return 1;
