@@ -24,13 +24,15 @@ void set_error(const std::string& msg);
 static inline int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static inline bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v && v[0] == (dflt ? '0' : '1') ? !dflt : dflt; }
 
-#define STCD_CHECK(cond, msg)                                              \
+// fn: the name the message starts with; checks that several entries share report under the entry's name
+#define STCD_CHECK_AS(fn, cond, msg)                                       \
     do {                                                                   \
         if (!(cond)) {                                                     \
-            ::stcd::set_error(std::string(__func__) + ": " + (msg));       \
+            ::stcd::set_error(std::string(fn) + ": " + (msg));             \
             return 1;                                                      \
         }                                                                  \
     } while (0)
+#define STCD_CHECK(cond, msg) STCD_CHECK_AS(__func__, cond, msg)
 
 #define STCD_HIP(call)                                                                        \
     do {                                                                                      \
@@ -610,29 +612,21 @@ void launch_augment(const float* x, const float* params, int N, int H, int W, co
 int64_t augment_scratch_bytes(int N, int H, int W);
 void launch_confusion(const float* logits, const int64_t* target, int B, int Cn, int64_t HW, int64_t* cm,
                       hipStream_t s);
-// whole-scene inference (kernels_scene.hip): the callers have validated the tile grid and the tile range
-void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
-                         const float* mean, const float* std_, float* x1, float* x2, hipStream_t s);
-void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
-                         const float* window, float* acc, float* wsum, hipStream_t s);
-void launch_scene_finalize(const float* acc, const float* wsum, int classes, int H, int W, float threshold, const uint8_t* label,
-                           uint8_t* mask, float* prob, int64_t* cm, hipStream_t s);
-// the D4 views of the two (d4 in 0..7: bit 0 mirrors columns, bit 1 rows, bit 2 transposes, last); d4 == 0 is the launch above
+// whole-scene inference (kernels_scene.hip): the callers have validated the tile grid and the tile range.  d4 in 0..7: bit 0 mirrors
+// columns, bit 1 rows, bit 2 transposes, last; 0 is the upright view.  The gather takes one scene (UnetSeg) with B == x2 == NULL, the
+// stitch 1..STCD_SCENE_MAX_HEADS heads of one forward (SegCD's three maps): the same kernels, so the same bits per scene and per head;
+// the heads' device pointers travel by value, acc is [n_heads * classes, H, W] over one wsum
 void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
                             const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s);
-void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
-                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s);
-// one scene (UnetSeg) and several heads of one forward (SegCD's three maps): the same kernels, so the same bits per scene and per head;
-// the heads' device pointers travel by value, acc is [n_heads * classes, H, W] over one wsum
-void launch_scene_gather_one_d4(const uint8_t* A, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles, const float* mean,
-                                const float* std_, float* x, int d4, hipStream_t s);
 struct SceneHeadPtrs { const float* p[STCD_SCENE_MAX_HEADS]; };
 void launch_scene_stitch_heads_d4(const SceneHeadPtrs& lg, int n_heads, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y,
                                   int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s);
+void launch_scene_finalize(const float* acc, const float* wsum, int classes, int H, int W, float threshold, const uint8_t* label,
+                           uint8_t* mask, float* prob, int64_t* cm, hipStream_t s);
 void launch_scene_finalize_seg(const float* acc, const float* wsum, int classes, int H, int W, float seg_threshold, float change_threshold,
                                const uint8_t* label_a, const uint8_t* label_b, const uint8_t* label_c, uint8_t* seg_a, uint8_t* seg_b,
                                uint8_t* change, uint8_t* gated, float* prob, int64_t* cm, hipStream_t s);
-// the tile-grid checks shared by every stcd_scene_* entry (engine.hip, ops_abi.hip); tiles per axis: max(0, ceil((L - T) / S)) + 1
+// the tile-grid checks shared by every stcd_scene_* entry (ops_abi.hip); tiles per axis: max(0, ceil((L - T) / S)) + 1
 inline int scene_tiles(int L, int T, int S) { return (L > T ? (int)(((int64_t)L - T + S - 1) / S) : 0) + 1; }
 inline int check_scene_grid(int height, int width, int tile, int stride, int tiles_x, int tiles_y, int first_tile, int n_tiles) {
     STCD_CHECK(height >= 1 && width >= 1 && tile >= 1, "bad shape");

@@ -3558,38 +3558,6 @@ int stcd_augment(const float* x, const float* params, int n_images, int height, 
     return 0;
 }
 
-int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
-                      int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, void* hip_stream) {
-    STCD_CHECK(scene_a && scene_b && mean3 && std3 && x1 && x2, "null pointer argument");
-    if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
-        return 1;
-    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
-    launch_scene_gather(scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2,
-                        (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
-    return 0;
-}
-int stcd_scene_stitch(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
-                      int first_tile, int n_tiles, const float* window, float* acc, float* wsum, void* hip_stream) {
-    STCD_CHECK(logits && acc && wsum, "null pointer argument");
-    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
-    if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
-    launch_scene_stitch(logits, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
-                        (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
-    return 0;
-}
-int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold, const uint8_t* label,
-                        uint8_t* mask, float* prob, int64_t* cm, void* hip_stream) {
-    STCD_CHECK(acc && wsum && mask, "null pointer argument");
-    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
-    STCD_CHECK(height >= 1 && width >= 1, "bad shape");
-    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
-    launch_scene_finalize(acc, wsum, classes, height, width, threshold, label, mask, prob, cm, (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
-    return 0;
-}
-
 int stcd_selftrain_score(const float* const* logits, int n_models, int batch, int classes, int64_t hw, float threshold, const uint8_t* label,
                          int mask_value, uint8_t* mask, int64_t* agree, int64_t* cm, void* hip_stream) {
     STCD_CHECK(logits && mask, "null pointer argument");
@@ -3606,28 +3574,6 @@ int stcd_selftrain_score(const float* const* logits, int n_models, int batch, in
     STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
     if (batch == 0 || hw == 0) return 0;
     launch_selftrain_score(lg, n_models, batch, classes, hw, threshold, label, mask_value, mask, agree, cm, (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
-    return 0;
-}
-
-int stcd_scene_cell_agree(const uint8_t* const* masks, int n_models, int height, int width, int cell, int cells_x, int cells_y,
-                          const uint8_t* label, int64_t* agree, int64_t* cm, void* hip_stream) {
-    STCD_CHECK(masks != nullptr, "null pointer argument");
-    STCD_CHECK(n_models >= 1 && n_models <= STCD_SELFTRAIN_MAX_MODELS, "n_models must be in [1, 8]");
-    SceneMaskPtrs mk{};
-    for (int k = 0; k < n_models; ++k) {
-        STCD_CHECK(masks[k] != nullptr, "a mask pointer is null");
-        mk.p[k] = masks[k];
-    }
-    STCD_CHECK(height >= 0 && width >= 0, "bad shape");
-    STCD_CHECK(cell >= 1, "cell must be >= 1");
-    STCD_CHECK(cells_x == (int)(((int64_t)width + cell - 1) / cell), "cells_x is not ceil(width / cell)");
-    STCD_CHECK(cells_y == (int)(((int64_t)height + cell - 1) / cell), "cells_y is not ceil(height / cell)");
-    STCD_CHECK((agree == nullptr) == (n_models == 1), "agree is NULL if and only if n_models == 1");
-    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
-    STCD_CHECK(n_models > 1 || label != nullptr, "one model and no label: nothing to compute");
-    if (height == 0 || width == 0) return 0;
-    launch_scene_cell_agree(mk, n_models, height, width, cell, cells_x, cells_y, label, agree, cm, (hipStream_t)hip_stream);
     STCD_HIP(hipGetLastError());
     return 0;
 }

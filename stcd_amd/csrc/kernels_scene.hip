@@ -255,19 +255,13 @@ static void scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, in
     }
 }
 
+// B == NULL (and then x2 == NULL) is the one-scene gather
 void launch_scene_gather_d4(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
                             const float* mean, const float* std_, float* x1, float* x2, int d4, hipStream_t s) {
-    scene_gather_d4<true>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, d4, s);
-}
-
-void launch_scene_gather_one_d4(const uint8_t* A, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles, const float* mean,
-                                const float* std_, float* x, int d4, hipStream_t s) {
-    scene_gather_d4<false>(A, nullptr, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x, nullptr, d4, s);
-}
-
-void launch_scene_gather(const uint8_t* A, const uint8_t* B, int H, int W, int T, int S, int tiles_x, int first_tile, int n_tiles,
-                         const float* mean, const float* std_, float* x1, float* x2, hipStream_t s) {
-    launch_scene_gather_d4(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, 0, s);
+    if (B)
+        scene_gather_d4<true>(A, B, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, x2, d4, s);
+    else
+        scene_gather_d4<false>(A, nullptr, H, W, T, S, tiles_x, first_tile, n_tiles, mean, std_, x1, nullptr, d4, s);
 }
 
 // ------------------------------------------------------------------ stitch: acc += w * logit, wsum += w, per scene pixel
@@ -558,18 +552,6 @@ void launch_scene_stitch_heads_d4(const SceneHeadPtrs& lg, int n_heads, int clas
 #undef STCD_STITCH_ROWS
 }
 #undef STCD_STITCH_SHAPES
-
-void launch_scene_stitch_d4(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile,
-                            int n_tiles, const float* window, float* acc, float* wsum, int d4, hipStream_t s) {
-    SceneHeadPtrs lg{};
-    lg.p[0] = logits;
-    launch_scene_stitch_heads_d4(lg, 1, classes, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, d4, s);
-}
-
-void launch_scene_stitch(const float* logits, int classes, int H, int W, int T, int S, int tiles_x, int tiles_y, int first_tile, int n_tiles,
-                         const float* window, float* acc, float* wsum, hipStream_t s) {
-    launch_scene_stitch_d4(logits, classes, H, W, T, S, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, 0, s);
-}
 
 // ------------------------------------------------------------------ finalize: mask, optional probability, optional confusion matrix
 template <int CLS>

@@ -1,4 +1,5 @@
-// ops_abi.hip -- per-op C-ABI entry points of the normalisation / pooling / fusion kernels (include/stcd_hip.h).
+// ops_abi.hip -- per-op C-ABI entry points of the normalisation / pooling / fusion kernels and every stcd_scene_* entry
+// (include/stcd_hip.h).
 //
 // These run EXACTLY the launch sequences the engine runs for one layer (statistics -> finalize -> apply, ...), on
 // caller-provided NHWC tensors, so the parity tests can pin every elementwise kernel against the reference's per-op
@@ -231,60 +232,84 @@ int stcd_op_skip_bwd(int dtype, int mode, const stcd_map_geom* g, const void* a,
     return 0;
 }
 
-// ---- the D4 views of the whole-scene gather and stitch (kernels_scene.hip): test-time augmentation without a host permutation.
-//      d4 is checked first; the other checks are those of stcd_scene_gather / stcd_scene_stitch (engine.hip).
-int stcd_scene_gather_d4(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
-                         int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, int d4,
-                         void* hip_stream) {
-    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
-    STCD_CHECK(scene_a && scene_b && mean3 && std3 && x1 && x2, "null pointer argument");
+// ---- whole-scene inference (kernels_scene.hip): every gather entry is scene_gather and every stitch entry scene_stitch, so each
+//      check stands once and reports under the entry's name.  d4 is checked first; the entries without the argument pass 0, the
+//      upright view.
+// pair: two scenes into x1 and x2; otherwise scene_b and x2 are not looked at and scene_a alone goes into x1
+static int scene_gather(const char* entry, bool pair, const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile,
+                        int stride, int tiles_x, int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2,
+                        int d4, void* hip_stream) {
+    STCD_CHECK_AS(entry, d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK_AS(entry, scene_a && (!pair || (scene_b && x2)) && mean3 && std3 && x1, "null pointer argument");
     if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
         return 1;
-    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
-    launch_scene_gather_d4(scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2, d4,
-                           (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
+    STCD_CHECK_AS(entry, std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
+    launch_scene_gather_d4(scene_a, pair ? scene_b : nullptr, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1,
+                           pair ? x2 : nullptr, d4, (hipStream_t)hip_stream);
+    const hipError_t err = hipGetLastError();
+    STCD_CHECK_AS(entry, err == hipSuccess, std::string("hipGetLastError(): ") + hipGetErrorString(err));
     return 0;
 }
-int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
-                         int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, void* hip_stream) {
-    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
-    STCD_CHECK(logits && acc && wsum, "null pointer argument");
-    STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
+// logits: host array of n_heads device pointers; the single-head entries pass the address of their one pointer, or NULL if that is NULL
+static int scene_stitch(const char* entry, const float* const* logits, int n_heads, int classes, int height, int width, int tile, int stride,
+                        int tiles_x, int tiles_y, int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4,
+                        void* hip_stream) {
+    STCD_CHECK_AS(entry, d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
+    STCD_CHECK_AS(entry, logits && acc && wsum, "null pointer argument");
+    STCD_CHECK_AS(entry, n_heads >= 1 && n_heads <= STCD_SCENE_MAX_HEADS, "n_heads must be in [1, 3]");
+    SceneHeadPtrs lg{};
+    for (int h = 0; h < n_heads; ++h) {
+        STCD_CHECK_AS(entry, logits[h] != nullptr, "a logits pointer is null");
+        lg.p[h] = logits[h];
+    }
+    STCD_CHECK_AS(entry, classes == 1 || classes == 2, "classes must be 1 or 2");
     if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
-    launch_scene_stitch_d4(logits, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum, d4,
-                           (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
+    launch_scene_stitch_heads_d4(lg, n_heads, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
+                                 d4, (hipStream_t)hip_stream);
+    const hipError_t err = hipGetLastError();
+    STCD_CHECK_AS(entry, err == hipSuccess, std::string("hipGetLastError(): ") + hipGetErrorString(err));
     return 0;
 }
 
-// ---- one scene (UnetSeg) and the three maps of SegCD's forward: the kernels of the entries above with one scene / several heads
+int stcd_scene_gather(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                      int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, void* hip_stream) {
+    return scene_gather(__func__, true, scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2, 0,
+                        hip_stream);
+}
+int stcd_scene_gather_d4(const uint8_t* scene_a, const uint8_t* scene_b, int height, int width, int tile, int stride, int tiles_x,
+                         int first_tile, int n_tiles, const float* mean3, const float* std3, float* x1, float* x2, int d4,
+                         void* hip_stream) {
+    return scene_gather(__func__, true, scene_a, scene_b, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x1, x2, d4,
+                        hip_stream);
+}
 int stcd_scene_gather_one_d4(const uint8_t* scene, int height, int width, int tile, int stride, int tiles_x, int first_tile, int n_tiles,
                              const float* mean3, const float* std3, float* x, int d4, void* hip_stream) {
-    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
-    STCD_CHECK(scene && mean3 && std3 && x, "null pointer argument");
-    if (check_scene_grid(height, width, tile, stride, tiles_x, stride >= 1 && tile >= 1 ? scene_tiles(height, tile, stride) : 0, first_tile, n_tiles))
-        return 1;
-    STCD_CHECK(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "std must be positive");
-    launch_scene_gather_one_d4(scene, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x, d4, (hipStream_t)hip_stream);
-    STCD_HIP(hipGetLastError());
-    return 0;
+    return scene_gather(__func__, false, scene, nullptr, height, width, tile, stride, tiles_x, first_tile, n_tiles, mean3, std3, x, nullptr,
+                        d4, hip_stream);
+}
+int stcd_scene_stitch(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                      int first_tile, int n_tiles, const float* window, float* acc, float* wsum, void* hip_stream) {
+    return scene_stitch(__func__, logits ? &logits : nullptr, 1, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles,
+                        window, acc, wsum, 0, hip_stream);
+}
+int stcd_scene_stitch_d4(const float* logits, int classes, int height, int width, int tile, int stride, int tiles_x, int tiles_y,
+                         int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4, void* hip_stream) {
+    return scene_stitch(__func__, logits ? &logits : nullptr, 1, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles,
+                        window, acc, wsum, d4, hip_stream);
 }
 int stcd_scene_stitch_heads_d4(const float* const* logits, int n_heads, int classes, int height, int width, int tile, int stride, int tiles_x,
                                int tiles_y, int first_tile, int n_tiles, const float* window, float* acc, float* wsum, int d4,
                                void* hip_stream) {
-    STCD_CHECK(d4 >= 0 && d4 <= 7, "d4 must be in [0, 7]");
-    STCD_CHECK(logits && acc && wsum, "null pointer argument");
-    STCD_CHECK(n_heads >= 1 && n_heads <= STCD_SCENE_MAX_HEADS, "n_heads must be in [1, 3]");
-    SceneHeadPtrs lg{};
-    for (int h = 0; h < n_heads; ++h) {
-        STCD_CHECK(logits[h] != nullptr, "a logits pointer is null");
-        lg.p[h] = logits[h];
-    }
+    return scene_stitch(__func__, logits, n_heads, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc,
+                        wsum, d4, hip_stream);
+}
+int stcd_scene_finalize(const float* acc, const float* wsum, int classes, int height, int width, float threshold, const uint8_t* label,
+                        uint8_t* mask, float* prob, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(acc && wsum && mask, "null pointer argument");
     STCD_CHECK(classes == 1 || classes == 2, "classes must be 1 or 2");
-    if (check_scene_grid(height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles)) return 1;
-    launch_scene_stitch_heads_d4(lg, n_heads, classes, height, width, tile, stride, tiles_x, tiles_y, first_tile, n_tiles, window, acc, wsum,
-                                 d4, (hipStream_t)hip_stream);
+    STCD_CHECK(height >= 1 && width >= 1, "bad shape");
+    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
+    launch_scene_finalize(acc, wsum, classes, height, width, threshold, label, mask, prob, cm, (hipStream_t)hip_stream);
     STCD_HIP(hipGetLastError());
     return 0;
 }
@@ -297,6 +322,29 @@ int stcd_scene_finalize_seg(const float* acc, const float* wsum, int classes, in
     STCD_CHECK((label_a || label_b || label_c) == (cm != nullptr), "cm goes with at least one label");
     launch_scene_finalize_seg(acc, wsum, classes, height, width, seg_threshold, change_threshold, label_a, label_b, label_c, seg_a, seg_b,
                               change, gated, prob, cm, (hipStream_t)hip_stream);
+    STCD_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- the round on whole scenes (kernels_scene_round.hip)
+int stcd_scene_cell_agree(const uint8_t* const* masks, int n_models, int height, int width, int cell, int cells_x, int cells_y,
+                          const uint8_t* label, int64_t* agree, int64_t* cm, void* hip_stream) {
+    STCD_CHECK(masks != nullptr, "null pointer argument");
+    STCD_CHECK(n_models >= 1 && n_models <= STCD_SELFTRAIN_MAX_MODELS, "n_models must be in [1, 8]");
+    SceneMaskPtrs mk{};
+    for (int k = 0; k < n_models; ++k) {
+        STCD_CHECK(masks[k] != nullptr, "a mask pointer is null");
+        mk.p[k] = masks[k];
+    }
+    STCD_CHECK(height >= 0 && width >= 0, "bad shape");
+    STCD_CHECK(cell >= 1, "cell must be >= 1");
+    STCD_CHECK(cells_x == (int)(((int64_t)width + cell - 1) / cell), "cells_x is not ceil(width / cell)");
+    STCD_CHECK(cells_y == (int)(((int64_t)height + cell - 1) / cell), "cells_y is not ceil(height / cell)");
+    STCD_CHECK((agree == nullptr) == (n_models == 1), "agree is NULL if and only if n_models == 1");
+    STCD_CHECK((label != nullptr) == (cm != nullptr), "label and cm go together");
+    STCD_CHECK(n_models > 1 || label != nullptr, "one model and no label: nothing to compute");
+    if (height == 0 || width == 0) return 0;
+    launch_scene_cell_agree(mk, n_models, height, width, cell, cells_x, cells_y, label, agree, cm, (hipStream_t)hip_stream);
     STCD_HIP(hipGetLastError());
     return 0;
 }

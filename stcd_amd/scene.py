@@ -16,10 +16,15 @@ network's output for that view back through the inverse, so no tile or logit is 
 two building masks, the change mask and the decision-level gate of train_stcd.py:170-176), and ``predict_scene_seg`` runs a
 one-input network such as ``UnetSeg`` over one scene (``stcd_scene_gather_one_d4``).
 
+The three entry points share one checker (``_check_args``) and one tile loop (``_stitched``), which always gathers through a
+``_d4`` entry (view 0 is the upright one) and stitches through ``stcd_scene_stitch_heads_d4`` with one head or three: the
+single-head entries of the header are that kernel with one head, so the bits are theirs.
+
 ``plan_tiles``, ``window_table`` and ``parse_tta`` are host-only and need no GPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import NamedTuple, Optional, Sequence
 
@@ -105,21 +110,50 @@ def parse_tta(tta) -> tuple:
 
 
 def _model_list(model) -> list:
-    """One module or a non-empty list / tuple of at most MAX_MODELS modules, all on one GPU."""
-    models = list(model) if isinstance(model, (list, tuple)) else [model]
+    """A module is one model, anything else is iterated: 1..MAX_MODELS modules.  Where they are is ``_device_of``'s to check."""
+    if isinstance(model, torch.nn.Module):
+        models = [model]
+    else:
+        try:
+            models = list(model)
+        except TypeError:
+            raise StcdError(f"a model must be a torch.nn.Module, got {type(model).__name__}") from None
     if not 1 <= len(models) <= MAX_MODELS:
         raise StcdError(f"between 1 and {MAX_MODELS} models, got {len(models)}")
-    devs = []
     for m in models:
         if not isinstance(m, torch.nn.Module):
             raise StcdError(f"a model must be a torch.nn.Module, got {type(m).__name__}")
+    return models
+
+
+def _device_of(models, who: str = "predict_scene") -> torch.device:
+    """The one GPU that every model's parameters are on; ``who`` is the caller the no-CPU-fallback error names."""
+    devs = []
+    for m in models:
         prm = next(iter(m.parameters()), None)
         devs.append(None if prm is None else prm.device)
     if any(d != devs[0] for d in devs):
         raise StcdError(f"the models are on different devices: {[str(d) for d in devs]}")
     if devs[0] is None or devs[0].type != "cuda":
-        raise StcdError("predict_scene runs on the GPU: move the model there first (no CPU fallback)")
-    return models
+        raise StcdError(f"{who} runs on the GPU: move the model there first (no CPU fallback)")
+    return devs[0]
+
+
+@contextlib.contextmanager
+def _evaluating(models):
+    """eval(), no_grad and frozen_weights for every model; the previous modes come back on exit, also on error."""
+    from .modules import frozen_weights
+    was = [m.training for m in models]
+    try:
+        with contextlib.ExitStack() as stack:
+            stack.enter_context(torch.no_grad())
+            for m in models:
+                m.eval()
+                stack.enter_context(frozen_weights(m))
+            yield
+    finally:
+        for m, w in zip(models, was):
+            m.train(w)
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -141,9 +175,131 @@ def _scene_tensor(scene, name: str) -> torch.Tensor:
     return scene
 
 
+def _label_tensor(label, name: str, H: int, W: int) -> Optional[torch.Tensor]:
+    """Checks only, as ``_scene_tensor``: None stays None."""
+    if label is None:
+        return None
+    lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
+    if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
+        raise StcdError(f"{name} must be uint8 [{H},{W}]")
+    return lab
+
+
+def _tile_args(H: int, W: int, tile, stride, batch, window, mean, std):
+    """The checks of the grid, the batch, the window and the normalisation: ``(plan, batch, window table)``."""
+    plan = plan_tiles(H, W, tile, stride)
+    if int(batch) < 1:
+        raise StcdError(f"batch must be >= 1, got {batch}")
+    win = window_table(plan.tile, window)
+    if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
+        raise StcdError("mean and std hold three values, std positive")
+    return plan, min(int(batch), plan.n), win
+
+
+def _check_map(t, n: int, T: int, what: str) -> None:
+    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[0] != n or t.shape[1] not in (1, 2) or tuple(t.shape[2:]) != (T, T):
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise StcdError(f"the model returned {what}{got} for {n} tiles of {T} x {T}: expected [{n},1|2,{T},{T}]")
+
+
 def _change_logits(out):
     """The change logits as CDTrainer takes them: the last element of a list / tuple (ChangeFormer's five maps, SegCD's three)."""
     return out[-1] if isinstance(out, (list, tuple)) else out
+
+
+class _SceneArgs(NamedTuple):
+    """The checked arguments of one run; nothing in it is on the device yet."""
+    views: tuple
+    scenes: list                        # one or two uint8 [H,W,3] tensors
+    H: int
+    W: int
+    plan: TilePlan
+    batch: int
+    win: Optional[np.ndarray]           # None: the flat window, NULL to the stitch
+    labels: list                        # uint8 [H,W] tensors or None, in the order they were given
+    models: list
+    dev: torch.device
+    mean: Sequence[float]
+    std: Sequence[float]
+
+
+def _check_args(model, scenes, labels, tile, stride, batch, window, mean, std, tta) -> _SceneArgs:
+    """Every argument check of the three entry points, in one order: ``tta``, the scenes, the tile grid, the labels, the models and,
+    last, their device, so that every other error shows without a GPU.  ``scenes`` and ``labels`` are ``(value, name)`` pairs."""
+    views = parse_tta(tta)
+    scenes = [_scene_tensor(t, name) for t, name in scenes]
+    if any(t.shape != scenes[0].shape for t in scenes):
+        raise StcdError(f"the scenes differ in shape: {' and '.join(str(tuple(t.shape)) for t in scenes)}")
+    H, W = int(scenes[0].shape[0]), int(scenes[0].shape[1])
+    plan, batch, win = _tile_args(H, W, tile, stride, batch, window, mean, std)
+    labels = [_label_tensor(t, name, H, W) for t, name in labels]
+    models = _model_list(model)
+    return _SceneArgs(views, scenes, H, W, plan, batch, None if window == "flat" else win, labels, models, _device_of(models), mean, std)
+
+
+def _on(t: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
+    return None if t is None else t.to(dev).contiguous()
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _stitched(args: _SceneArgs, n_heads: int, maps_of):
+    """The tile loop of every entry point: models outermost in the given order, then views, then the batches of tiles ascending;
+    each batch is gathered (one scene or two), predicted and stitched into one ``acc [n_heads*classes,H,W]`` / ``wsum [H,W]`` pair.
+    ``maps_of`` turns what a forward returned into its ``n_heads`` maps, or raises.  Returns ``(acc, wsum, classes)``."""
+    l = _lib.lib()
+    dev, plan, H, W = args.dev, args.plan, args.H, args.W
+    T, S = plan.tile, plan.stride
+    scenes = [_on(t, dev) for t in args.scenes]
+    win = None if args.win is None else torch.from_numpy(args.win).to(dev)
+    m3, s3 = (C.c_float * 3)(*args.mean), (C.c_float * 3)(*args.std)
+    acc = wsum = None
+    classes = 0
+    with torch.cuda.device(dev), _evaluating(args.models):
+        stream = _stream(dev)
+        xs = [torch.empty((args.batch, 3, T, T), dtype=torch.float32, device=dev) for _ in scenes]     # reused by every batch
+        for m in args.models:
+            for d4 in args.views:
+                for first in range(0, plan.n, args.batch):
+                    n = min(args.batch, plan.n - first)
+                    if len(scenes) == 2:
+                        _lib.check(l.stcd_scene_gather_d4(_ptr(scenes[0]), _ptr(scenes[1]), H, W, T, S, plan.tiles_x, first, n, m3, s3,
+                                                          _ptr(xs[0]), _ptr(xs[1]), d4, stream))
+                    else:
+                        _lib.check(l.stcd_scene_gather_one_d4(_ptr(scenes[0]), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(xs[0]), d4,
+                                                              stream))
+                    maps = maps_of(m(*[x[:n] for x in xs]))
+                    for h, t in enumerate(maps):
+                        _check_map(t, n, T, f"map {h} as " if n_heads > 1 else "")
+                    if len({tuple(t.shape) for t in maps}) != 1:                              # only predict_scene_heads has several
+                        raise StcdError(f"the three maps differ in shape: {[tuple(t.shape) for t in maps]}")
+                    if acc is None:
+                        classes = int(maps[0].shape[1])
+                        acc = torch.zeros((n_heads * classes, H, W), dtype=torch.float32, device=dev)
+                        wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
+                    elif maps[0].shape[1] != classes:
+                        raise StcdError("the number of classes changed between batches, views or models")
+                    maps = [t.float().contiguous() for t in maps]
+                    ptrs = (C.c_void_p * n_heads)(*[t.data_ptr() for t in maps])
+                    _lib.check(l.stcd_scene_stitch_heads_d4(ptrs, n_heads, classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
+                                                            _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
+    return acc, wsum, classes
+
+
+def _scene_result(args: _SceneArgs, acc, wsum, classes: int, threshold: float, return_prob: bool) -> SceneResult:
+    """``stcd_scene_finalize`` over one stitched map: the result of ``predict_scene`` and of ``predict_scene_seg``."""
+    dev, H, W = args.dev, args.H, args.W
+    lab = _on(args.labels[0], dev)
+    with torch.cuda.device(dev):
+        mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        prob = torch.empty((H, W), dtype=torch.float32, device=dev) if return_prob else None
+        cm = torch.zeros(4, dtype=torch.int64, device=dev) if lab is not None else None
+        _lib.check(_lib.lib().stcd_scene_finalize(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(threshold), _ptr(lab), _ptr(mask),
+                                                  _ptr(prob), _ptr(cm), _stream(dev)))
+    cm_host = cm.cpu().numpy().reshape(2, 2) if cm is not None else None
+    return SceneResult(mask, prob, cm_host, scores_from_cm(cm_host) if cm_host is not None else None)
 
 
 def predict_scene(model, scene_a, scene_b, tile: int = 256, stride: Optional[int] = None, batch: int = 16, window: str = "flat",
@@ -165,74 +321,10 @@ def predict_scene(model, scene_a, scene_b, tile: int = 256, stride: Optional[int
     then views in the given order, then tile batches ascending.  All of it goes into one ``acc`` / ``wsum`` pair, so the result
     is the ``wsum``-weighted mean of the logits over models, views and overlapping tiles.  The bits depend on that order and on
     nothing else: they are the same on every run and independent of ``batch``.  Every argument error is raised before the first
-    launch."""
-    from .modules import frozen_weights
-
-    views = parse_tta(tta)
-    models = _model_list(model)
-    dev = next(iter(models[0].parameters())).device
-    a, b = _scene_tensor(scene_a, "scene_a"), _scene_tensor(scene_b, "scene_b")
-    if a.shape != b.shape:
-        raise StcdError(f"the scenes differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
-    H, W = int(a.shape[0]), int(a.shape[1])
-    plan = plan_tiles(H, W, tile, stride)
-    if int(batch) < 1:
-        raise StcdError(f"batch must be >= 1, got {batch}")
-    batch = min(int(batch), plan.n)
-    win = window_table(plan.tile, window)
-    lab = None
-    if label is not None:
-        lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
-        if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
-            raise StcdError(f"label must be uint8 [{H},{W}]")
-    if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
-        raise StcdError("mean and std hold three values, std positive")
-    # everything is checked: from here on the device works
-    a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
-    lab = None if lab is None else lab.to(dev).contiguous()
-    win = None if window == "flat" else torch.from_numpy(win).to(dev)         # NULL window: all ones
-
-    l = _lib.lib()
-    T, S = plan.tile, plan.stride
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    was_training = [m.training for m in models]
-    try:
-        with torch.cuda.device(dev), torch.no_grad():
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            x1 = torch.empty((batch, 3, T, T), dtype=torch.float32, device=dev)       # reused by every batch
-            x2 = torch.empty_like(x1)
-            acc = wsum = None
-            classes = 0
-            for m in models:
-                m.eval()
-                with frozen_weights(m):
-                    for d4 in views:
-                        for first in range(0, plan.n, batch):
-                            n = min(batch, plan.n - first)
-                            _lib.check(l.stcd_scene_gather_d4(_ptr(a), _ptr(b), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(x1), _ptr(x2),
-                                                              d4, stream))
-                            logits = _change_logits(m(x1[:n], x2[:n]))
-                            if logits.dim() != 4 or logits.shape[0] != n or logits.shape[1] not in (1, 2) or tuple(logits.shape[2:]) != (T, T):
-                                raise StcdError(f"the model returned {tuple(logits.shape)} for {n} tiles of {T} x {T}: expected [{n},1|2,{T},{T}]")
-                            if acc is None:
-                                classes = int(logits.shape[1])
-                                acc = torch.zeros((classes, H, W), dtype=torch.float32, device=dev)
-                                wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
-                            elif logits.shape[1] != classes:
-                                raise StcdError("the number of classes changed between batches, views or models")
-                            logits = logits.float().contiguous()
-                            _lib.check(l.stcd_scene_stitch_d4(_ptr(logits), classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
-                                                              _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
-            mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
-            prob = torch.empty((H, W), dtype=torch.float32, device=dev) if return_prob else None
-            cm = torch.zeros(4, dtype=torch.int64, device=dev) if lab is not None else None
-            _lib.check(l.stcd_scene_finalize(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(threshold), _ptr(lab), _ptr(mask), _ptr(prob),
-                                             _ptr(cm), stream))
-    finally:
-        for m, was in zip(models, was_training):
-            m.train(was)
-    cm_host = cm.cpu().numpy().reshape(2, 2) if cm is not None else None
-    return SceneResult(mask, prob, cm_host, scores_from_cm(cm_host) if cm_host is not None else None)
+    launch, the device's last, so that the others show without a GPU."""
+    args = _check_args(model, ((scene_a, "scene_a"), (scene_b, "scene_b")), ((label, "label"),), tile, stride, batch, window, mean, std, tta)
+    acc, wsum, classes = _stitched(args, 1, lambda out: [_change_logits(out)])
+    return _scene_result(args, acc, wsum, classes, threshold, return_prob)
 
 
 # ------------------------------------------------------------------------------------------------ one scene, and SegCD's three maps
@@ -249,32 +341,6 @@ class SceneHeads(NamedTuple):
 HEAD_KEYS = ("seg_a", "seg_b", "change", "gated")
 
 
-def _label_tensor(label, name: str, H: int, W: int) -> Optional[torch.Tensor]:
-    if label is None:
-        return None
-    lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
-    if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
-        raise StcdError(f"{name} must be uint8 [{H},{W}]")
-    return lab
-
-
-def _tile_args(H: int, W: int, tile, stride, batch, window, mean, std):
-    """predict_scene's checks of the grid, the batch, the window and the normalisation: ``(plan, batch, window table)``."""
-    plan = plan_tiles(H, W, tile, stride)
-    if int(batch) < 1:
-        raise StcdError(f"batch must be >= 1, got {batch}")
-    win = window_table(plan.tile, window)
-    if len(mean) != 3 or len(std) != 3 or min(std) <= 0:
-        raise StcdError("mean and std hold three values, std positive")
-    return plan, min(int(batch), plan.n), win
-
-
-def _check_map(t, n: int, T: int, what: str) -> None:
-    if not torch.is_tensor(t) or t.dim() != 4 or t.shape[0] != n or t.shape[1] not in (1, 2) or tuple(t.shape[2:]) != (T, T):
-        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
-        raise StcdError(f"the model returned {what}{got} for {n} tiles of {T} x {T}: expected [{n},1|2,{T},{T}]")
-
-
 def predict_scene_seg(model, scene, tile: int = 256, stride: Optional[int] = None, batch: int = 16, window: str = "flat", label=None,
                       return_prob: bool = False, threshold: float = 0.0, mean: Sequence[float] = MEAN, std: Sequence[float] = STD,
                       tta=None) -> SceneResult:
@@ -284,58 +350,17 @@ def predict_scene_seg(model, scene, tile: int = 256, stride: Optional[int] = Non
     pipeline and contract to the letter: eval mode and ``frozen_weights`` with the previous modes restored on exit, models outermost,
     then views, then tile batches into one ``acc`` / ``wsum`` pair, ``label`` uint8 ``[H,W]`` (>= 1 is set, 255 is ignored), every
     argument error raised before the first launch, no CPU fallback."""
-    from .modules import frozen_weights
+    args = _check_args(model, ((scene, "scene"),), ((label, "label"),), tile, stride, batch, window, mean, std, tta)
+    acc, wsum, classes = _stitched(args, 1, lambda out: [out])
+    return _scene_result(args, acc, wsum, classes, threshold, return_prob)
 
-    views = parse_tta(tta)
-    a = _scene_tensor(scene, "scene")
-    H, W = int(a.shape[0]), int(a.shape[1])
-    plan, batch, win = _tile_args(H, W, tile, stride, batch, window, mean, std)
-    lab = _label_tensor(label, "label", H, W)
-    models = _model_list(model)                                               # the device last: the other errors show without a GPU
-    dev = next(iter(models[0].parameters())).device
-    # everything is checked: from here on the device works
-    a = a.to(dev).contiguous()
-    lab = None if lab is None else lab.to(dev).contiguous()
-    win = None if window == "flat" else torch.from_numpy(win).to(dev)         # NULL window: all ones
 
-    l = _lib.lib()
-    T, S = plan.tile, plan.stride
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    was_training = [m.training for m in models]
-    try:
-        with torch.cuda.device(dev), torch.no_grad():
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            x = torch.empty((batch, 3, T, T), dtype=torch.float32, device=dev)        # reused by every batch
-            acc = wsum = None
-            classes = 0
-            for m in models:
-                m.eval()
-                with frozen_weights(m):
-                    for d4 in views:
-                        for first in range(0, plan.n, batch):
-                            n = min(batch, plan.n - first)
-                            _lib.check(l.stcd_scene_gather_one_d4(_ptr(a), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(x), d4, stream))
-                            logits = m(x[:n])
-                            _check_map(logits, n, T, "")
-                            if acc is None:
-                                classes = int(logits.shape[1])
-                                acc = torch.zeros((classes, H, W), dtype=torch.float32, device=dev)
-                                wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
-                            elif logits.shape[1] != classes:
-                                raise StcdError("the number of classes changed between batches, views or models")
-                            logits = logits.float().contiguous()
-                            _lib.check(l.stcd_scene_stitch_d4(_ptr(logits), classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
-                                                              _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
-            mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
-            prob = torch.empty((H, W), dtype=torch.float32, device=dev) if return_prob else None
-            cm = torch.zeros(4, dtype=torch.int64, device=dev) if lab is not None else None
-            _lib.check(l.stcd_scene_finalize(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(threshold), _ptr(lab), _ptr(mask), _ptr(prob),
-                                             _ptr(cm), stream))
-    finally:
-        for m, was in zip(models, was_training):
-            m.train(was)
-    cm_host = cm.cpu().numpy().reshape(2, 2) if cm is not None else None
-    return SceneResult(mask, prob, cm_host, scores_from_cm(cm_host) if cm_host is not None else None)
+def _three_maps(out):
+    if not isinstance(out, (list, tuple)) or len(out) != 3:
+        got = f"a {type(out).__name__} of {len(out)}" if isinstance(out, (list, tuple)) else (
+            f"one tensor {tuple(out.shape)}" if torch.is_tensor(out) else f"a {type(out).__name__}")
+        raise StcdError(f"predict_scene_heads needs the three maps (mask_t1, mask_t2, change) of SegCD / FFCTLCD: the model returned {got}")
+    return out
 
 
 def predict_scene_heads(model, scene_a, scene_b, tile: int = 256, stride: Optional[int] = None, batch: int = 16, window: str = "flat",
@@ -353,70 +378,18 @@ def predict_scene_heads(model, scene_a, scene_b, tile: int = 256, stride: Option
 
     Everything else is ``predict_scene``'s contract (modes, order of models, views and batches, errors before the first launch, no
     CPU fallback), and ``change`` is bit-equal to ``predict_scene(...).mask`` for the same arguments."""
-    from .modules import frozen_weights
-
-    views = parse_tta(tta)
-    a, b = _scene_tensor(scene_a, "scene_a"), _scene_tensor(scene_b, "scene_b")
-    if a.shape != b.shape:
-        raise StcdError(f"the scenes differ in shape: {tuple(a.shape)} and {tuple(b.shape)}")
-    H, W = int(a.shape[0]), int(a.shape[1])
-    plan, batch, win = _tile_args(H, W, tile, stride, batch, window, mean, std)
-    labs = [_label_tensor(t, name, H, W) for t, name in ((label_a, "label_a"), (label_b, "label_b"), (label, "label"))]
-    models = _model_list(model)                                               # the device last: the other errors show without a GPU
-    dev = next(iter(models[0].parameters())).device
-    # everything is checked: from here on the device works
-    a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
-    labs = [None if t is None else t.to(dev).contiguous() for t in labs]
-    win = None if window == "flat" else torch.from_numpy(win).to(dev)         # NULL window: all ones
-
-    l = _lib.lib()
-    T, S = plan.tile, plan.stride
-    m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
-    was_training = [m.training for m in models]
-    try:
-        with torch.cuda.device(dev), torch.no_grad():
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            x1 = torch.empty((batch, 3, T, T), dtype=torch.float32, device=dev)       # reused by every batch
-            x2 = torch.empty_like(x1)
-            acc = wsum = None
-            classes = 0
-            for m in models:
-                m.eval()
-                with frozen_weights(m):
-                    for d4 in views:
-                        for first in range(0, plan.n, batch):
-                            n = min(batch, plan.n - first)
-                            _lib.check(l.stcd_scene_gather_d4(_ptr(a), _ptr(b), H, W, T, S, plan.tiles_x, first, n, m3, s3, _ptr(x1), _ptr(x2),
-                                                              d4, stream))
-                            out = m(x1[:n], x2[:n])
-                            if not isinstance(out, (list, tuple)) or len(out) != 3:
-                                got = f"a {type(out).__name__} of {len(out)}" if isinstance(out, (list, tuple)) else (
-                                    f"one tensor {tuple(out.shape)}" if torch.is_tensor(out) else f"a {type(out).__name__}")
-                                raise StcdError(f"predict_scene_heads needs the three maps (mask_t1, mask_t2, change) of SegCD / FFCTLCD: "
-                                                f"the model returned {got}")
-                            for h, t in enumerate(out):
-                                _check_map(t, n, T, f"map {h} as ")
-                            if len({tuple(t.shape) for t in out}) != 1:
-                                raise StcdError(f"the three maps differ in shape: {[tuple(t.shape) for t in out]}")
-                            if acc is None:
-                                classes = int(out[0].shape[1])
-                                acc = torch.zeros((3 * classes, H, W), dtype=torch.float32, device=dev)
-                                wsum = torch.zeros((H, W), dtype=torch.float32, device=dev)
-                            elif out[0].shape[1] != classes:
-                                raise StcdError("the number of classes changed between batches, views or models")
-                            heads = [t.float().contiguous() for t in out]
-                            ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in heads])
-                            _lib.check(l.stcd_scene_stitch_heads_d4(ptrs, 3, classes, H, W, T, S, plan.tiles_x, plan.tiles_y, first, n,
-                                                                    _ptr(win), _ptr(acc), _ptr(wsum), d4, stream))
-            masks = torch.empty((4, H, W), dtype=torch.uint8, device=dev)
-            prob = torch.empty((3, H, W), dtype=torch.float32, device=dev) if return_prob else None
-            cm = torch.zeros((4, 4), dtype=torch.int64, device=dev) if any(t is not None for t in labs) else None
-            _lib.check(l.stcd_scene_finalize_seg(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(seg_threshold), C.c_float(threshold),
-                                                 _ptr(labs[0]), _ptr(labs[1]), _ptr(labs[2]), _ptr(masks[0]), _ptr(masks[1]), _ptr(masks[2]),
-                                                 _ptr(masks[3]), _ptr(prob), _ptr(cm), stream))
-    finally:
-        for m, was in zip(models, was_training):
-            m.train(was)
+    args = _check_args(model, ((scene_a, "scene_a"), (scene_b, "scene_b")), ((label_a, "label_a"), (label_b, "label_b"), (label, "label")),
+                       tile, stride, batch, window, mean, std, tta)
+    acc, wsum, classes = _stitched(args, 3, _three_maps)
+    dev, H, W = args.dev, args.H, args.W
+    labs = [_on(t, dev) for t in args.labels]
+    with torch.cuda.device(dev):
+        masks = torch.empty((4, H, W), dtype=torch.uint8, device=dev)
+        prob = torch.empty((3, H, W), dtype=torch.float32, device=dev) if return_prob else None
+        cm = torch.zeros((4, 4), dtype=torch.int64, device=dev) if any(t is not None for t in labs) else None
+        _lib.check(_lib.lib().stcd_scene_finalize_seg(_ptr(acc), _ptr(wsum), classes, H, W, C.c_float(seg_threshold), C.c_float(threshold),
+                                                      _ptr(labs[0]), _ptr(labs[1]), _ptr(labs[2]), _ptr(masks[0]), _ptr(masks[1]),
+                                                      _ptr(masks[2]), _ptr(masks[3]), _ptr(prob), _ptr(cm), _stream(dev)))
     cms = {}
     if cm is not None:
         cm_host = cm.cpu().numpy().reshape(4, 2, 2)

@@ -18,7 +18,6 @@ drivers copy back once per ``flush`` batches.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 import os
 from typing import Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -29,9 +28,7 @@ import torch
 from . import _lib
 from ._lib import StcdError
 from .metrics import scores_from_cm
-from .scene import _change_logits, predict_scene
-
-MAX_MODELS = 8
+from .scene import MAX_MODELS, _change_logits, _device_of, _evaluating, _label_tensor, _model_list, _ptr, predict_scene
 
 
 class BatchScore(NamedTuple):
@@ -48,49 +45,6 @@ class Selection(NamedTuple):
     agree: np.ndarray                   # int64 [N,K-1,2,2]
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _model_list(models) -> list:
-    models = [models] if isinstance(models, torch.nn.Module) else list(models)
-    if not 1 <= len(models) <= MAX_MODELS:
-        raise StcdError(f"between 1 and {MAX_MODELS} models, got {len(models)}")
-    for m in models:
-        if not isinstance(m, torch.nn.Module):
-            raise StcdError(f"a model must be a torch module, got {type(m).__name__}")
-    return models
-
-
-def _device_of(models) -> torch.device:
-    dev = None
-    for m in models:
-        prm = next(iter(m.parameters()), None)
-        if prm is None or not prm.is_cuda:
-            raise StcdError("the self-training round runs on the GPU: move every model there first (no CPU fallback)")
-        if dev is not None and prm.device != dev:
-            raise StcdError(f"the models sit on different devices: {dev} and {prm.device}")
-        dev = prm.device
-    return dev
-
-
-@contextlib.contextmanager
-def _evaluating(models):
-    """eval(), no_grad and frozen_weights for every model; the previous modes come back on exit, also on error."""
-    from .modules import frozen_weights
-    was = [m.training for m in models]
-    try:
-        with contextlib.ExitStack() as stack:
-            stack.enter_context(torch.no_grad())
-            for m in models:
-                m.eval()
-                stack.enter_context(frozen_weights(m))
-            yield
-    finally:
-        for m, w in zip(models, was):
-            m.train(w)
-
-
 def score_batch(models, x1: torch.Tensor, x2: torch.Tensor, label: Optional[torch.Tensor] = None, threshold: float = 0.0,
                 mask_value: int = 1, cm: Optional[torch.Tensor] = None) -> BatchScore:
     """Every model of ``models`` (1..8 modules on one GPU: engine families, ``SegCD``, ``ChangeFormerV6`` or any torch module that
@@ -101,7 +55,7 @@ def score_batch(models, x1: torch.Tensor, x2: torch.Tensor, label: Optional[torc
     where the raw output is above ``threshold`` (0 is the reference's ``sigmoid > 0.5``), two-class models where class 1 wins.
     A ``cm`` passed in (int64 ``[4]`` on the device) is accumulated into.  Everything stays on the device; nothing synchronises."""
     models = _model_list(models)
-    dev = _device_of(models)
+    dev = _device_of(models, "the self-training round")
     for name, x in (("x1", x1), ("x2", x2)):
         if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4:
             raise StcdError(f"{name} must be an fp32 [B,C,H,W] tensor")
@@ -454,11 +408,7 @@ def scene_round(models, scene_a, scene_b, cell: int = 256, tile: int = 256, stri
         raise StcdError(f"close_radius must be in [0, 4] (0: no closing), got {close_radius}")
     if not isinstance(stem, str) or not stem:
         raise StcdError(f"stem must be a non-empty string, got {stem!r}")
-    lab = None
-    if label is not None:
-        lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
-        if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
-            raise StcdError(f"label must be uint8 [{H},{W}]")
+    lab = _label_tensor(label, "label", H, W)
     # everything is checked: from here on the device works
     a, b = a.to(dev).contiguous(), b.to(dev).contiguous()       # once, not once per checkpoint
     lab = None if lab is None else lab.to(dev).contiguous()
@@ -501,11 +451,7 @@ def export_cells(round: SceneRound, scene_a, scene_b, root: str, label=None) -> 
     H, W = (int(v) for v in round.pseudo.shape)
     if tuple(a.shape) != (H, W, 3) or tuple(b.shape) != (H, W, 3):
         raise StcdError(f"the scenes must be [{H},{W},3] as the round's pseudo-label: {tuple(a.shape)} and {tuple(b.shape)}")
-    lab = None
-    if label is not None:
-        lab = torch.from_numpy(np.ascontiguousarray(label)) if isinstance(label, np.ndarray) else label
-        if not torch.is_tensor(lab) or lab.dtype != torch.uint8 or tuple(lab.shape) != (H, W):
-            raise StcdError(f"label must be uint8 [{H},{W}]")
+    lab = _label_tensor(label, "label", H, W)
     cell = int(round.cell)
     cells_y, cells_x = cell_grid(H, W, cell)
     if tuple(round.full.shape) != (cells_y, cells_x) or len(round.names) != cells_y * cells_x:

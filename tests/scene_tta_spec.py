@@ -66,3 +66,43 @@ TTA_EXPECTED = [
     (np.array([4, 1]), (4, 1)),
 ]
 TTA_ERRORS = ["D4", "rot90", "", [], (), [0, 0], [1, 2, 1], [8], [-1], [0, 1.5], ["d4"], [True], 3]
+
+# One wrong argument each for predict_scene / predict_scene_seg / predict_scene_heads on 8 x 8 scenes with tile=8, and the word
+# its error must hold.  "scene" and "label" stand for each scene and each label argument of the entry point in turn.
+BAD_CALLS = [
+    (dict(scene=np.zeros((8, 8), np.uint8)), r"\[H,W,3\]"),
+    (dict(label=np.zeros((8, 7), np.uint8)), "must be uint8"),
+    (dict(label=np.zeros((8, 8), np.int64)), "must be uint8"),
+    (dict(stride=9), "stride"),
+    (dict(window="hamming"), "window"),
+    (dict(batch=0), "batch"),
+    (dict(mean=(0.5, 0.5)), "mean"),
+    (dict(tta="rot90"), "tta"),
+]
+
+
+def check_argument_errors(fn, model, meta_model, scene_names, label_names):
+    """Every BAD_CALLS entry through ``fn`` with ``model``, a module on the CPU: the error names the wrong argument, not the
+    device, although the device is wrong too.  Then a valid call ends at the device, and ``[model, meta_model]`` at the two devices."""
+    import pytest
+
+    from stcd_amd._lib import StcdError
+
+    def call(models, **kw):
+        return fn(models, **{**{name: np.zeros((8, 8, 3), np.uint8) for name in scene_names}, "tile": 8, **kw})
+
+    for kw, word in BAD_CALLS:
+        if "scene" in kw:
+            cases = [({name: kw["scene"]}, word) for name in scene_names]
+        elif "label" in kw:
+            cases = [({name: kw["label"]}, name + " " + word) for name in label_names]
+        else:
+            cases = [(kw, word)]
+        for case, want in cases:
+            with pytest.raises(StcdError, match=want) as e:
+                call(model, **case)
+            assert "GPU" not in str(e.value), (case, str(e.value))
+    with pytest.raises(StcdError, match="GPU"):
+        call(model)
+    with pytest.raises(StcdError, match="different devices"):
+        call([model, meta_model])

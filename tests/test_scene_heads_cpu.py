@@ -12,6 +12,7 @@ import torch
 from stcd_amd import _lib, selftrain
 from stcd_amd.scene import SceneHeads, predict_scene_heads, predict_scene_seg
 from tests import scene_heads_spec as HS
+from tests import scene_tta_spec as TS
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H, W = 7, 9
@@ -111,6 +112,7 @@ class _Tiny(torch.nn.Module):
 def test_predict_scene_seg_argument_errors_need_no_gpu():
     a = np.zeros((8, 8, 3), np.uint8)
     m = _Tiny()                                                       # on the CPU: a valid call ends at the no-CPU-fallback error
+    TS.check_argument_errors(predict_scene_seg, m, _Tiny().to("meta"), ("scene",), ("label",))
     with pytest.raises(_lib.StcdError, match="GPU"):
         predict_scene_seg(m, a, tile=8)
     with pytest.raises(_lib.StcdError, match="GPU"):
@@ -134,6 +136,7 @@ def test_predict_scene_seg_argument_errors_need_no_gpu():
 def test_predict_scene_heads_argument_errors_need_no_gpu():
     a = np.zeros((8, 8, 3), np.uint8)
     m = _Tiny()
+    TS.check_argument_errors(predict_scene_heads, m, _Tiny().to("meta"), ("scene_a", "scene_b"), ("label", "label_a", "label_b"))
     with pytest.raises(_lib.StcdError, match="GPU"):
         predict_scene_heads(m, a, a, tile=8)
     with pytest.raises(_lib.StcdError, match="tta"):

@@ -38,6 +38,8 @@ DEV = "cuda:0"
 SHAPES = [(100, 70, 64, 32), (1, 5, 64, 64), (130, 67, 72, 40), (100, 70, 30, 14), (257, 255, 128, 64)]
 CASES = [(shape, d) for i, shape in enumerate(SHAPES) for d in (range(8) if i in (0, 3) else (0, 3, 5))]
 CASE_IDS = ["{}x{}-T{}-S{}-d{}".format(*shape, d) for shape, d in CASES]
+# small grids, T % 4 == 0 and T % 4 != 0, on which view 0 is also held against the pair entry without d4
+UPRIGHT_CASES = [((20, 13, 8, 4), 0), ((17, 9, 6, 3), 0)]
 
 
 def _p(t):
@@ -87,7 +89,7 @@ def gather_pair_x1(scene, T, S, first, n, d):
     return x1
 
 
-@pytest.mark.parametrize("shape,d", CASES, ids=CASE_IDS)
+@pytest.mark.parametrize("shape,d", CASES + UPRIGHT_CASES, ids=CASE_IDS + ["{}x{}-T{}-S{}-d{}".format(*shape, d) for shape, d in UPRIGHT_CASES])
 def test_gather_one_is_x1_of_the_pair_gather_on_the_same_scene(shape, d):
     H, W, T, S = shape
     scene = _dev(_scene(H, W, 3 + H + T)[0])
@@ -95,6 +97,11 @@ def test_gather_one_is_x1_of_the_pair_gather_on_the_same_scene(shape, d):
     want = gather_pair_x1(scene, T, S, 0, plan.n, d)
     got = gather_one(scene, T, S, 0, plan.n, d)
     assert not torch.isnan(got).any() and torch.equal(got, want)
+    if d == 0:                                                         # the pair entry without d4 writes the same x1 and x2
+        x1 = torch.full_like(want, float("nan"))
+        x2 = torch.full_like(want, float("nan"))
+        _lib.check(_lib.lib().stcd_scene_gather(_p(scene), _p(scene), H, W, T, S, plan.tiles_x, 0, plan.n, M3, S3, _p(x1), _p(x2), _stream()))
+        assert torch.equal(x1, want) and torch.equal(x2, want)
     if plan.n > 2:                                                     # a range that does not start at tile 0
         first = plan.n // 2
         assert torch.equal(gather_one(scene, T, S, first, plan.n - first, d), want[first:])

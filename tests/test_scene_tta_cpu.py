@@ -108,6 +108,7 @@ class _Tiny(torch.nn.Module):
 def test_predict_scene_argument_errors_need_no_gpu():
     a = np.zeros((8, 8, 3), np.uint8)
     m = _Tiny()                                                       # on the CPU: a valid call would end at the no-CPU-fallback error
+    TS.check_argument_errors(predict_scene, m, _Tiny().to("meta"), ("scene_a", "scene_b"), ("label",))
     for tta in TS.TTA_ERRORS:
         with pytest.raises(_lib.StcdError, match="tta"):
             predict_scene(m, a, a, tile=8, tta=tta)

@@ -99,7 +99,9 @@ def gpu_finalize(acc, wsum, want_prob=False):
 
 # ------------------------------------------------------------------ 1. gather
 # reflection on both edges; a scene smaller than a tile; one full 64 x 64 staging patch plus a partial one; the scalar path
-GATHER_SHAPES = [(100, 70, 64, 32), (1, 5, 64, 64), (130, 67, 72, 40), (100, 70, 30, 14)]
+# UPRIGHT_SHAPES: small grids, T % 4 == 0 and T % 4 != 0, on which the entries without d4 are held against their d4 == 0 siblings
+UPRIGHT_SHAPES = [(20, 13, 8, 4), (17, 9, 6, 3)]
+GATHER_SHAPES = [(100, 70, 64, 32), (1, 5, 64, 64), (130, 67, 72, 40), (100, 70, 30, 14)] + UPRIGHT_SHAPES
 _upright = {}
 
 
@@ -210,7 +212,7 @@ def test_stitch_d4_chain_of_eight_views_is_exact_and_ties_are_class_zero(H, W, T
 
 # ------------------------------------------------------------------ 3. stitch, Hann: the upright entry on the un-transformed logits
 @pytest.mark.parametrize("classes", [2, 1])
-@pytest.mark.parametrize("H,W,T,S", [(300, 420, 64, 32), (100, 70, 64, 32)])
+@pytest.mark.parametrize("H,W,T,S", [(300, 420, 64, 32), (100, 70, 64, 32)] + UPRIGHT_SHAPES)
 def test_stitch_d4_hann_is_bit_equal_to_the_upright_entry(H, W, T, S, classes):
     plan = plan_tiles(H, W, T, S)
     gen = torch.Generator().manual_seed(4 + H)
