@@ -221,6 +221,9 @@ int stcd_forward(stcd_engine* e, const float* x1, const float* x2, const float* 
  * Must follow a training-mode stcd_forward on the same workspace.  grads (flat fp32, layout of params) is
  * OVERWRITTEN with d loss / d param.  stage: -1 = whole backward; 0 = decoder half (its gradients are final
  * when it returns, so a data-parallel caller may start reducing them), 1 = encoder half.
+ * ONE backward per forward: the backward kernels overwrite the stored activations and output gradients in place, so stage -1 and
+ * stage 1 consume the forward -- a further stcd_backward (any stage) fails until the next training-mode stcd_forward.  Stage 0
+ * does not consume it: stage 0 followed by stage 1 is the staged form of one backward.
  */
 int stcd_backward(stcd_engine* e, const float* grad_logits, const float* params, float* grads,
                   void* workspace, int stage, void* hip_stream);

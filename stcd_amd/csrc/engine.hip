@@ -3365,9 +3365,13 @@ int stcd_forward(stcd_engine* e, const float* x1, const float* x2, const float* 
 int stcd_backward(stcd_engine* e, const float* grad_logits, const float* params, float* grads, void* workspace, int stage,
                   void* hip_stream) {
     STCD_CHECK(e && e->configured, "engine not configured");
-    STCD_CHECK(e->fwd_training, "backward requires a preceding training-mode forward on this engine");
+    STCD_CHECK(e->fwd_training, "backward requires a preceding training-mode forward on this engine that no backward has consumed "
+               "(one backward per forward: it overwrites the stored activations in place)");
     STCD_CHECK(grad_logits && params && grads && workspace, "null pointer argument");
     STCD_CHECK(stage >= -1 && stage <= 1, "stage must be -1, 0 or 1");
+    // the backward kernels overwrite the stored activations / output gradients in place: one backward per forward.  Stage 0 leaves
+    // the encoder half pending (stage 1 follows it); the whole backward and stage 1 consume the forward
+    if (stage != 0) e->fwd_training = false;
     if (is_cf(e->arch)) return backward_cf(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
     if (is_snunet(e->arch)) return backward_snunet(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);
     if (is_segcd(e->arch)) return backward_segcd(*e, grad_logits, params, grads, workspace, stage, (hipStream_t)hip_stream);

@@ -62,6 +62,9 @@ class _EngineFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         model = ctx.model
+        if ctx.ticket is None:
+            raise StcdError("backward() a second time through one forward pass: the engine's backward overwrites the saved "
+                            "activations in place (retain_graph=True cannot keep them); run the forward again")
         if ctx.ticket != model._engine.ticket:
             raise StcdError("backward() for a forward pass whose saved activations were overwritten by a later "
                             "forward of the same module (the engine keeps one step of activations)")
@@ -78,6 +81,7 @@ class _EngineFn(torch.autograd.Function):
                     g[k * b:(k + 1) * b].zero_()
                 else:
                     g[k * b:(k + 1) * b].copy_(gk)
+        ctx.ticket = None      # consumed: the engine's backward rewrites what the forward stored
         model._run_backward(g)
         return None, None, None, None
 
