@@ -5,9 +5,11 @@ keeps a checkpoint at each third, as examples/selftrain_round_synth.py does (or 
 for instance that example's ``runs/STCD_round``); each checkpoint labels a synthetic mosaic through ``predict_scene``; ``scene_round``
 turns the three stitched masks into a reliability per 256-pixel cell and a closed pseudo-label scene without leaving the device, ``export_cells`` writes the
 tile set ``CD_Dataset`` reads (``A/``, ``B/``, ``pseudo_label/``, ``label/``, ``list/reliable_ids.txt``, ``list/unreliable_ids.txt``)
-and the reference's score line is printed for the pseudo-label scene.
+and the reference's score line is printed for the pseudo-label scene, followed by one line of object-level scores
+(``objects.match_objects``).  ``--min_area`` / ``--max_hole`` clean the pseudo-label at object level first (``refine_round``: small
+blobs cleared, small holes filled, on the device); at their default 0 the tile set and the score line are what they were without them.
 
-    python examples/selftrain_scene_synth.py --size 1024 --cell 256 --stride 128 --window hann --close_radius 2
+    python examples/selftrain_scene_synth.py --size 1024 --cell 256 --stride 128 --window hann --close_radius 2 --min_area 64 --max_hole 32
 """
 import argparse
 import glob
@@ -23,7 +25,8 @@ import torch
 from stcd_amd import synth
 from stcd_amd.modules import SiamUnet_diff
 from stcd_amd.optim import FlatAdam
-from stcd_amd.selftrain import export_cells, scene_round
+from stcd_amd.objects import match_objects
+from stcd_amd.selftrain import export_cells, refine_round, scene_round
 
 parser = argparse.ArgumentParser()
 parser.add_argument("--save_name", type=str, default="runs/STCD_scene_round", help="the tile set goes here")
@@ -38,6 +41,8 @@ parser.add_argument("--batch_size", type=int, default=16)
 parser.add_argument("--window", type=str, default="hann", choices=("flat", "hann"))
 parser.add_argument("--tta", type=str, default="", choices=("", "flip", "d4"))
 parser.add_argument("--close_radius", type=int, default=2, help="2 is the reference's 5 x 5 closing (train_stcd.py:186-188); 0: none")
+parser.add_argument("--min_area", type=int, default=0, help="clear pseudo-label objects of fewer pixels (0: none)")
+parser.add_argument("--max_hole", type=int, default=0, help="fill pseudo-label holes of at most this many pixels (0: none)")
 parser.add_argument("--cumulative", action="store_true", help="the reference's never-reset metric instead of the per-cell IoU")
 
 
@@ -104,11 +109,18 @@ def main(argv=None):
           "%d reliable, %d unreliable" % (args.size, args.size, len(models), time.perf_counter() - t0, r.full.size, int(r.full.sum()),
                                           np.nanmin(listed) if listed.size else float("nan"), np.nanmax(listed) if listed.size else float("nan"),
                                           len(r.reliable), len(r.unreliable)))
+    if args.min_area > 0 or args.max_hole > 0:
+        before = int(torch.count_nonzero(r.pseudo))
+        r = refine_round(r, min_area=args.min_area, max_hole=args.max_hole, label=label)
+        print("object filter (min_area %d, max_hole %d): %d -> %d pseudo-label pixels" % (args.min_area, args.max_hole, before, int(torch.count_nonzero(r.pseudo))))
     export_cells(r, a, b, args.save_name, label=label)
     print("wrote %d cells under %s/{A,B,pseudo_label,label} and the two lists under %s/list" % (int(r.full.sum()), args.save_name, args.save_name))
     s = r.scores
     print("change predictions:  train f1 %.3f, iou: %.3f, OA %.3f, Pre: %.3f, Rec: %.3f"             # train_stcd.py:203-204
           % (s["f1"][1], s["iou"][1], s["oa"], s["precision"][1], s["recall"][1]))
+    o = match_objects(r.pseudo, label)
+    print("change objects:  %d predicted (%d matched), %d labelled (%d found), object f1 %.3f, Pre: %.3f, Rec: %.3f"
+          % (o.n_pred, o.tp_pred, o.n_label, o.tp_label, o.f1, o.precision, o.recall))
     return r
 
 

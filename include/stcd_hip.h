@@ -477,6 +477,37 @@ int stcd_scene_cell_agree(const uint8_t* const* masks, int n_models, int height,
  * passes in LDS and writes its 48 x 240 tile; no alignment is required of in, out or width. */
 int stcd_mask_close(const uint8_t* in, int height, int width, int radius, int mask_value, uint8_t* out, void* hip_stream);
 
+/* ---- change objects: connected components of a binary mask, their table and the area / hole filter of the pseudo-label.  No
+ *      counterpart in the reference: the cleaning of train_stcd.py:186-188 one level up, from pixels to objects.  Bytes and
+ *      integers only: every output is a pure function of the input.  height * width must be below 2^31 (labels are int32);
+ *      connectivity is 4 or 8; no alignment is required of a mask or of the width.  Arguments are checked before any HIP call;
+ *      height == 0 or width == 0 launches nothing.  Every phase is its own launch: no block ever waits for another block, and
+ *      every find / union loop walks strictly decreasing pixel indices under an iteration cap (the pixel count); a thread that
+ *      reaches the cap sets the status word, the LAST 4 BYTES of the scratch buffer (zeroed at the start of a call), which
+ *      reports a bug and never a property of the input. */
+/* Bytes of the scratch buffer of the two entries below (8-byte aligned, a multiple of 4 bytes); 0 for a shape they refuse. */
+int64_t stcd_objects_scratch_bytes(int height, int width);
+/* labels: int32 [height,width] on the device: 0 is background, 1..n the components of the non-zero (invert == 1: the zero)
+ * pixels of mask (uint8 [height,width]), numbered in raster order of each component's first pixel: scipy.ndimage.label's numbering
+ * with the cross (4) or the full 3 x 3 structure (8).  count: one int32 on the device, n (it may be the 4 bytes before the
+ * status word, so that one 8-byte copy reads both).  Launches: tile pass (a 64 x 64 tile labelled in LDS), seam pass (atomicMin
+ * across tile edges), flatten, a three-launch prefix sum over the roots, relabel. */
+int stcd_objects_label(const uint8_t* mask, int height, int width, int connectivity, int invert, int32_t* labels, int32_t* count,
+                       void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* The table of the objects 1..n of a label image (a label outside 1..n is skipped): area int64 [n]; bbox int32 [n,4] =
+ * (y0, x0, y1, x1), inclusive; with an overlay (uint8 [height,width], >= 1 is set, 255 is ignored; NULL together with overlap)
+ * overlap int64 [n,2] = (pixels of the object that are not ignored, those of them where the overlay is set).  The table is
+ * overwritten, not added to; one integer atomic per run of a label within 64 pixels of a row.  n == 0 launches nothing. */
+int stcd_objects_table(const int32_t* labels, int height, int width, int n, const uint8_t* overlay, int64_t* area, int32_t* bbox,
+                       int64_t* overlap, void* hip_stream);
+/* The object filter of a mask in one call with no host read inside.  Step 1: every component of non-zero pixels (connectivity
+ * 4 or 8) with area < min_area is cleared.  Step 2, on the result of step 1: every component of unset pixels, taken with the
+ * complementary connectivity (4 when objects use 8 and the reverse), of area <= max_hole that touches no scene border is set.
+ * min_area <= 1 skips step 1, max_hole == 0 skips step 2 (both: out is the binarised input); max_hole < 0 is an error.
+ * out: uint8 [height,width], mask_value (1..255) where set, else 0; it must not overlap in, and neither may overlap scratch. */
+int stcd_mask_filter_objects(const uint8_t* in, int height, int width, int connectivity, int64_t min_area, int64_t max_hole,
+                             int mask_value, uint8_t* out, void* scratch, int64_t scratch_bytes, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

@@ -1,0 +1,182 @@
+"""Change objects on the device: connected components of a mask, their table, the area / hole filter and object-level scores.
+
+No counterpart in the reference: the pseudo-label cleaning of ``selftrain.mask_close`` (train_stcd.py:186-188) and the scoring of
+``metrics.scores_from_cm`` one level up, from pixels to objects.  Every function takes a contiguous uint8 ``[H,W]`` tensor on the
+GPU (the checks of ``selftrain._check_mask``), raises ``StcdError`` and has no CPU fallback; the kernels are
+stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_table`` and ``stcd_mask_filter_objects``
+(include/stcd_hip.h).  All outputs are integers: tests/objects_spec.py states them in numpy and the tests ask for equality.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import StcdError
+from .selftrain import _check_mask
+
+TILE = 64               # the tile pass labels TILE x TILE pixels per block (OBJ_TILE of kernels_objects.hip): where the seams lie
+
+_SCRATCH = {}           # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
+
+
+class Components(NamedTuple):
+    labels: torch.Tensor                # int32 [H,W] on the device: 0 background, 1..count in raster order of the first pixel
+    count: int
+
+
+class ObjectTable(NamedTuple):
+    area: torch.Tensor                  # int64 [n] on the device
+    bbox: torch.Tensor                  # int32 [n,4] on the device: (y0, x0, y1, x1), inclusive
+    overlap: Optional[torch.Tensor]     # int64 [n,2] on the device: (pixels not ignored by the overlay, those where it is set)
+
+
+class ObjectScores(NamedTuple):
+    n_pred: int                         # predicted objects with at least one counted pixel
+    n_label: int                        # labelled objects with at least one counted pixel
+    tp_pred: int                        # predicted objects matched by the label
+    tp_label: int                       # labelled objects found by the prediction
+    precision: float                    # tp_pred / n_pred, 0.0 for no object
+    recall: float                       # tp_label / n_label, 0.0 for no object
+    f1: float
+    pred_table: ObjectTable
+    label_table: ObjectTable
+
+
+def _ptr(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _scratch_for(device, height: int, width: int) -> torch.Tensor:
+    nbytes = int(_lib.lib().stcd_objects_scratch_bytes(int(height), int(width)))
+    key = (str(device), nbytes)
+    t = _SCRATCH.get(key)
+    if t is None:
+        t = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+def _check_shape(H: int, W: int) -> None:
+    if H * W >= 2 ** 31:
+        raise StcdError(f"a scene of {H} x {W} has 2^31 pixels or more: the labels are int32")
+
+
+def _check_connectivity(connectivity) -> int:
+    if connectivity not in (4, 8):
+        raise StcdError(f"connectivity must be 4 or 8, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _raise_if_status(status: int, what: str) -> None:
+    if status:
+        raise StcdError(f"{what}: a find / union loop reached its iteration cap (status {status}); this is a bug in the kernels, not a property of the mask")
+
+
+def label_components(mask: torch.Tensor, connectivity: int = 8, invert: bool = False) -> Components:
+    """The connected components of the non-zero (``invert``: the zero) pixels of ``mask``: int32 labels on the device, 0 for the
+    background and 1..count in raster order of each component's first pixel (``scipy.ndimage.label`` with the cross structure for
+    4, the full 3 x 3 structure for 8).  Reads back the count and the status word: one copy of 8 bytes."""
+    _check_mask(mask, "mask")
+    connectivity = _check_connectivity(connectivity)
+    H, W = (int(v) for v in mask.shape)
+    _check_shape(H, W)
+    dev = mask.device
+    with torch.cuda.device(dev):
+        labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+        if H == 0 or W == 0:
+            return Components(labels, 0)
+        scratch = _scratch_for(dev, H, W)
+        tail = scratch[-8:]                                     # the count, then the status word
+        _lib.check(_lib.lib().stcd_objects_label(_ptr(mask), H, W, connectivity, 1 if invert else 0, _ptr(labels), _ptr(tail), _ptr(scratch),
+                                                 scratch.numel(), _stream(dev)))
+        count, status = (int(v) for v in tail.cpu().numpy().view(np.int32))
+    _raise_if_status(status, "label_components")
+    return Components(labels, count)
+
+
+def object_table(components: Components, overlay: Optional[torch.Tensor] = None) -> ObjectTable:
+    """Area, bounding box and, with an ``overlay`` (uint8 ``[H,W]``, >= 1 is set, 255 is ignored), the overlap counts of every
+    component, on the device.  Nothing synchronises."""
+    labels, n = components.labels, int(components.count)
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_cuda or not labels.is_contiguous():
+        raise StcdError("components.labels must be a contiguous int32 [H,W] tensor on the GPU")
+    H, W = (int(v) for v in labels.shape)
+    _check_shape(H, W)
+    if not 0 <= n <= H * W:
+        raise StcdError(f"components.count must be in [0, {H * W}], got {n}")
+    dev = labels.device
+    if overlay is not None:
+        _check_mask(overlay, "overlay", (H, W), dev)
+    with torch.cuda.device(dev):
+        area = torch.zeros(n, dtype=torch.int64, device=dev)
+        bbox = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        overlap = None if overlay is None else torch.zeros((n, 2), dtype=torch.int64, device=dev)
+        if n and H and W:
+            _lib.check(_lib.lib().stcd_objects_table(_ptr(labels), H, W, n, _ptr(overlay), _ptr(area), _ptr(bbox), _ptr(overlap), _stream(dev)))
+    return ObjectTable(area, bbox, overlap)
+
+
+def filter_objects(mask: torch.Tensor, min_area: int = 0, max_hole: int = 0, connectivity: int = 8, mask_value: int = 255,
+                   check: bool = True) -> torch.Tensor:
+    """One ``stcd_mask_filter_objects`` call: a new mask holding ``mask_value`` where set.  Step 1 clears every component of
+    non-zero pixels with fewer than ``min_area`` pixels (``min_area <= 1``: none); step 2, on that result, sets every component of
+    unset pixels (complementary connectivity) of at most ``max_hole`` pixels that touches no scene border (``max_hole == 0``:
+    none).  ``check=True`` reads the 4-byte status word afterwards and raises if it is set; ``check=False`` synchronises nothing."""
+    _check_mask(mask, "mask")
+    connectivity = _check_connectivity(connectivity)
+    min_area, max_hole = int(min_area), int(max_hole)
+    if max_hole < 0:
+        raise StcdError(f"max_hole must be >= 0, got {max_hole}")
+    if not 1 <= int(mask_value) <= 255:
+        raise StcdError(f"mask_value must be in [1, 255], got {mask_value}")
+    H, W = (int(v) for v in mask.shape)
+    _check_shape(H, W)
+    dev = mask.device
+    with torch.cuda.device(dev):
+        out = torch.empty_like(mask)
+        if H == 0 or W == 0:                                    # an empty mask has one address for both: nothing to filter
+            return out
+        scratch = _scratch_for(dev, H, W)
+        _lib.check(_lib.lib().stcd_mask_filter_objects(_ptr(mask), H, W, connectivity, min(min_area, 2 ** 62), min(max_hole, 2 ** 62),
+                                                       int(mask_value), _ptr(out), _ptr(scratch), scratch.numel(), _stream(dev)))
+        if check:
+            _raise_if_status(int(scratch[-4:].cpu().numpy().view(np.int32)[0]), "filter_objects")
+    return out
+
+
+def score_tables(pred_overlap: np.ndarray, label_overlap: np.ndarray, min_overlap: float = 0.5):
+    """``(n_pred, n_label, tp_pred, tp_label, precision, recall, f1)`` from the two integer overlap tables ``[n,2]``, on the host: an
+    object with no counted pixel is dropped, an object is matched if ``overlap[1] >= min_overlap * overlap[0]``."""
+    out = []
+    for ov in (pred_overlap, label_overlap):
+        ov = np.asarray(ov, np.int64).reshape(-1, 2)
+        ov = ov[ov[:, 0] > 0]
+        out.append((int(ov.shape[0]), int(np.count_nonzero(ov[:, 1] >= float(min_overlap) * ov[:, 0]))))
+    (n_pred, tp_pred), (n_label, tp_label) = out
+    precision = tp_pred / n_pred if n_pred else 0.0
+    recall = tp_label / n_label if n_label else 0.0
+    f1 = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return n_pred, n_label, tp_pred, tp_label, precision, recall, f1
+
+
+def match_objects(pred: torch.Tensor, label: torch.Tensor, connectivity: int = 8, min_overlap: float = 0.5) -> ObjectScores:
+    """Object-level scores of a predicted mask against a label (uint8 ``[H,W]``, >= 1 is an object pixel, 255 is ignored).  The
+    components of ``pred`` are tabled with the label as overlay, the components of the label's object pixels with ``pred`` (as
+    0 / 1: a prediction ignores no pixel, whatever byte marks it) as overlay; every decision is then made on the host from the two integer tables (``score_tables``)."""
+    _check_mask(pred, "pred")
+    _check_mask(label, "label", tuple(pred.shape), pred.device)
+    if not 0.0 < float(min_overlap) <= 1.0:
+        raise StcdError(f"min_overlap must be in (0, 1], got {min_overlap}")
+    with torch.cuda.device(pred.device):
+        objects = torch.where(label == 255, torch.zeros_like(label), label)
+        pred_table = object_table(label_components(pred, connectivity), overlay=label)
+        label_table = object_table(label_components(objects, connectivity), overlay=(pred != 0).to(torch.uint8))
+        scores = score_tables(pred_table.overlap.cpu().numpy(), label_table.overlap.cpu().numpy(), min_overlap)
+    return ObjectScores(*scores, pred_table, label_table)

@@ -12,7 +12,8 @@ drivers copy back once per ``flush`` batches.
 ``scene_round`` is the same round over one pair of whole scenes instead of pre-cut crops: every checkpoint goes through
 ``scene.predict_scene`` (``gate="seg"``: ``scene.predict_scene_heads`` and its gated mask, train_stcd.py:170-176),
 ``stcd_scene_cell_agree`` counts the agreement per cell of the scene, ``stcd_mask_close`` is the 5 x 5 closing of the pseudo-label
-(train_stcd.py:186-188), and ``export_cells`` writes the tile set and the two lists.
+(train_stcd.py:186-188), and ``export_cells`` writes the tile set and the two lists.  ``refine_round`` cleans a round's pseudo-label
+at object level (``objects.filter_objects``: small blobs cleared, small holes filled) and scores it again.
 
 ``reliability``, ``split_reliable``, ``write_lists`` and ``cell_grid`` are host-only and need no GPU.
 """
@@ -468,3 +469,33 @@ def export_cells(round: SceneRound, scene_a, scene_b, root: str, label=None) -> 
                 crop = src[cy * cell:(cy + 1) * cell, cx * cell:(cx + 1) * cell].contiguous().cpu().numpy()
                 Image.fromarray(crop).save(os.path.join(root, sub, name), format="PNG")
     write_lists(os.path.join(root, "list"), round.reliable, round.unreliable)
+
+
+def refine_round(round: SceneRound, min_area: int = 0, max_hole: int = 0, connectivity: int = 8, label=None) -> SceneRound:
+    """A ``scene_round`` result with its pseudo-label cleaned at object level: ``pseudo`` becomes
+    ``objects.filter_objects(round.pseudo, min_area, max_hole, connectivity, 255)`` (set objects below ``min_area`` pixels are
+    cleared, then holes of at most ``max_hole`` pixels off the scene border are filled).  With a ``label`` (uint8 ``[H,W]``, >= 1 is
+    change, 255 is ignored) ``cell_cm``, ``cm`` and ``scores`` are counted again from the new pseudo-label by one
+    ``stcd_scene_cell_agree`` launch and one copy; without one they are None.  Every other field is carried over, so
+    ``export_cells`` works on the result unchanged.  Every argument error is raised before the first launch."""
+    from . import objects as _objects
+
+    if not isinstance(round, SceneRound):
+        raise StcdError(f"refine_round takes a SceneRound, got {type(round).__name__}")
+    _check_mask(round.pseudo, "round.pseudo")
+    H, W = (int(v) for v in round.pseudo.shape)
+    cells_y, cells_x = cell_grid(H, W, round.cell)
+    _objects._check_connectivity(connectivity)
+    if int(max_hole) < 0:
+        raise StcdError(f"max_hole must be >= 0, got {max_hole}")
+    lab = _label_tensor(label, "label", H, W)
+    # everything is checked: from here on the device works
+    dev = round.pseudo.device
+    lab = None if lab is None else lab.to(dev).contiguous()
+    pseudo = _objects.filter_objects(round.pseudo, min_area=min_area, max_hole=max_hole, connectivity=connectivity, mask_value=255)
+    cell_cm = cm = scores = None
+    if lab is not None:
+        cell_cm = scene_cell_agree([pseudo], round.cell, label=lab)[1].cpu().numpy().reshape(cells_y, cells_x, 2, 2)
+        cm = cell_cm.sum(axis=(0, 1))
+        scores = scores_from_cm(cm)
+    return round._replace(pseudo=pseudo, cell_cm=cell_cm, cm=cm, scores=scores)
