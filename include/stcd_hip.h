@@ -243,9 +243,19 @@ int stcd_grad_stage_range(const stcd_engine* e, int stage, int64_t* begin, int64
  *      STCD_ARCH_BIT also, always fp32 for the tokens: "bit.tokens.in|.Y|.dY|.dIn" [2*batch, 1, 4, 32], the tokens before / after the
  *      encoder and their gradients, and "bit.dec.in|.Y|.dY|.dIn", the decoder's maps -- conv_pred.dY = bit.dec.dIn + the tokenizer's
  *      data gradient)
- *      and the FC-Siam families ("<conv name>.in|.Y|.A.g0|.A.g1|.dY"; the activation per date); 0 tensors for SNUNet.  NHWC: element (n, y, x, ch) at offset_bytes + (((n*h + y)*w + x)*ld + ch) * elem_size.
+ *      and the FC-Siam families ("<conv name>.in|.Y|.A.g0|.A.g1|.dY"; the activation per date),
+ *      and the three SNUNet ids: per block "convL_J.in|.Y1|.A1|.Y2|.Out|.dZ2|.dY2|.dY1|.dIn" (both dates of an encoder level in one
+ *      tensor, date 0 first; ".P|.dP" for the pooled encoder blocks; no ".dIn" for conv0_0; ".dY2" / ".dY1" are the dOut / dA1
+ *      buffers as the backward leaves them; conv0_1..conv0_4's ".Out" is a channel slice, ld = 128, of the head's input), per
+ *      transposed conv "UpL_J.in|.Y|.dY|.dIn" (".in": the lower block's ".Out", its date-1 half below an encoder level; ".Y" / ".dY":
+ *      the tail slice of the consumer's ".in" / ".dIn"), and the head: "ecam.in|.Y|.dY" + "conv_final.dY" (the packed 8-channel
+ *      gradient), or "head.in" for the two Conc ids.
+ *      NHWC: element (n, y, x, ch) at offset_bytes + (((n*h + y)*w + x)*ld + ch) * elem_size.
  *      stcd_set_debug bit 0 (before stcd_configure): every layer writes its input gradient to a buffer of its own (the
- *      producer gathers it) instead of in place into the producer's gradient tensor, so ".dIn" survives the backward. */
+ *      producer gathers it) instead of in place into the producer's gradient tensor, so ".dIn" survives the backward.
+ *      SNUNet: the bit adds copies of the two values its backward overwrites, in buffers of their own at the end of the
+ *      workspace -- "convL_J.dOut", the gathered output gradient before bn2's backward runs in place on it, and "ecam.dIn" /
+ *      "head.dIn", the head's data gradient before conv0_1..conv0_4 gather into it; without the bit neither exists. */
 typedef struct stcd_ws_tensor {
     char name[96];
     int64_t offset_bytes;

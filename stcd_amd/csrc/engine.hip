@@ -186,6 +186,7 @@ struct NBlock {                                              // conv_block_neste
     std::vector<SrcSlice> srcs;                              // prefix slices copied in; the up-sampled tail is written in place
     int up = -1;
     TRef Y1, A1, Y2, Out, P, dOut, dP, dZ2, dA1;
+    TRef dbg_dOut;                                           // stcd_set_debug bit 0: copy of the gathered dOut (bn2's backward overwrites it)
     bool pool = false;
     int64_t stat1 = -1, stat2 = -1;
     int64_t facc1 = -1, bacc1 = -1, facc2 = -1, bacc2 = -1;
@@ -213,6 +214,7 @@ struct stcd_engine_impl {
     int sn_final = -1;
     int64_t sn_w[4] = {0, 0, 0, 0};                          // ca.fc1, ca.fc2, ca1.fc1, ca1.fc2 offsets in the flat params
     TRef snE, sndE, snZ, sndZ;
+    TRef sn_dbg_dE;                                          // stcd_set_debug bit 0: copy of the head's data gradient sndE
     int64_t sn_pool = -1, sn_argm = -1, sn_att = -1, sn_hid = -1, sn_sums = -1, sn_dpool = -1, sn_part = -1;
     int64_t sn_dout_begin = -1, sn_dout_end = -1;
     ConvOp sn_final_fwd, sn_final_dgr; WgradOp sn_final_wg;
@@ -2165,6 +2167,47 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     }
     build_pack_jobs(e, ws);
     e.jobs_uploaded_ws = nullptr;
+
+    // test introspection (stcd_ws_tensor_*): every tensor a block, a transposed conv or the head stores, as it stands after a
+    // forward / backward.  Two values do not survive the backward -- the gathered dOut (bn2's backward runs in place) and the head's
+    // data gradient (it is the base term of conv0_1..conv0_4's dOut): debug bit 0 keeps a copy of each in a buffer of its own at the
+    // END of the workspace, so that the plan without the bit is byte for byte the plan it was.
+    e.ws_tensors.clear();
+    auto rec = [&](const std::string& name, const TRef& t, int n, int h, int w, int c) {
+        if (t.off < 0) return;
+        stcd_ws_tensor r;
+        memset(&r, 0, sizeof(r));
+        snprintf(r.name, sizeof(r.name), "%s", name.c_str());
+        r.offset_bytes = t.off; r.n = n; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
+        e.ws_tensors.push_back(r);
+    };
+    const bool dbg = (e.debug_flags & 1) != 0;
+    for (auto& b : e.sn_blocks) {
+        b.dbg_dOut = dbg ? plain(b.N, b.H, b.W, b.C) : TRef{};
+        rec(b.name + ".in", b.in, b.N, b.H, b.W, b.Cin);
+        rec(b.name + ".Y1", b.Y1, b.N, b.H, b.W, b.C); rec(b.name + ".A1", b.A1, b.N, b.H, b.W, b.C);
+        rec(b.name + ".Y2", b.Y2, b.N, b.H, b.W, b.C); rec(b.name + ".Out", b.Out, b.N, b.H, b.W, b.C);
+        if (b.pool) { rec(b.name + ".P", b.P, b.N, b.H / 2, b.W / 2, b.C); rec(b.name + ".dP", b.dP, b.N, b.H / 2, b.W / 2, b.C); }
+        rec(b.name + ".dOut", b.dbg_dOut, b.N, b.H, b.W, b.C);
+        rec(b.name + ".dZ2", b.dZ2, b.N, b.H, b.W, b.C);
+        rec(b.name + ".dY2", b.dOut, b.N, b.H, b.W, b.C);          // the dOut buffer after bn2's backward
+        rec(b.name + ".dY1", b.dA1, b.N, b.H, b.W, b.C);           // the dA1 buffer after bn1's backward
+        rec(b.name + ".dIn", b.dIn, b.N, b.H, b.W, b.Cin);
+    }
+    for (const auto& u : e.sn_ups) {
+        if (u.N == 0) continue;
+        const std::string& cn = e.convs[u.conv].name;              // "UpL_J.up"
+        const std::string un = cn.substr(0, cn.size() - 3);
+        rec(un + ".in", u.src, u.N, u.h, u.w, u.C); rec(un + ".Y", u.out, u.N, 2 * u.h, 2 * u.w, u.C);
+        rec(un + ".dY", u.dOut, u.N, 2 * u.h, 2 * u.w, u.C); rec(un + ".dIn", u.tmp, u.N, u.h, u.w, u.C);
+    }
+    e.sn_dbg_dE = dbg ? plain(B, H, W, c4) : TRef{};
+    if (conc) {
+        rec("head.in", e.snE, B, H, W, c4); rec("head.dIn", e.sn_dbg_dE, B, H, W, c4);
+    } else {
+        rec("ecam.in", e.snE, B, H, W, c4); rec("ecam.Y", e.snZ, B, H, W, c4); rec("ecam.dY", e.sndZ, B, H, W, c4);
+        rec("ecam.dIn", e.sn_dbg_dE, B, H, W, c4); rec("conv_final.dY", e.G, B, H, W, 8);
+    }
     e.ws_bytes = ws.cur;
     return 0;
 }
@@ -2237,6 +2280,9 @@ static void sn_block_backward(const Ctx& c, const NBlock& b) {
                              b.groups, b.npg, HW, 1, c.at<long long>(b.bacc2), c.s, c.at(b.Y1.off), b.Y1.ld, &xs, b.grad_base ? 1 : 0,
                              c.at(b.dOut.off));
     }
+    if (b.dbg_dOut.off >= 0)         // debug bit 0: keep the gathered sum, which the launch below overwrites in place
+        (void)hipMemcpy2DAsync(c.at(b.dbg_dOut.off), (size_t)b.dbg_dOut.ld * T, c.at(b.dOut.off), (size_t)b.dOut.ld * T, (size_t)b.C * T,
+                               (size_t)px, hipMemcpyDeviceToDevice, c.s);
     {
         ProfScope ps(c, PC_BN_BWD_APPLY, 0.0, 5.0 * act_bytes);
         launch_bn_bwd_apply(e.dt, c.at(b.dOut.off), b.dOut.ld, goff_out, c.at(b.dOut.off), b.dOut.ld, c.at(b.Y2.off), b.Y2.ld,
@@ -2355,6 +2401,8 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
                              grads + e.sn_w[1], grads + e.sn_w[2], grads + e.sn_w[3], c.at<float>(e.sn_pool), c.at<int64_t>(e.sn_argm),
                              c.at<float>(e.sn_att), c.at<float>(e.sn_hid), c.at<float>(e.sn_sums), c.at<float>(e.sn_dpool), c.at<float>(e.sn_part), s);
     }
+    if (e.sn_dbg_dE.off >= 0)        // debug bit 0: the head's data gradient, before conv0_1..conv0_4 gather into it
+        STCD_HIP(hipMemcpyAsync(c.at(e.sn_dbg_dE.off), c.at(e.sndE.off), (int64_t)B * e.H * e.W * c4 * T, hipMemcpyDeviceToDevice, s));
     for (int oi = (int)e.sn_order.size() - 1; oi >= 0; --oi) {
         const NBlock& b = e.sn_blocks[e.sn_order[oi]];
         if (b.pool) {    // gradient coming back through the 2x2 max-pool of this encoder output

@@ -198,7 +198,7 @@ class Engine:
         self.shape = None
 
     def ws_tensors(self):
-        """-> {name: NHWC view [n, h, w, c] of the live workspace} for the current configuration (SegCD only)."""
+        """-> {name: NHWC view [n, h, w, c] of the live workspace} for the current configuration (the families include/stcd_hip.h lists)."""
         out = {}
         wt = _lib.WsTensor()
         for i in range(self._l.stcd_ws_tensor_count(self._h)):

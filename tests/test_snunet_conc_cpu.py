@@ -138,6 +138,132 @@ def test_abi_parameter_table_and_plan(golden, arch, label):
         l.stcd_destroy(h)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The SNUNet workspace tensor table (stcd_ws_tensor_*), which tests/test_snunet_inplace_gpu.py reads.
+# stcd_workspace_bytes of the commit BEFORE the table existed, label_ch 2, debug off: the table may not move a byte of the plan.
+WS_BYTES_BEFORE = {
+    ("snunet", "bf16", (2, 32, 64)): 332711168, ("snunet", "bf16", (16, 256, 256)): 10416133120,
+    ("snunet", "fp32", (2, 32, 64)): 271798272, ("snunet", "fp32", (16, 256, 256)): 20028562944,
+    ("snunet_conc", "bf16", (2, 32, 64)): 330010880, ("snunet_conc", "bf16", (16, 256, 256)): 9858392576,
+    ("snunet_conc", "fp32", (2, 32, 64)): 266964224, ("snunet_conc", "fp32", (16, 256, 256)): 18917711104,
+    ("snunet_conc_ds", "bf16", (2, 32, 64)): 330081024, ("snunet_conc_ds", "bf16", (16, 256, 256)): 9860510208,
+    ("snunet_conc_ds", "fp32", (2, 32, 64)): 267034368, ("snunet_conc_ds", "fp32", (16, 256, 256)): 18919828736,
+}
+SN_ARCH = {"snunet": _lib.ARCH_SNUNET, "snunet_conc": _lib.ARCH_SNUNET_CONC, "snunet_conc_ds": _lib.ARCH_SNUNET_CONC_DS}
+SN_BLOCKS = [f"conv{l}_{j}" for l in range(5) for j in range(5 - l)]                     # 15
+SN_UPS = [f"Up{l}_{j}" for l in range(1, 5) for j in range(5 - l)]                       # 10
+SN_F = (32, 64, 128, 256, 512)
+
+
+def _sn_table(arch, dtype, shape, debug):
+    l = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(l.stcd_create(SN_ARCH[arch], 3, 2, _lib.DTYPE_IDS[dtype], C.byref(h)))
+    try:
+        _lib.check(l.stcd_set_debug(h, debug))
+        _lib.check(l.stcd_configure(h, *shape))
+        wt, out = _lib.WsTensor(), {}
+        for i in range(l.stcd_ws_tensor_count(h)):
+            _lib.check(l.stcd_ws_tensor_get(h, i, C.byref(wt)))
+            assert wt.name.decode() not in out, wt.name
+            out[wt.name.decode()] = SimpleNamespace(off=wt.offset_bytes, n=wt.n, h=wt.h, w=wt.w, c=wt.c, ld=wt.ld, dtype=wt.dtype)
+        return out, l.stcd_workspace_bytes(h)
+    finally:
+        l.stcd_destroy(h)
+
+
+def _sn_expected_names(arch, debug):
+    names = set()
+    for b in SN_BLOCKS:
+        lvl, j = int(b[4]), int(b[6])
+        names |= {f"{b}.{k}" for k in ("in", "Y1", "A1", "Y2", "Out", "dZ2", "dY2", "dY1")}
+        if b != "conv0_0":
+            names.add(b + ".dIn")
+        if j == 0 and lvl < 4:
+            names |= {b + ".P", b + ".dP"}
+    names |= {f"{u}.{k}" for u in SN_UPS for k in ("in", "Y", "dY", "dIn")}
+    names |= {"ecam.in", "ecam.Y", "ecam.dY", "conv_final.dY"} if arch == "snunet" else {"head.in"}
+    retained = {b + ".dOut" for b in SN_BLOCKS} | {"ecam.dIn" if arch == "snunet" else "head.dIn"}
+    return names | (retained if debug else set()), retained
+
+
+def _sn_planned_views(B):
+    """child -> (parent, channel offset, first image): the aliases the plan has on purpose (configure_snunet)."""
+    v = {}
+    for j in range(1, 5):
+        v[f"conv0_{j}.Out"] = ("HEAD.in", 32 * (j - 1), 0)                                # x0_1..x0_4 live in the head's input
+    for lvl in range(1, 5):                                                                # an encoder level reads the pooled level above;
+        v[f"conv{lvl}_0.in"] = (f"conv{lvl - 1}_0.P", 0, B if lvl == 4 else 0)             # conv4_0: the date-1 half alone
+        v[f"conv{lvl}_0.dIn"] = (f"conv{lvl - 1}_0.dP", 0, B if lvl == 4 else 0)
+    for lvl in range(4):
+        for j in range(1, 5 - lvl):                                                        # convL_J = [xL_0 A, xL_0 B, xL_1..xL_{J-1}, Up tail]
+            up, low = f"Up{lvl + 1}_{j - 1}", f"conv{lvl + 1}_{j - 1}"
+            v[up + ".Y"] = (f"conv{lvl}_{j}.in", (j + 1) * SN_F[lvl], 0)
+            v[up + ".dY"] = (f"conv{lvl}_{j}.dIn", (j + 1) * SN_F[lvl], 0)
+            v[up + ".in"] = (low + ".Out", 0, B if (j == 1 and lvl + 1 < 4) else 0)        # below an encoder level: its date-1 half
+    return v
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 64), (16, 256, 256)])
+@pytest.mark.parametrize("dtype", ["bf16", "fp32"])
+@pytest.mark.parametrize("arch", list(SN_ARCH))
+def test_workspace_tensor_table(arch, dtype, shape):
+    """The table names 15 blocks, 10 transposed convs and the head; every tensor lies inside the workspace; two tensors share
+    bytes only where the plan aliases them on purpose (_sn_planned_views; conv0_1..conv0_4's .Out / .dY2 interleave as 32-channel
+    slices of the head's 128-channel input / gradient buffer); without the debug bit the workspace is byte for byte the size it
+    was before the table existed, and the three retained copies (convL_J.dOut, ecam.dIn / head.dIn) exist with the bit alone."""
+    B, H, W = shape
+    es = 2 if dtype == "bf16" else 4
+    off_tab, off_bytes = _sn_table(arch, dtype, shape, 0)
+    on_tab, on_bytes = _sn_table(arch, dtype, shape, 1)
+    want_on, retained = _sn_expected_names(arch, 1)
+    assert set(off_tab) == _sn_expected_names(arch, 0)[0] and set(on_tab) == want_on
+    assert len(SN_BLOCKS) == 15 and len(SN_UPS) == 10 and not (retained & set(off_tab))
+    assert off_bytes == WS_BYTES_BEFORE[(arch, dtype, shape)]
+    assert on_bytes > off_bytes
+    assert all(vars(on_tab[k]) == vars(t) for k, t in off_tab.items()), "the debug copies moved a tensor of the plan"
+    assert all(on_tab[k].off >= off_bytes for k in retained)          # the copies sit behind everything else
+    head = "ecam.in" if arch == "snunet" else "head.in"
+    views = {k: ((head if p == "HEAD.in" else p), c, n) for k, (p, c, n) in _sn_planned_views(B).items()}
+
+    for tab, total in ((off_tab, off_bytes), (on_tab, on_bytes)):
+        span = {}
+        for k, t in tab.items():
+            assert t.dtype == _lib.DTYPE_IDS[dtype] and t.ld >= t.c > 0 and t.off >= 0 and t.off % 16 == 0, k
+            span[k] = (t.off, t.off + ((t.n * t.h * t.w - 1) * t.ld + t.c) * es)
+            assert span[k][1] <= total, k
+            lvl = int(k[4]) if k.startswith("conv") and k[4].isdigit() else (int(k[2]) if k.startswith("Up") else 0)
+            if k.startswith("Up"):
+                hw = (H >> lvl, W >> lvl) if k.endswith((".in", ".dIn")) else (H >> (lvl - 1), W >> (lvl - 1))
+                assert (t.n, t.h, t.w, t.c) == (B, *hw, SN_F[lvl]), k
+            elif k.startswith("conv") and k[4].isdigit():
+                j = int(k[6])
+                n = 2 * B if (j == 0 and lvl < 4) else B
+                cin = (8 if lvl == 0 else SN_F[lvl - 1]) if j == 0 else (j + 1) * SN_F[lvl] + SN_F[lvl + 1]
+                sfx = k.split(".")[1]
+                hw = (H >> (lvl + 1), W >> (lvl + 1)) if sfx in ("P", "dP") else (H >> lvl, W >> lvl)
+                assert (t.n, t.h, t.w, t.c) == (n, *hw, cin if sfx in ("in", "dIn") else SN_F[lvl]), k
+            else:
+                assert (t.n, t.h, t.w, t.c) == (B, H, W, 8 if k == "conv_final.dY" else 128), k
+        for k, (p, coff, n0) in views.items():       # each planned view sits exactly where the plan puts it
+            c, q = tab[k], tab[p]
+            assert c.ld == q.ld and (c.h, c.w) == (q.h, q.w) and n0 + c.n <= q.n and coff + c.c <= q.c, (k, p)
+            assert c.off == q.off + ((n0 * q.h * q.w) * q.ld + coff) * es, (k, p)
+        names = sorted(tab)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                if span[a][1] <= span[b][0] or span[b][1] <= span[a][0]:
+                    continue
+                if views.get(a, ("",))[0] == b or views.get(b, ("",))[0] == a:
+                    continue
+                # the one other contact: the four 32-channel slices of the head's input / gradient buffer interleave pixel by pixel
+                ta, tb = tab[a], tab[b]
+                slices = a[:6] == "conv0_" and b[:6] == "conv0_" and a[6] in "1234" and b[6] in "1234" and \
+                    a.split(".")[1] == b.split(".")[1] and a.split(".")[1] in ("Out", "dY2")
+                d = (tb.off - ta.off) % (ta.ld * es)
+                assert slices and ta.ld == tb.ld == 128 and ta.c * es <= d and d + tb.c * es <= ta.ld * es, (a, b, span[a], span[b])
+
+
 def test_deep_supervision_refuses_more_than_two_classes():
     l = _lib.lib()
     h = C.c_void_p()
