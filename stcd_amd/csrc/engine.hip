@@ -507,12 +507,44 @@ static void build_fcsiam_tables(stcd_engine& e) {
 }
 
 // ------------------------------------------------------------------------------------------ workspace plan
-struct Bump {
+struct Planner;
+static void build_pack_jobs(stcd_engine& e, Planner& ws);
+// The workspace planner every configure_* builds its plan with: a bump allocator over the caller's workspace (256-byte slices, in
+// the order of the calls -- each family keeps its own sequence), the named tensors of the test introspection, the bias jobs and
+// the tail all four families share.
+struct Planner {
+    stcd_engine& e;
+    const int64_t T;                     // bytes per activation element
     int64_t cur = 0;
+    explicit Planner(stcd_engine& e_) : e(e_), T((int64_t)dsize(e_.dt)) {}
     int64_t take(int64_t bytes) {
         int64_t o = cur;
         cur += (bytes + 255) & ~(int64_t)255;
+        e.ws_bytes = cur;                // the plan's size is whatever has been taken so far (SNUNet takes its debug copies after tables())
         return o;
+    }
+    TRef plain(int n, int h, int w, int c) { TRef t; t.off = take((int64_t)n * h * w * c * T); t.ld = c; return t; }
+    // test introspection (stcd_ws_tensor_*): a named [n, h, w, c] tensor at `off` with pixel stride ld; a tensor the plan does not hold
+    // (off < 0) is not listed.  dtype < 0: the engine's activation type (BIT's tokens are fp32 in either mode)
+    void tensor(const std::string& name, int64_t off, int ld, int n, int h, int w, int c, int dtype = -1) {
+        if (off < 0) return;
+        stcd_ws_tensor r;
+        memset(&r, 0, sizeof(r));
+        snprintf(r.name, sizeof(r.name), "%s", name.c_str());
+        r.offset_bytes = off; r.n = n; r.h = h; r.w = w; r.c = c; r.ld = ld; r.dtype = dtype < 0 ? e.dt : dtype;
+        e.ws_tensors.push_back(r);
+    }
+    void tensor(const std::string& name, const TRef& t, int n, int h, int w, int c) { tensor(name, t.off, t.ld, n, h, w, c); }
+    // a bias gradient summed in the integer accumulator at acc_off (C channels, `valid` of them real): k_bias_finish converts it
+    void bias_job(int64_t acc_off, int conv, int C, int valid) {
+        BiasJob jb{}; jb.acc_off = acc_off; jb.out_off = e.convs[conv].b_off; jb.C = C; jb.valid = valid; jb.scale = BN_BS;
+        e.bias_jobs.push_back(jb);
+    }
+    // the tail of every plan: the bias-job table, then the slab / reduce / weight-gradient / repack job tables
+    void tables() {
+        e.bias_jobs_off = take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
+        build_pack_jobs(e, *this);
+        e.jobs_uploaded_ws = nullptr;
     }
 };
 
@@ -527,32 +559,79 @@ static int bn_index(const stcd_engine& e, const std::string& name) {
     return -1;
 }
 
-static stcd_conv_geom geom3(int N, int H, int W, int K, int ldi, int co, int ldo) {
+// ------------------------------------------------------------------------------------------ conv geometries
+// Every stcd_conv_geom the engine binds is built by one of these (the per-op ABI checks the caller's own: check_geom).  A wrong
+// hi or ldo here is an out-of-bounds access, not a failing assert -- so each shape is written once.  Tap lists that follow a filter
+// layout are derived from the PackSpec that orders the filter image: (ky, kx) -> (dy, dx) cannot drift from the packed taps.
+static stcd_conv_geom geom_base(int n, int hi, int wi, int ci, int ldi, int hm, int wm, int in_stride,
+                                int ho, int wo, int out_stride, int oy0, int ox0, int co, int ldo) {
     stcd_conv_geom g;
     memset(&g, 0, sizeof(g));
-    g.n = N; g.hi = H; g.wi = W; g.ci = K; g.ldi = ldi;
-    g.hm = H; g.wm = W; g.in_stride = 1;
-    g.ho = H; g.wo = W; g.out_stride = 1; g.oy0 = 0; g.ox0 = 0;
+    g.n = n; g.hi = hi; g.wi = wi; g.ci = ci; g.ldi = ldi;
+    g.hm = hm; g.wm = wm; g.in_stride = in_stride;
+    g.ho = ho; g.wo = wo; g.out_stride = out_stride; g.oy0 = oy0; g.ox0 = ox0;
     g.co = co; g.ldo = ldo;
+    return g;
+}
+// stride-1 3x3 (padding 1) over the whole map
+static stcd_conv_geom geom3(int N, int H, int W, int K, int ldi, int co, int ldo) {
+    stcd_conv_geom g = geom_base(N, H, W, K, ldi, H, W, 1, H, W, 1, 0, 0, co, ldo);
     g.ntaps = 9;
     for (int t = 0; t < 9; ++t) { g.dy[t] = (int8_t)(t / 3 - 1); g.dx[t] = (int8_t)(t % 3 - 1); }
     return g;
 }
-
-// 4 sub-pixel phases of ConvTranspose2d(k3,s2,p1,op1): out(2m+py, 2n+px) = sum_{dy<=py, dx<=px} in(m+dy, n+dx) W[py+1-2dy][px+1-2dx]
-static stcd_conv_geom geom_up_phase(const UpConv& U, int py, int px, int ldi, int ldo, int* tap0) {
-    stcd_conv_geom g;
-    memset(&g, 0, sizeof(g));
-    g.n = U.N; g.hi = U.h; g.wi = U.w; g.ci = U.C; g.ldi = ldi;
-    g.hm = U.h; g.wm = U.w; g.in_stride = 1;
-    g.ho = U.Ho; g.wo = U.Wo; g.out_stride = 2; g.oy0 = py; g.ox0 = px;
-    g.co = U.C; g.ldo = ldo;
-    int t = 0;
-    for (int dy = 0; dy <= py; ++dy)
-        for (int dx = 0; dx <= px; ++dx) { g.dy[t] = (int8_t)dy; g.dx[t] = (int8_t)dx; ++t; }
-    g.ntaps = t;
-    static const int start[4] = {0, 1, 3, 5};
-    *tap0 = start[py * 2 + px];
+// stride-1 1x1 (dy / dx[1..8] keep geom3's values: no kernel reads past ntaps)
+static stcd_conv_geom geom1(int N, int H, int W, int K, int ldi, int co, int ldo) {
+    stcd_conv_geom g = geom3(N, H, W, K, ldi, co, ldo);
+    g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0;
+    return g;
+}
+// stride-2 gather: output (m, n) of an hm x wm map reads input (2m + ky - pad, 2n + kx - pad) for every tap (ky, kx) of `ps` -- a
+// strided Conv2d's forward, a stride-2 ConvTranspose2d's data gradient.  (hi, wi) are the BUFFER dims (row pitch): the taps reach
+// row 2 hm - 1 / column 2 wm - 1 at most, so the replication-padded rows / columns of an odd-sized concat buffer are never read.
+static stcd_conv_geom geom_gather2(int n, int hi, int wi, int ci, int ldi, int hm, int wm, int co, int ldo, const PackSpec& ps, int pad) {
+    stcd_conv_geom g = geom_base(n, hi, wi, ci, ldi, hm, wm, 2, hm, wm, 1, 0, 0, co, ldo);
+    g.ntaps = ps.ntaps;
+    for (int t = 0; t < ps.ntaps; ++t) { g.dy[t] = (int8_t)(ps.ky[t] - pad); g.dx[t] = (int8_t)(ps.kx[t] - pad); }
+    return g;
+}
+// sub-pixel phase ph = 2 py + px of a stride-2 scatter (a ConvTranspose2d's forward, a strided Conv2d's data gradient) as a
+// stride-1 launch that writes every second pixel of the ho x wo buffer:  out(2m + py, 2n + px) = sum_t in(m + dy_t, n + dx_t) W[ky_t][kx_t]
+// over the taps [tap0, tap0 + ntaps) of `ps` that land on this phase, dy = (py + pad - ky) / 2 (likewise dx).
+static stcd_conv_geom geom_phase(int n, int h, int w, int ci, int ldi, int ho, int wo, int co, int ldo, int ph, const PackSpec& ps, int pad,
+                                 int tap0, int ntaps) {
+    const int py = ph >> 1, px = ph & 1;
+    stcd_conv_geom g = geom_base(n, h, w, ci, ldi, h, w, 1, ho, wo, 2, py, px, co, ldo);
+    g.ntaps = ntaps;
+    for (int t = 0; t < ntaps; ++t) { g.dy[t] = (int8_t)((py + pad - ps.ky[tap0 + t]) / 2); g.dx[t] = (int8_t)((px + pad - ps.kx[tap0 + t]) / 2); }
+    return g;
+}
+// 3x3 stride 2 padding 1 sorts its nine taps by phase / parity plane (0,0), (0,1), (1,0), (1,1): 1 + 2 + 2 + 4 (make_specs); phase
+// ph owns the taps [PHASE3_TAP0[ph], PHASE3_TAP0[ph + 1])
+static const int PHASE3_TAP0[5] = {0, 1, 3, 5, 9};
+// ... e.g. ConvTranspose2d(k3,s2,p1,op1): out(2m+py, 2n+px) = sum_{dy<=py, dx<=px} in(m+dy, n+dx) W[py+1-2dy][px+1-2dx]
+static stcd_conv_geom geom_phase3(int n, int h, int w, int ci, int ldi, int ho, int wo, int co, int ldo, int ph, const PackSpec& ps, int* tap0) {
+    *tap0 = PHASE3_TAP0[ph];
+    return geom_phase(n, h, w, ci, ldi, ho, wo, co, ldo, ph, ps, 1, *tap0, PHASE3_TAP0[ph + 1] - *tap0);
+}
+// weight gradient of a stride-2 layer over the parity plane (py, px) of its input: input pixel (2m + ky - pad, 2n + kx - pad) lies in
+// the plane at plane coordinates (m + dy, n + dx), dy = (ky - pad - py) / 2 for the taps of that parity.  A plane is a VIEW of the
+// NHWC tensor [n, Hi, Wi, ld] starting at pixel (py, px): pixel stride 2 * ld and a virtual row of Wi pixels (= two real rows), of
+// which the first Wi / 2 exist (the launch's wi_valid) -- one stride-1 launch per plane (and per <= 9 of its taps).
+static stcd_conv_geom geom_plane(int n, int Hi, int Wi, int ci, int ld, int ho, int wo, int co, int ldo, int ph, int pad, int ntaps,
+                                 const int8_t* ky, const int8_t* kx) {
+    const int py = ph >> 1, px = ph & 1;
+    stcd_conv_geom g = geom_base(n, Hi / 2, Wi, ci, 2 * ld, ho, wo, 1, ho, wo, 1, 0, 0, co, ldo);
+    g.ntaps = ntaps;
+    for (int t = 0; t < ntaps; ++t) { g.dy[t] = (int8_t)((ky[t] - pad - py) / 2); g.dx[t] = (int8_t)((kx[t] - pad - px) / 2); }
+    return g;
+}
+// the 7x7 stride-2 stem's forward on the tap-list GEMM kernel: tap = filter row ky, and the 7 filter columns x 8 (padded) channels
+// of a row are 112 contiguous bytes of the NHWC8 input -- one 64-"channel" row of 8 pixels starting 3 pixels to the left
+static stcd_conv_geom geom_stem_rows(int n, int Hi, int Wi, int ldi, int ho, int wo, int co, int ldo) {
+    stcd_conv_geom g = geom_base(n, Hi, Wi, 64, ldi, ho, wo, 2, ho, wo, 1, 0, 0, co, ldo);
+    g.ntaps = 7;
+    for (int t = 0; t < 7; ++t) { g.dy[t] = (int8_t)(t - 3); g.dx[t] = -3; }
     return g;
 }
 
@@ -617,7 +696,7 @@ static bool conv_on_ref(bool mfma, const ConvOp& op) { return !(mfma && op.plan.
 // ---- the binder: every conv-shaped launch and every weight gradient of every family is bound here, at configure time.  Both start
 //      from a value-initialised op (a re-configure at another shape reuses the objects) and keep only what the caller passes.
 struct Binder {
-    stcd_engine& e; Bump& ws;
+    stcd_engine& e; Planner& ws;
     bool with_tile = false;      // k_conv_tile is a candidate (FC-Siam)
     void conv(ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) const {
         op = ConvOp();
@@ -652,7 +731,7 @@ struct Binder {
     }
 };
 // the fp32 filter images of the reference kernels and the fp64 accumulators of the reference weight-gradient path
-static void take_ref_images(stcd_engine& e, Bump& ws, bool with_dwe = true) {
+static void take_ref_images(stcd_engine& e, Planner& ws, bool with_dwe = true) {
     for (auto& c : e.convs) {
         c.wpk_fwd = ws.take((int64_t)c.fwd.ntaps * c.fwd.kpad * c.fwd.wld * 4);
         if (c.dgrad.ntaps) c.wpk_dgrad = ws.take((int64_t)c.dgrad.ntaps * c.dgrad.kpad * c.dgrad.wld * 4);
@@ -674,7 +753,7 @@ static bool same_group(const WgradGroup& G, const WgradOp& op) {
 // STCD_CF_SIDE=0: ChangeFormer's single-call backward keeps its grouped weight gradients on the caller's stream
 static bool cf_side_on() { static const bool on = env_flag("STCD_CF_SIDE", true); return on; }
 
-static void build_pack_jobs(stcd_engine& e, Bump& ws) {
+static void build_pack_jobs(stcd_engine& e, Planner& ws) {
     // ---- per-launch slab regions + the batched reduce job tables (MFMA path only)
     for (int st = 0; st < 2; ++st) { e.rjobs[st].clear(); e.rjobs_total[st] = 0; }
     for (int st = 0; st < 2; ++st) e.wgroups[st].clear();
@@ -867,45 +946,68 @@ static void build_pack_jobs(stcd_engine& e, Bump& ws) {
 static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
     const int64_t T = (int64_t)dsize(e.dt);
     const int ND = fc_dates(e);            // encoder streams (dates) stacked in the batch dimension
-    e.enc.clear(); e.dec.clear(); e.ups.clear(); e.drops.clear();
-    e.drop_floats = 0;
     e.Hs[0] = H; e.Ws[0] = W;
     for (int s = 0; s < 4; ++s) { e.Hs[s + 1] = e.Hs[s] / 2; e.Ws[s + 1] = e.Ws[s] / 2; }
-    Bump ws;
+    Planner ws(e);
     auto add_drop = [&](const std::string& name, int rows, int C) {
         DropP d; d.name = name; d.rows = rows; d.C = C; d.off = e.drop_floats;
         e.drop_floats += (int64_t)rows * C;
         e.drops.push_back(d);
         return (int)e.drops.size() - 1;
     };
-    auto plain = [&](int N, int h, int w, int C) { TRef t; t.off = ws.take((int64_t)N * h * w * C * T); t.ld = C; return t; };
 
-    e.X0 = plain(ND * B, H, W, 8);
+    e.X0 = ws.plain(ND * B, H, W, 8);
     // concat buffers first (conc keeps its skips inside them)
     for (int s = 0; s < 4; ++s) {
         int Cd = ENC_C[s] + (e.arch == STCD_ARCH_CONC ? 2 : 1) * ENC_C[s];
-        e.D[s] = plain(B, e.Hs[s], e.Ws[s], Cd);
-        e.dD[s] = plain(B, e.Hs[s], e.Ws[s], Cd);
-        e.P[s] = plain(ND * B, e.Hs[s + 1], e.Ws[s + 1], ENC_C[s]);
-        e.dP[s] = plain(ND * B, e.Hs[s + 1], e.Ws[s + 1], ENC_C[s]);
+        e.D[s] = ws.plain(B, e.Hs[s], e.Ws[s], Cd);
+        e.dD[s] = ws.plain(B, e.Hs[s], e.Ws[s], Cd);
+        e.P[s] = ws.plain(ND * B, e.Hs[s + 1], e.Ws[s + 1], ENC_C[s]);
+        e.dP[s] = ws.plain(ND * B, e.Hs[s + 1], e.Ws[s + 1], ENC_C[s]);
     }
     // ---- zero arena, directly behind dP[3] (whose date-0 half must read as zero: the reference's T1 bottleneck pool is
     //      dead work, SiamUnet_diff.py:119 overwritten at :143; the date-1 half is rewritten by upconv4's data gradient):
-    //      BatchNorm accumulators of every layer (forward + backward) and the bias-gradient accumulators
+    //      BatchNorm accumulators of every layer (forward + backward) and the bias-gradient accumulators.
+    //      ONE walk over the model tables hands out the slices, in slice order: it runs here from offset 0 to size the arena (the
+    //      layers do not exist yet, nothing is assigned) and again from the arena's offset once they do -- a slice the first run
+    //      did not count cannot be handed out by the second.
     auto r256 = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-    int64_t arena_bytes = 0;
-    for (int s = 0; s < 4; ++s) arena_bytes += 2 * ENC_STAGE_CONVS[s] * r256(bn_acc_bytes(2, ENC_C[s]));
-    for (int k = 0; k < 4; ++k) {
-        for (int j = 0; j < DEC[k].n; ++j)
-            if (DEC[k].cout[j] >= 0) arena_bytes += 2 * r256(bn_acc_bytes(1, DEC[k].cout[j]));
-        arena_bytes += r256(bn_acc_bytes(1, DEC[k].C));
-    }
-    arena_bytes += r256(bn_acc_bytes(1, 8));
-    if (fc_cross(e)) for (int s = 0; s < 4; ++s) arena_bytes += 4 * r256(bn_acc_bytes(1, ENC_C[s]));      // two BatchNorms per cross_conc block
+    auto zero_arena = [&](int64_t at, bool assign) {
+        auto acc = [&](int groups, int C) { const int64_t o = at; at += r256(bn_acc_bytes(groups, C)); return o; };
+        for (int s = 0; s < 4 && fc_cross(e); ++s) {      // two BatchNorms per cross_conc block
+            const int C = ENC_C[s];
+            const int64_t a[4] = {acc(1, C), acc(1, C), acc(1, C), acc(1, C)};
+            if (assign) { XConc& X = e.xc[s]; X.facc1 = a[0]; X.bacc1 = a[1]; X.res.facc = a[2]; X.res.bacc = a[3]; }
+        }
+        size_t li = 0;
+        for (int s = 0; s < 4; ++s)
+            for (int j = 0; j < ENC_STAGE_CONVS[s]; ++j, ++li) {
+                const int64_t a[2] = {acc(ND, ENC_C[s]), acc(ND, ENC_C[s])};
+                if (assign) { e.enc[li].facc = a[0]; e.enc[li].bacc = a[1]; }
+            }
+        li = 0;
+        for (int k = 0; k < 4; ++k)
+            for (int j = 0; j < DEC[k].n; ++j) {
+                if (DEC[k].cout[j] < 0) continue;
+                const int64_t a[2] = {acc(1, DEC[k].cout[j]), acc(1, DEC[k].cout[j])};
+                if (assign) { e.dec[li].facc = a[0]; e.dec[li].bacc = a[1]; }
+                ++li;
+            }
+        for (int k = 0; k < 4; ++k) {
+            const int64_t a = acc(1, DEC[k].C);
+            if (assign) e.ups[k].bias_acc = a;
+        }
+        const int64_t a = acc(1, 8);
+        if (assign) e.final_bias_acc = a;
+        return at;
+    };
+    int64_t arena_bytes = zero_arena(0, false);
+    // (FC-EF's one encoder stream has one BatchNorm group per layer; its arena is sized like the two-date families', the slack at its
+    //  end -- the size tests/golden/plan_layout.json records)
+    for (int s = 0; s < 4; ++s) arena_bytes += 2 * ENC_STAGE_CONVS[s] * (r256(bn_acc_bytes(2, ENC_C[s])) - r256(bn_acc_bytes(ND, ENC_C[s])));
     e.zero_begin = e.dP[3].off;
-    Bump za;
-    za.cur = ws.take(arena_bytes);
-    e.zero_end = za.cur + arena_bytes;
+    const int64_t arena_off = ws.take(arena_bytes);
+    e.zero_end = arena_off + arena_bytes;
     // ---- encoder
     for (int s = 0; s < 4; ++s) {
         const int C = ENC_C[s], h = e.Hs[s], w = e.Ws[s];
@@ -920,13 +1022,13 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
             if (first && s == 0) { L.in = e.X0; L.K = 8; }
             else if (first) { L.in = e.P[s - 1]; L.K = ENC_C[s - 1]; }
             else { L.in.off = e.enc.back().A.off; L.in.ld = C; L.K = C; }
-            L.Y = plain(ND * B, h, w, C);
+            L.Y = ws.plain(ND * B, h, w, C);
             if (last && fc_concat_skips(e)) {
                 L.A.off = e.D[s].off + C * T; L.A.ld = e.D[s].ld; L.A.goff = C;
                 L.dA.off = e.dD[s].off + C * T; L.dA.ld = e.dD[s].ld; L.dA.goff = C;
-                L.dY = plain(ND * B, h, w, C);
+                L.dY = ws.plain(ND * B, h, w, C);
             } else {
-                TRef a = plain(ND * B, h, w, C), da = plain(ND * B, h, w, C);
+                TRef a = ws.plain(ND * B, h, w, C), da = ws.plain(ND * B, h, w, C);
                 L.A.off = a.off; L.A.ld = C; L.A.goff = (int64_t)B * h * w * C;
                 L.dA.off = da.off; L.dA.ld = C; L.dA.goff = L.A.goff;
                 L.dY = da;   // in place
@@ -967,8 +1069,8 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
             const int C = d.cout[j];
             L.N = B; L.H = h; L.W = w; L.groups = 1; L.npg = B;
             L.in = in; L.K = K;
-            L.Y = plain(B, h, w, C);
-            TRef a = plain(B, h, w, C), da = plain(B, h, w, C);
+            L.Y = ws.plain(B, h, w, C);
+            TRef a = ws.plain(B, h, w, C), da = ws.plain(B, h, w, C);
             L.A.off = a.off; L.A.ld = C; L.A.goff = 0;
             L.dA.off = da.off; L.dA.ld = C; L.dA.goff = 0;
             L.dY = da;
@@ -983,38 +1085,27 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
         for (int s = 0; s < 4; ++s) {       // activation IS the skip slice of the level's concat buffer
             XConc& X = e.xc[s];
             const int C = ENC_C[s], h = e.Hs[s], w = e.Ws[s];
-            X.G = plain(B, h, w, C); X.dG = plain(B, h, w, C); X.R = plain(B, h, w, C); X.dR = plain(B, h, w, C);
+            X.G = ws.plain(B, h, w, C); X.dG = ws.plain(B, h, w, C); X.R = ws.plain(B, h, w, C); X.dR = ws.plain(B, h, w, C);
             X.stat1 = ws.take((int64_t)4 * C * 4);
             X.part = ws.take(pairdw_partial_floats(B, h, w, C) * 4);
             Cbrd& L = X.res;
             L.drop = -1; L.N = B; L.H = h; L.W = w; L.groups = 1; L.npg = B;
             L.in = X.R; L.K = C;
-            L.Y = plain(B, h, w, C);
+            L.Y = ws.plain(B, h, w, C);
             L.A.off = e.D[s].off + C * T; L.A.ld = e.D[s].ld; L.A.goff = 0;
             L.dA.off = e.dD[s].off + C * T; L.dA.ld = e.dD[s].ld; L.dA.goff = 0;
-            L.dY = plain(B, h, w, C);
+            L.dY = ws.plain(B, h, w, C);
             L.has_dIn = true; L.dIn = X.dR;
             L.stat = ws.take((int64_t)4 * C * 4);
         }
     }
-    e.G = plain(B, H, W, 8);
-    for (auto& X : e.xc) {
-        X.facc1 = za.take(bn_acc_bytes(1, X.C)); X.bacc1 = za.take(bn_acc_bytes(1, X.C));
-        X.res.facc = za.take(bn_acc_bytes(1, X.C)); X.res.bacc = za.take(bn_acc_bytes(1, X.C));
-    }
-    for (auto& L : e.enc) { L.facc = za.take(bn_acc_bytes(L.groups, e.convs[L.conv].cout)); L.bacc = za.take(bn_acc_bytes(L.groups, e.convs[L.conv].cout)); }
-    for (auto& L : e.dec) { L.facc = za.take(bn_acc_bytes(L.groups, e.convs[L.conv].cout)); L.bacc = za.take(bn_acc_bytes(L.groups, e.convs[L.conv].cout)); }
-    for (auto& U : e.ups) U.bias_acc = za.take(bn_acc_bytes(1, U.C));
-    e.final_bias_acc = za.take(bn_acc_bytes(1, 8));
-    if (za.cur > e.zero_end) { set_error("internal: zero arena overflow"); return 1; }
+    e.G = ws.plain(B, H, W, 8);
+    zero_arena(arena_off, true);
     e.scratch8 = ws.take(256);
     e.masks = ws.take(e.drop_floats * 4);
     take_ref_images(e, ws);
 
     // ---- bind every conv-shaped launch (geometry, filter, MFMA plan); the layer vectors are final from here on
-    e.conv_ops.clear();
-    e.wgrad_ops.clear();
-    e.slab_floats = 0;
     const Binder bind{e, ws, true};
     auto wg_stage = [&](int conv) { return e.convs[conv].w_off < e.enc_param_end ? 1 : 0; };     // encoder filters are finalised by stage 1
     auto bind_cbrd = [&](Cbrd& L) {
@@ -1032,21 +1123,12 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
         const ConvW& cv = e.convs[U.conv];
         for (int ph = 0; ph < 4; ++ph) {
             int tap0;
-            stcd_conv_geom g = geom_up_phase(U, ph >> 1, ph & 1, U.in.ld, U.out.ld, &tap0);
+            const stcd_conv_geom g = geom_phase3(U.N, U.h, U.w, U.C, U.in.ld, U.Ho, U.Wo, U.C, U.out.ld, ph, cv.fwd, &tap0);
             bind.conv(U.fwd[ph], g, U.conv, false, tap0, U.C, U.C);
             bind.wgrad(U.wg[ph], g, U.conv, U.in.off, U.dOut.off, wg_stage(U.conv), tap0);
         }
-        // data gradient: 3x3 stride-2 conv over dOut.  (hi,wi) are the BUFFER dims (row pitch); taps reach at most
-        // row 2h-1 / col 2w-1, so replication-padded rows/cols are never read.
-        stcd_conv_geom gd;
-        memset(&gd, 0, sizeof(gd));
-        gd.n = U.N; gd.hi = U.Ho; gd.wi = U.Wo; gd.ci = cv.dgrad.kpad; gd.ldi = U.dOut.ld;
-        gd.hm = U.h; gd.wm = U.w; gd.in_stride = 2;
-        gd.ho = U.h; gd.wo = U.w; gd.out_stride = 1;
-        gd.co = U.C; gd.ldo = U.dIn.ld;
-        gd.ntaps = 9;
-        for (int t = 0; t < 9; ++t) { gd.dy[t] = (int8_t)(t / 3 - 1); gd.dx[t] = (int8_t)(t % 3 - 1); }
-        bind.conv(U.dgr, gd, U.conv, true, 0, U.C, U.C);
+        // data gradient: 3x3 stride-2 conv over dOut, whose buffer may carry replication-padded rows / columns (geom_gather2)
+        bind.conv(U.dgr, geom_gather2(U.N, U.Ho, U.Wo, cv.dgrad.kpad, U.dOut.ld, U.h, U.w, U.C, U.dIn.ld, cv.dgrad, 1), U.conv, true, 0, U.C, U.C);
     }
     {
         const ConvW& cv = e.convs[e.final_conv];
@@ -1131,7 +1213,6 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
     //      buffer, so its bias gradient is the per-channel sum of that slice of d(concat) -- which the data-gradient launch
     //      of the stage's first conv produces.  When that launch runs on the resident-filter kernel it sums the slice in its
     //      epilogue (integer accumulators, as the BatchNorm statistics); one k_bias_finish launch per backward converts.
-    e.bias_jobs.clear();
     {
         size_t di = 0;
         for (int k = 0; k < 4; ++k) {
@@ -1146,56 +1227,33 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
                 U.bias_fused = true;
                 L.dgr_sum_acc = U.bias_acc; L.dgr_sum_c0 = 0; L.dgr_sum_C = U.C;
             }
-            if (e.dt == BF16) {     // fused or not, the bf16 path sums the bias gradient in the integer accumulator (deterministic)
-                BiasJob jb{}; jb.acc_off = U.bias_acc; jb.out_off = e.convs[U.conv].b_off; jb.C = U.C; jb.valid = U.C; jb.scale = BN_BS;
-                e.bias_jobs.push_back(jb);
-            }
+            // fused or not, the bf16 path sums the bias gradient in the integer accumulator (deterministic)
+            if (e.dt == BF16) ws.bias_job(U.bias_acc, U.conv, U.C, U.C);
         }
-        BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.final_conv].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
-        e.bias_jobs.push_back(jb);
-        e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
+        ws.bias_job(e.final_bias_acc, e.final_conv, 8, e.label);
     }
 
     // test introspection (stcd_ws_tensor_*): input, conv output, activation (per date: the two halves may sit in different
     // buffers) and output gradient of every conv + BN layer, as they stand after a forward / backward
-    e.ws_tensors.clear();
     auto rec_layer = [&](const Cbrd& L) {
         const ConvW& cv = e.convs[L.conv];
-        auto rec = [&](const char* sfx, int64_t off, int ld, int n, int ch) {
-            if (off < 0) return;
-            stcd_ws_tensor r;
-            memset(&r, 0, sizeof(r));
-            snprintf(r.name, sizeof(r.name), "%s.%s", cv.name.c_str(), sfx);
-            r.offset_bytes = off; r.n = n; r.h = L.H; r.w = L.W; r.c = ch; r.ld = ld; r.dtype = e.dt;
-            e.ws_tensors.push_back(r);
-        };
         // "in.virt": the input is the producer's RAW conv output (virtual activation); the producer then records no A
-        rec(L.xsrc ? "in.virt" : "in", L.in.off, L.in.ld, L.N, L.K);
-        rec("Y", L.Y.off, L.Y.ld, L.N, cv.cout);
-        for (int g = 0; g < L.groups && !L.virt && !skip_recomputed(e, L); ++g) {
-            char sfx[8];
-            snprintf(sfx, sizeof(sfx), "A.g%d", g);
-            rec(sfx, L.A.off + g * L.A.goff * T, L.A.ld, L.npg, cv.cout);
-        }
-        rec("dY", L.dY.off, L.dY.ld, L.N, cv.cout);
+        ws.tensor(cv.name + (L.xsrc ? ".in.virt" : ".in"), L.in, L.N, L.H, L.W, L.K);
+        ws.tensor(cv.name + ".Y", L.Y, L.N, L.H, L.W, cv.cout);
+        for (int g = 0; g < L.groups && !L.virt && !skip_recomputed(e, L); ++g)
+            ws.tensor(cv.name + ".A.g" + std::to_string(g), L.A.off + g * L.A.goff * T, L.A.ld, L.npg, L.H, L.W, cv.cout);
+        ws.tensor(cv.name + ".dY", L.dY, L.N, L.H, L.W, cv.cout);
     };
     for (const Cbrd& L : e.enc) rec_layer(L);
     for (const Cbrd& L : e.dec) rec_layer(L);
     for (const XConc& X : e.xc) {      // cross_conc block: the pairwise conv as a layer of its own (Y = G, A = R, dY = dG), then conv_res
-        auto rec = [&](const char* sfx, const TRef& t) {
-            stcd_ws_tensor r;
-            memset(&r, 0, sizeof(r));
-            snprintf(r.name, sizeof(r.name), "cross_conc%d.diff.0.%s", X.level + 1, sfx);
-            r.offset_bytes = t.off; r.n = X.res.N; r.h = X.res.H; r.w = X.res.W; r.c = X.C; r.ld = t.ld; r.dtype = e.dt;
-            e.ws_tensors.push_back(r);
-        };
-        rec("Y", X.G); rec("A.g0", X.R); rec("dY", X.dG);
-        rec_layer(X.res);
+        const std::string n = "cross_conc" + std::to_string(X.level + 1) + ".diff.0.";
+        const Cbrd& R = X.res;
+        ws.tensor(n + "Y", X.G, R.N, R.H, R.W, X.C); ws.tensor(n + "A.g0", X.R, R.N, R.H, R.W, X.C); ws.tensor(n + "dY", X.dG, R.N, R.H, R.W, X.C);
+        rec_layer(R);
     }
 
-    build_pack_jobs(e, ws);
-    e.jobs_uploaded_ws = nullptr;
-    e.ws_bytes = ws.cur;
+    ws.tables();
     return 0;
 }
 
@@ -1940,34 +1998,25 @@ static int sn_up_index(const stcd_engine& e, const std::string& name) {
     return -1;
 }
 
-static stcd_conv_geom geom1(int N, int H, int W, int K, int ldi, int co, int ldo) {   // 1x1
-    stcd_conv_geom g = geom3(N, H, W, K, ldi, co, ldo);
-    g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0;
-    return g;
-}
-
 static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     const int64_t T = (int64_t)dsize(e.dt);
     const int* f = SN_F;
-    e.drops.clear(); e.drop_floats = 0;
-    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0;
-    Bump ws;
+    Planner ws(e);
     int hs[5], wsz[5];
     hs[0] = H; wsz[0] = W;
     for (int l = 0; l < 4; ++l) { hs[l + 1] = hs[l] / 2; wsz[l + 1] = wsz[l] / 2; }
-    auto plain = [&](int N, int h, int w, int C) { TRef t; t.off = ws.take((int64_t)N * h * w * C * T); t.ld = C; return t; };
     auto B_ = [&](const char* n) -> NBlock& { return e.sn_blocks[sn_block_index(e, n)]; };
 
     const bool conc = is_snconc(e.arch);       // no ECAM: no gated copy of E, no packed output gradient (kernels_snhead.hip)
-    e.X0 = plain(2 * B, H, W, 8);
-    if (!conc) e.G = plain(B, H, W, 8);
+    e.X0 = ws.plain(2 * B, H, W, 8);
+    if (!conc) e.G = ws.plain(B, H, W, 8);
     const int c4 = f[0] * 4;
-    e.snE = plain(B, H, W, c4);
-    if (!conc) { e.snZ = plain(B, H, W, c4); e.sndZ = plain(B, H, W, c4); }
+    e.snE = ws.plain(B, H, W, c4);
+    if (!conc) { e.snZ = ws.plain(B, H, W, c4); e.sndZ = ws.plain(B, H, W, c4); }
 
     // ---- activation buffers of every block.  dOut buffers are allocated back to back: one memset per backward.
     e.sn_dout_begin = ws.cur;
-    e.sndE = plain(B, H, W, c4);
+    e.sndE = ws.plain(B, H, W, c4);
     for (auto& b : e.sn_blocks) {
         const int lvl = b.name[4] - '0', j = b.name[6] - '0';
         const bool enc = j == 0;
@@ -1978,7 +2027,7 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         if (lvl == 0 && j >= 1) {            // x0_1..x0_4 live directly in the ECAM input (one copy less)
             b.dOut.off = e.sndE.off + (int64_t)(j - 1) * f[0] * T; b.dOut.ld = c4;
         } else {
-            b.dOut = plain(b.N, b.H, b.W, b.C);
+            b.dOut = ws.plain(b.N, b.H, b.W, b.C);
         }
     }
     e.sn_dout_end = ws.cur;
@@ -1986,11 +2035,11 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         const int lvl = b.name[4] - '0', j = b.name[6] - '0';
         const bool enc = j == 0;
         if (lvl == 0 && j >= 1) { b.Out.off = e.snE.off + (int64_t)(j - 1) * f[0] * T; b.Out.ld = c4; }
-        else b.Out = plain(b.N, b.H, b.W, b.C);
-        b.Y1 = plain(b.N, b.H, b.W, b.C); b.A1 = plain(b.N, b.H, b.W, b.C); b.Y2 = plain(b.N, b.H, b.W, b.C);
-        b.dZ2 = plain(b.N, b.H, b.W, b.C); b.dA1 = plain(b.N, b.H, b.W, b.C);
+        else b.Out = ws.plain(b.N, b.H, b.W, b.C);
+        b.Y1 = ws.plain(b.N, b.H, b.W, b.C); b.A1 = ws.plain(b.N, b.H, b.W, b.C); b.Y2 = ws.plain(b.N, b.H, b.W, b.C);
+        b.dZ2 = ws.plain(b.N, b.H, b.W, b.C); b.dA1 = ws.plain(b.N, b.H, b.W, b.C);
         b.pool = enc && lvl < 4;
-        if (b.pool) { b.P = plain(b.N, b.H / 2, b.W / 2, b.C); b.dP = plain(b.N, b.H / 2, b.W / 2, b.C); }
+        if (b.pool) { b.P = ws.plain(b.N, b.H / 2, b.W / 2, b.C); b.dP = ws.plain(b.N, b.H / 2, b.W / 2, b.C); }
         b.stat1 = ws.take((int64_t)b.groups * 4 * b.C * 4);
         b.stat2 = ws.take((int64_t)b.groups * 4 * b.C * 4);
     }
@@ -2018,7 +2067,7 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
             }
             continue;
         }
-        b.in = plain(b.N, b.H, b.W, b.Cin); b.dIn = plain(b.N, b.H, b.W, b.Cin);
+        b.in = ws.plain(b.N, b.H, b.W, b.Cin); b.dIn = ws.plain(b.N, b.H, b.W, b.Cin);
         NBlock& enc = e.sn_blocks[sn_block_index(e, std::string("conv") + char('0' + lvl) + "_0")];
         const int64_t half = (int64_t)B * enc.H * enc.W * enc.C * T;
         int coff = 0;
@@ -2047,7 +2096,7 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
         u.out = TRef{b.in.off + (int64_t)coff * T, b.Cin};
         u.dOut = TRef{b.dIn.off + (int64_t)coff * T, b.Cin};
         u.coff = coff;
-        u.tmp = plain(B, u.h, u.w, u.C);
+        u.tmp = ws.plain(B, u.h, u.w, u.C);
     }
     // ---- dense concatenation without copy kernels: every producer writes its output straight into its consumers' concat
     //      slices (extra destinations of its last activation kernel), and gathers its gradient from their concat-gradient
@@ -2085,7 +2134,6 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     // ---- forward order (SNUNet.py:119-142)
     static const char* ORDER[] = {"conv0_0", "conv1_0", "conv2_0", "conv3_0", "conv4_0", "conv0_1", "conv1_1", "conv0_2", "conv2_1",
                                   "conv1_2", "conv0_3", "conv3_1", "conv2_2", "conv1_3", "conv0_4"};
-    e.sn_order.clear();
     for (auto n : ORDER) e.sn_order.push_back(sn_block_index(e, n));
 
     e.scratch8 = ws.take(256);
@@ -2114,26 +2162,13 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     for (auto& u : e.sn_ups) {
         if (u.N == 0) continue;
         const ConvW& cv = e.convs[u.conv];
-        for (int ph = 0; ph < 4; ++ph) {
-            stcd_conv_geom g;
-            memset(&g, 0, sizeof(g));
-            g.n = u.N; g.hi = u.h; g.wi = u.w; g.ci = u.C; g.ldi = u.src.ld;
-            g.hm = u.h; g.wm = u.w; g.in_stride = 1;
-            g.ho = 2 * u.h; g.wo = 2 * u.w; g.out_stride = 2; g.oy0 = ph >> 1; g.ox0 = ph & 1;
-            g.co = u.C; g.ldo = u.out.ld;
-            g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0;
+        for (int ph = 0; ph < 4; ++ph) {      // ConvTranspose2d(k2, s2): phase ph is the one tap ph, out(2m + py, 2n + px) = in(m, n) W[py][px]
+            const stcd_conv_geom g = geom_phase(u.N, u.h, u.w, u.C, u.src.ld, 2 * u.h, 2 * u.w, u.C, u.out.ld, ph, cv.fwd, 0, ph, 1);
             bind.conv(u.fwd[ph], g, u.conv, false, ph, u.C, u.C);
             bind.wgrad(u.wg[ph], g, u.conv, u.src.off, u.dOut.off, 0, ph);
         }
-        stcd_conv_geom gd;
-        memset(&gd, 0, sizeof(gd));
-        gd.n = u.N; gd.hi = 2 * u.h; gd.wi = 2 * u.w; gd.ci = cv.dgrad.kpad; gd.ldi = u.dOut.ld;
-        gd.hm = u.h; gd.wm = u.w; gd.in_stride = 2;
-        gd.ho = u.h; gd.wo = u.w; gd.out_stride = 1;
-        gd.co = u.C; gd.ldo = u.tmp.ld;
-        gd.ntaps = 4;
-        for (int t = 0; t < 4; ++t) { gd.dy[t] = (int8_t)(t >> 1); gd.dx[t] = (int8_t)(t & 1); }
-        bind.conv(u.dgr, gd, u.conv, true, 0, u.C, u.C);
+        // data gradient: the four taps (dy, dx) of a stride-2 gather over dOut
+        bind.conv(u.dgr, geom_gather2(u.N, 2 * u.h, 2 * u.w, cv.dgrad.kpad, u.dOut.ld, u.h, u.w, u.C, u.tmp.ld, cv.dgrad, 0), u.conv, true, 0, u.C, u.C);
     }
     if (!conc) {
         const ConvW& cv = e.convs[e.sn_final];
@@ -2143,7 +2178,6 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
     }
     e.slab = ws.take(e.slab_floats * 4);
     // bias gradients of the transposed convs: summed by the consumer block's conv1 data gradient (see configure_fcsiam)
-    e.bias_jobs.clear();
     for (auto& b : e.sn_blocks) {
         b.d1_sum_acc = -1;
         if (b.up < 0) continue;
@@ -2153,62 +2187,42 @@ static int configure_snunet(stcd_engine& e, int B, int H, int W) {
             u.bias_fused = true;
             b.d1_sum_acc = u.bias_acc; b.d1_sum_c0 = u.coff; b.d1_sum_C = u.C;
         }
-        if (e.dt == BF16) {
-            BiasJob jb{}; jb.acc_off = u.bias_acc; jb.out_off = e.convs[u.conv].b_off; jb.C = u.C; jb.valid = u.C; jb.scale = BN_BS;
-            e.bias_jobs.push_back(jb);
-        }
+        if (e.dt == BF16) ws.bias_job(u.bias_acc, u.conv, u.C, u.C);
     }
-    {
-        if (!conc) {
-            BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.sn_final].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
-            e.bias_jobs.push_back(jb);
-        }
-        e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
-    }
-    build_pack_jobs(e, ws);
-    e.jobs_uploaded_ws = nullptr;
+    if (!conc) ws.bias_job(e.final_bias_acc, e.sn_final, 8, e.label);
+    ws.tables();
 
     // test introspection (stcd_ws_tensor_*): every tensor a block, a transposed conv or the head stores, as it stands after a
     // forward / backward.  Two values do not survive the backward -- the gathered dOut (bn2's backward runs in place) and the head's
     // data gradient (it is the base term of conv0_1..conv0_4's dOut): debug bit 0 keeps a copy of each in a buffer of its own at the
     // END of the workspace, so that the plan without the bit is byte for byte the plan it was.
-    e.ws_tensors.clear();
-    auto rec = [&](const std::string& name, const TRef& t, int n, int h, int w, int c) {
-        if (t.off < 0) return;
-        stcd_ws_tensor r;
-        memset(&r, 0, sizeof(r));
-        snprintf(r.name, sizeof(r.name), "%s", name.c_str());
-        r.offset_bytes = t.off; r.n = n; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
-        e.ws_tensors.push_back(r);
-    };
     const bool dbg = (e.debug_flags & 1) != 0;
     for (auto& b : e.sn_blocks) {
-        b.dbg_dOut = dbg ? plain(b.N, b.H, b.W, b.C) : TRef{};
-        rec(b.name + ".in", b.in, b.N, b.H, b.W, b.Cin);
-        rec(b.name + ".Y1", b.Y1, b.N, b.H, b.W, b.C); rec(b.name + ".A1", b.A1, b.N, b.H, b.W, b.C);
-        rec(b.name + ".Y2", b.Y2, b.N, b.H, b.W, b.C); rec(b.name + ".Out", b.Out, b.N, b.H, b.W, b.C);
-        if (b.pool) { rec(b.name + ".P", b.P, b.N, b.H / 2, b.W / 2, b.C); rec(b.name + ".dP", b.dP, b.N, b.H / 2, b.W / 2, b.C); }
-        rec(b.name + ".dOut", b.dbg_dOut, b.N, b.H, b.W, b.C);
-        rec(b.name + ".dZ2", b.dZ2, b.N, b.H, b.W, b.C);
-        rec(b.name + ".dY2", b.dOut, b.N, b.H, b.W, b.C);          // the dOut buffer after bn2's backward
-        rec(b.name + ".dY1", b.dA1, b.N, b.H, b.W, b.C);           // the dA1 buffer after bn1's backward
-        rec(b.name + ".dIn", b.dIn, b.N, b.H, b.W, b.Cin);
+        b.dbg_dOut = dbg ? ws.plain(b.N, b.H, b.W, b.C) : TRef{};
+        ws.tensor(b.name + ".in", b.in, b.N, b.H, b.W, b.Cin);
+        ws.tensor(b.name + ".Y1", b.Y1, b.N, b.H, b.W, b.C); ws.tensor(b.name + ".A1", b.A1, b.N, b.H, b.W, b.C);
+        ws.tensor(b.name + ".Y2", b.Y2, b.N, b.H, b.W, b.C); ws.tensor(b.name + ".Out", b.Out, b.N, b.H, b.W, b.C);
+        if (b.pool) { ws.tensor(b.name + ".P", b.P, b.N, b.H / 2, b.W / 2, b.C); ws.tensor(b.name + ".dP", b.dP, b.N, b.H / 2, b.W / 2, b.C); }
+        ws.tensor(b.name + ".dOut", b.dbg_dOut, b.N, b.H, b.W, b.C);
+        ws.tensor(b.name + ".dZ2", b.dZ2, b.N, b.H, b.W, b.C);
+        ws.tensor(b.name + ".dY2", b.dOut, b.N, b.H, b.W, b.C);          // the dOut buffer after bn2's backward
+        ws.tensor(b.name + ".dY1", b.dA1, b.N, b.H, b.W, b.C);           // the dA1 buffer after bn1's backward
+        ws.tensor(b.name + ".dIn", b.dIn, b.N, b.H, b.W, b.Cin);
     }
     for (const auto& u : e.sn_ups) {
         if (u.N == 0) continue;
         const std::string& cn = e.convs[u.conv].name;              // "UpL_J.up"
         const std::string un = cn.substr(0, cn.size() - 3);
-        rec(un + ".in", u.src, u.N, u.h, u.w, u.C); rec(un + ".Y", u.out, u.N, 2 * u.h, 2 * u.w, u.C);
-        rec(un + ".dY", u.dOut, u.N, 2 * u.h, 2 * u.w, u.C); rec(un + ".dIn", u.tmp, u.N, u.h, u.w, u.C);
+        ws.tensor(un + ".in", u.src, u.N, u.h, u.w, u.C); ws.tensor(un + ".Y", u.out, u.N, 2 * u.h, 2 * u.w, u.C);
+        ws.tensor(un + ".dY", u.dOut, u.N, 2 * u.h, 2 * u.w, u.C); ws.tensor(un + ".dIn", u.tmp, u.N, u.h, u.w, u.C);
     }
-    e.sn_dbg_dE = dbg ? plain(B, H, W, c4) : TRef{};
+    e.sn_dbg_dE = dbg ? ws.plain(B, H, W, c4) : TRef{};
     if (conc) {
-        rec("head.in", e.snE, B, H, W, c4); rec("head.dIn", e.sn_dbg_dE, B, H, W, c4);
+        ws.tensor("head.in", e.snE, B, H, W, c4); ws.tensor("head.dIn", e.sn_dbg_dE, B, H, W, c4);
     } else {
-        rec("ecam.in", e.snE, B, H, W, c4); rec("ecam.Y", e.snZ, B, H, W, c4); rec("ecam.dY", e.sndZ, B, H, W, c4);
-        rec("ecam.dIn", e.sn_dbg_dE, B, H, W, c4); rec("conv_final.dY", e.G, B, H, W, 8);
+        ws.tensor("ecam.in", e.snE, B, H, W, c4); ws.tensor("ecam.Y", e.snZ, B, H, W, c4); ws.tensor("ecam.dY", e.sndZ, B, H, W, c4);
+        ws.tensor("ecam.dIn", e.sn_dbg_dE, B, H, W, c4); ws.tensor("conv_final.dY", e.G, B, H, W, 8);
     }
-    e.ws_bytes = ws.cur;
     return 0;
 }
 
@@ -2571,23 +2585,19 @@ static void build_segcd_tables(stcd_engine& e) {
 static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     const int64_t T = (int64_t)dsize(e.dt);
     const int D = e.seg_dates, N = D * B;
-    e.drops.clear(); e.drop_floats = 0;
-    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0;
-    e.g_fwd.clear();
-    Bump ws;
-    auto plain = [&](int n, int h, int w, int C) { TRef t; t.off = ws.take((int64_t)n * h * w * C * T); t.ld = C; return t; };
+    Planner ws(e);
     auto view = [&](const TRef& t, int coff, int ld, int h, int w) {       // both dates of a plain [2B,h,w,ld] tensor, channel offset coff
         ViewRef v; v.off = t.off + (int64_t)coff * T; v.ld = ld; v.goff = D == 2 ? (int64_t)B * h * w * ld : 0; v.gmask = D == 2 ? 3 : 1; return v;
     };
     for (auto& L : e.g_layers) { L.extra_dst.clear(); L.grad_src.clear(); L.grad_base = true; L.res = TRef(); L.dRes = TRef(); L.ndgr = 0; }
-    e.X0 = plain(N, H, W, 8);
+    e.X0 = ws.plain(N, H, W, 8);
     // ---- shapes + activation buffers, forward order
     auto shape = [&](GLayer& L, const TRef& in, int K, int hi, int wi, int stride, int ng = 0) {
         const ConvW& cv = e.convs[L.conv];
         if (ng == 0) ng = D;
         const int n = ng * B;
         L.N = n; L.groups = ng; L.npg = B; L.in = in; L.K = K; L.Hi = hi; L.Wi = wi; L.Ho = hi / stride; L.Wo = wi / stride; L.C = cv.cout;
-        L.Y = plain(n, L.Ho, L.Wo, L.C); L.A = plain(n, L.Ho, L.Wo, L.C); L.dA = plain(n, L.Ho, L.Wo, L.C);
+        L.Y = ws.plain(n, L.Ho, L.Wo, L.C); L.A = ws.plain(n, L.Ho, L.Wo, L.C); L.dA = ws.plain(n, L.Ho, L.Wo, L.C);
         L.stat = ws.take((int64_t)std::max(2, ng) * 4 * L.C * 4); L.coef = ws.take((int64_t)std::max(2, ng) * 5 * L.C * 4);
         L.g_first = 0;
     };
@@ -2595,7 +2605,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     shape(S, e.X0, 8, H, W, 2);
     S.has_dIn = false;
     { GStep st; st.kind = GS_LAYER; st.layer = e.g_stem; e.g_fwd.push_back(st); }
-    e.gP0 = plain(N, H / 4, W / 4, 64); e.gdP0 = plain(N, H / 4, W / 4, 64);
+    e.gP0 = ws.plain(N, H / 4, W / 4, 64); e.gdP0 = ws.plain(N, H / 4, W / 4, 64);
     e.g_pool_idx = ws.take((int64_t)N * (H / 4) * (W / 4) * 64);
     e.g_stem_part = ws.take(stem_wgrad_part_floats(N, H, W, e.in_ch, 64) * 4);
     { GStep st; st.kind = GS_MAXPOOL; st.src = S.A; st.dst = e.gP0; st.dsrc = S.dA; st.ddst = e.gdP0; st.N = N; st.h = H / 2; st.w = W / 2; st.C = 64; e.g_fwd.push_back(st); }
@@ -2621,13 +2631,13 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             L3.res = blk[3] >= 0 ? e.g_layers[blk[3]].A : cur;
             // gradient wiring: single-consumer tensors are written in place, the block input gets contribution buffers
             if (e.debug_flags & 1) {
-                if (L2) { L2->dIn = plain(N, h, w, L1.C); L1.grad_base = false; L1.grad_src.push_back(view(L2->dIn, 0, L1.C, h, w)); }
-                L3.dIn = plain(N, ho, wo, Lm.C); Lm.grad_base = false; Lm.grad_src.push_back(view(L3.dIn, 0, Lm.C, ho, wo));
+                if (L2) { L2->dIn = ws.plain(N, h, w, L1.C); L1.grad_base = false; L1.grad_src.push_back(view(L2->dIn, 0, L1.C, h, w)); }
+                L3.dIn = ws.plain(N, ho, wo, Lm.C); Lm.grad_base = false; Lm.grad_src.push_back(view(L3.dIn, 0, Lm.C, ho, wo));
             } else { if (L2) L2->dIn = L1.dA; L3.dIn = Lm.dA; }
-            L1.dIn = (prev_out < 0) ? e.gdP0 : plain(N, h, w, curC);
+            L1.dIn = (prev_out < 0) ? e.gdP0 : ws.plain(N, h, w, curC);
             TRef idc;                                                          // identity-branch contribution to d(cur)
-            if (blk[3] >= 0) { GLayer& Ld = e.g_layers[blk[3]]; L3.dRes = Ld.dA; Ld.dIn = plain(N, h, w, curC); idc = Ld.dIn; }
-            else { L3.dRes = plain(N, h, w, curC); idc = L3.dRes; }
+            if (blk[3] >= 0) { GLayer& Ld = e.g_layers[blk[3]]; L3.dRes = Ld.dA; Ld.dIn = ws.plain(N, h, w, curC); idc = Ld.dIn; }
+            else { L3.dRes = ws.plain(N, h, w, curC); idc = L3.dRes; }
             if (prev_out >= 0) {
                 GLayer& Pv = e.g_layers[prev_out];
                 Pv.grad_base = false;
@@ -2646,9 +2656,9 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         GLayer& X = e.g_layers[stage_out.back()];
         X.grad_base = true;                                                                 // the up-sampling gradient alone
         const int Ct = X.C, h4 = 2 * X.Ho, w4 = 2 * X.Wo;
-        GStep up; up.kind = GS_UPSAMPLE; up.src = X.A; up.dsrc = X.dA; up.dst = plain(N, h4, w4, Ct); up.ddst = plain(N, h4, w4, Ct);
+        GStep up; up.kind = GS_UPSAMPLE; up.src = X.A; up.dsrc = X.dA; up.dst = ws.plain(N, h4, w4, Ct); up.ddst = ws.plain(N, h4, w4, Ct);
         up.N = N; up.h = X.Ho; up.w = X.Wo; up.C = Ct; e.g_fwd.push_back(up);
-        GStep cp; cp.kind = GS_BCONV; cp.src = up.dst; cp.dsrc = up.ddst; cp.dst = plain(N, h4, w4, 32); cp.ddst = plain(N, h4, w4, 32);
+        GStep cp; cp.kind = GS_BCONV; cp.src = up.dst; cp.dsrc = up.ddst; cp.dst = ws.plain(N, h4, w4, 32); cp.ddst = ws.plain(N, h4, w4, 32);
         cp.N = N; cp.h = h4; cp.w = w4; cp.C = Ct; e.g_fwd.push_back(cp);
         TRef pair_src = cp.dst, pair_dsrc = cp.ddst;      // what |x1 - x2| reads and where its backward writes
         if (e.bit.on) {      // tokenizer -> token encoder -> decoder; the differencing then reads the decoder's output
@@ -2664,23 +2674,23 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             b.dmh = ws.take((int64_t)L * N * 8 * 128 * 4); b.dm = ws.take((int64_t)L * N * 128 * 4);
             b.enc_part = ws.take(bit_enc_part_floats(B, 64) * 4);
             b.tok_part = ws.take((int64_t)N * 128 * 4);
-            b.dec_din = plain(N, h4, w4, 32);
+            b.dec_din = ws.plain(N, h4, w4, 32);
             GStep tk; tk.kind = GS_TOKENIZE; tk.src = cp.dst; tk.dsrc = cp.ddst; tk.N = N; tk.h = h4; tk.w = w4; tk.C = 32; e.g_fwd.push_back(tk);
             GStep te; te.kind = GS_TOKENENC; te.N = N; e.g_fwd.push_back(te);
-            GStep td; td.kind = GS_TOKENDEC; td.src = cp.dst; td.dsrc = b.dec_din; td.dst = plain(N, h4, w4, 32); td.ddst = plain(N, h4, w4, 32);
+            GStep td; td.kind = GS_TOKENDEC; td.src = cp.dst; td.dsrc = b.dec_din; td.dst = ws.plain(N, h4, w4, 32); td.ddst = ws.plain(N, h4, w4, 32);
             td.N = N; td.h = h4; td.w = w4; td.C = 32; e.g_fwd.push_back(td);
             pair_src = td.dst; pair_dsrc = td.ddst;      // the differencing reads the decoder's output, not conv_pred's
         }
-        GStep ab; ab.kind = GS_ABSPAIR; ab.src = pair_src; ab.dsrc = pair_dsrc; ab.dst = plain(B, h4, w4, 32); ab.ddst = plain(B, h4, w4, 32);
+        GStep ab; ab.kind = GS_ABSPAIR; ab.src = pair_src; ab.dsrc = pair_dsrc; ab.dst = ws.plain(B, h4, w4, 32); ab.ddst = ws.plain(B, h4, w4, 32);
         ab.N = B; ab.h = h4; ab.w = w4; ab.C = 32; e.g_fwd.push_back(ab);
-        GStep bl; bl.kind = GS_BILINEAR; bl.src = ab.dst; bl.dsrc = ab.ddst; bl.dst = plain(B, H, W, 32); bl.ddst = plain(B, H, W, 32);
+        GStep bl; bl.kind = GS_BILINEAR; bl.src = ab.dst; bl.dsrc = ab.ddst; bl.dst = ws.plain(B, H, W, 32); bl.ddst = ws.plain(B, H, W, 32);
         bl.N = B; bl.h = h4; bl.w = w4; bl.C = 32; e.g_fwd.push_back(bl);
         GLayer& CL = e.g_layers[e.g_cls];
         shape(CL, bl.dst, 32, H, W, 1, 1);
         CL.dIn = bl.ddst; CL.grad_base = true;                                              // dA: the head's data gradient
         { GStep st; st.layer = e.g_cls; e.g_fwd.push_back(st); }
         e.gX3 = CL.A; e.gdX3 = CL.dA;
-        e.G = plain(B, H, W, 8);
+        e.G = ws.plain(B, H, W, 8);
     } else {
     // ---- decoder: x = f5; block i: nearest x2 into cat_i[:, :Cx], skip (written by its encoder producer) in cat_i[:, Cx:]
     const int skip_layer[4] = {stage_out[2], stage_out[1], stage_out[0], e.g_stem};          // f4, f3, f2, f1
@@ -2690,7 +2700,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     const int DG = ffc ? 3 : D, ND = DG * B;                                                // decoder groups / images
     auto absdiff = [&](const TRef& val, const TRef& grad, int coff, int C, int h_, int w_, GLayer& producer) {
         // third group of `val` (channels [coff, coff + C)) = |date 0 - date 1|; its gradient returns to `producer` as a contribution
-        TRef tmp = plain(N, h_, w_, C);
+        TRef tmp = ws.plain(N, h_, w_, C);
         GStep st; st.kind = GS_ABSDIFF; st.N = B; st.h = h_; st.w = w_; st.C = C;
         st.src = val; st.src.off += (int64_t)coff * T; st.dsrc = grad; st.dsrc.off += (int64_t)coff * T; st.ddst = tmp;
         e.g_fwd.push_back(st);
@@ -2698,14 +2708,14 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     };
     if (ffc) {      // x = [f5(date 0); f5(date 1); |f5 - f5|]: the last encoder layer writes the two dates into a 3B-image tensor
         GLayer& X = e.g_layers[xl];
-        X.A = plain(ND, X.Ho, X.Wo, X.C); X.dA = plain(ND, X.Ho, X.Wo, X.C);
+        X.A = ws.plain(ND, X.Ho, X.Wo, X.C); X.dA = ws.plain(ND, X.Ho, X.Wo, X.C);
         absdiff(X.A, X.dA, 0, X.C, X.Ho, X.Wo, X);
     }
     for (int i = 0; i < 5; ++i) {
         GLayer& X = e.g_layers[xl];
         const int Cx = X.C, hh = 2 * X.Ho, ww = 2 * X.Wo;
         const int Cs = i < 4 ? e.g_layers[skip_layer[i]].C : 0;
-        TRef cat = plain(ND, hh, ww, Cx + Cs), dcat = plain(ND, hh, ww, Cx + Cs);
+        TRef cat = ws.plain(ND, hh, ww, Cx + Cs), dcat = ws.plain(ND, hh, ww, Cx + Cs);
         { GStep st; st.kind = GS_UPSAMPLE; st.src = X.A; st.dst = cat; st.dsrc = X.dA; st.ddst = dcat; st.N = ND; st.h = X.Ho; st.w = X.Wo; st.C = Cx; e.g_fwd.push_back(st); }
         if (i < 4) {
             GLayer& Sk = e.g_layers[skip_layer[i]];
@@ -2719,7 +2729,7 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         if (ffc) D1.g_first = D2.g_first = 2;          // model.py:413-419: decoder(|f1 - f2|) runs before decoder(f1), decoder(f2)
         D1.dIn = dcat;
         if (e.debug_flags & 1) {
-            D2.dIn = plain(ND, hh, ww, D1.C); D1.grad_base = false;
+            D2.dIn = ws.plain(ND, hh, ww, D1.C); D1.grad_base = false;
             ViewRef v = view(D2.dIn, 0, D1.C, hh, ww);
             if (ffc) v.gmask = 7;
             D1.grad_src.push_back(v);
@@ -2731,17 +2741,17 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     //      (UnetSeg: X3 = d, B images, the head's output is the network's)
     GLayer& DL = e.g_layers[xl];
     const int nhead = D == 2 ? 3 * B : B;
-    e.gX3 = plain(nhead, H, W, 16); e.gdX3 = plain(nhead, H, W, 16);
+    e.gX3 = ws.plain(nhead, H, W, 16); e.gdX3 = ws.plain(nhead, H, W, 16);
     DL.A = e.gX3; DL.dA = e.gdX3;
     DL.grad_base = true;
     if (D == 2) {
         if (!ffc) {      // FFCTLCD's last decoder layer already holds [d(f1); d(f2); d(|f1 - f2|)]: the head reads it as it is
-            e.gFuseTmp = plain(N, H, W, 16);
+            e.gFuseTmp = ws.plain(N, H, W, 16);
             DL.grad_src.push_back(view(e.gFuseTmp, 0, 16, H, W));
         }
         e.g_raw3 = ws.take((int64_t)3 * B * e.label * H * W * 4); e.g_draw3 = ws.take((int64_t)3 * B * e.label * H * W * 4);
     }
-    e.G = plain(nhead, H, W, 8);
+    e.G = ws.plain(nhead, H, W, 8);
     }
     for (auto& L : e.g_layers)
         if ((int)L.extra_dst.size() > MAX_VIEWS || (int)L.grad_src.size() > MAX_VIEWS) { set_error("internal: too many views"); return 1; }
@@ -2756,26 +2766,22 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
     take_ref_images(e, ws);
     // ---- bind every conv-shaped launch
     const Binder bind{e, ws};
+    // weight gradient of a stride-2 layer over parity plane ph of its input (geom_plane): nt taps (ky, kx) of that parity
+    auto bind_plane = [&](WgradOp& op, const GLayer& L, int ci, int ph, int pad, int tap0, int nt, const int8_t* ky, const int8_t* kx, bool own_taps) {
+        const stcd_conv_geom gw = geom_plane(L.N, L.Hi, L.Wi, ci, L.in.ld, L.Ho, L.Wo, e.convs[L.conv].cout, L.dA.ld, ph, pad, nt, ky, kx);
+        bind.wgrad(op, gw, L.conv, L.in.off + ((int64_t)(ph >> 1) * L.Wi + (ph & 1)) * L.in.ld * T, L.dA.off, 0, tap0, L.Wi / 2,
+                   own_taps ? ky : nullptr, own_taps ? kx : nullptr);
+    };
     for (auto& L : e.g_layers) {
         if (L.kind == K_STEM7) {
             // 7x7 stride-2 weight gradient on the MFMA path: row 2y + ky - 3 lies in parity plane py = (ky + 1) & 1 at plane row
             // y + (ky - 3 - py) / 2; per plane 3x3 / 3x4 / 4x3 / 4x4 taps, run as stride-1 launches of <= 9 taps over plane views
-            // (see the stride-2 layers below).  fp32 mode (and any plan that does not fit) keeps the dedicated fp32 kernel.
+            // (geom_plane).  fp32 mode (and any plan that does not fit) keeps the dedicated fp32 kernel.
             L.nwg = 0;
             L.fwd = ConvOp();
-            if (e.dt == BF16 && e.use_mfma && e.use_gemm) {
-                // forward on the tap-list GEMM kernel: tap = filter row ky, and the 7 filter columns x 8 (padded) channels of a
-                // row are 112 contiguous bytes of the NHWC8 input -- one 64-"channel" row of 8 pixels starting 3 pixels to the left
-                stcd_conv_geom gs;
-                memset(&gs, 0, sizeof(gs));
-                gs.n = L.N; gs.hi = L.Hi; gs.wi = L.Wi; gs.ci = 64; gs.ldi = L.in.ld;
-                gs.hm = L.Ho; gs.wm = L.Wo; gs.in_stride = 2; gs.ho = L.Ho; gs.wo = L.Wo; gs.out_stride = 1;
-                gs.co = e.convs[L.conv].cout; gs.ldo = L.Y.ld; gs.ntaps = 7;
-                for (int t = 0; t < 7; ++t) { gs.dy[t] = (int8_t)(t - 3); gs.dx[t] = -3; }
-                bind.stem(L.fwd, gs, L.conv, L.groups);
-            }
+            if (e.dt == BF16 && e.use_mfma && e.use_gemm)      // forward on the tap-list GEMM kernel over 8-pixel rows
+                bind.stem(L.fwd, geom_stem_rows(L.N, L.Hi, L.Wi, L.in.ld, L.Ho, L.Wo, e.convs[L.conv].cout, L.Y.ld), L.conv, L.groups);
             if (!(e.dt == BF16 && e.use_mfma && e.use_wgroup)) continue;
-            const ConvW& cv = e.convs[L.conv];
             bool all_ok = true;
             int nops = 0;
             for (int ph = 0; ph < 4 && all_ok; ++ph) {
@@ -2787,18 +2793,9 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
                 const int nchunk = ((int)taps.size() + 8) / 9, per = ((int)taps.size() + nchunk - 1) / nchunk;
                 for (int c0 = 0; c0 < (int)taps.size(); c0 += per) {
                     const int nt = std::min(per, (int)taps.size() - c0);
-                    stcd_conv_geom gw;
-                    memset(&gw, 0, sizeof(gw));
-                    gw.n = L.N; gw.hi = L.Hi / 2; gw.wi = L.Wi; gw.ci = 8; gw.ldi = 2 * L.in.ld;
-                    gw.hm = L.Ho; gw.wm = L.Wo; gw.in_stride = 1; gw.ho = L.Ho; gw.wo = L.Wo; gw.out_stride = 1;
-                    gw.co = cv.cout; gw.ldo = L.dA.ld; gw.ntaps = nt;
                     int8_t oky[9], okx[9];
-                    for (int t = 0; t < nt; ++t) {
-                        const int ky = taps[c0 + t].first, kx = taps[c0 + t].second;
-                        gw.dy[t] = (int8_t)((ky - 3 - py) / 2); gw.dx[t] = (int8_t)((kx - 3 - px) / 2);
-                        oky[t] = (int8_t)ky; okx[t] = (int8_t)kx;
-                    }
-                    bind.wgrad(L.wg[nops], gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, 0, 0, L.Wi / 2, oky, okx);
+                    for (int t = 0; t < nt; ++t) { oky[t] = (int8_t)taps[c0 + t].first; okx[t] = (int8_t)taps[c0 + t].second; }
+                    bind_plane(L.wg[nops], L, 8, ph, 3, 0, nt, oky, okx, true);
                     all_ok = all_ok && L.wg[nops].plan.ok;
                     ++nops;
                 }
@@ -2808,73 +2805,38 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
             continue;
         }
         const ConvW& cv = e.convs[L.conv];
-        stcd_conv_geom g;
         const int stride = L.Hi / L.Ho;
-        if (L.kind == K_CONV3 && stride == 1) g = geom3(L.N, L.Hi, L.Wi, L.K, L.in.ld, cv.cout, L.Y.ld);
-        else if (L.kind == K_CONV1 && stride == 1) g = geom1(L.N, L.Hi, L.Wi, L.K, L.in.ld, cv.cout, L.Y.ld);
-        else {      // stride-2 gathers (3x3 p1 or 1x1)
-            memset(&g, 0, sizeof(g));
-            g.n = L.N; g.hi = L.Hi; g.wi = L.Wi; g.ci = L.K; g.ldi = L.in.ld;
-            g.hm = L.Ho; g.wm = L.Wo; g.in_stride = 2; g.ho = L.Ho; g.wo = L.Wo; g.out_stride = 1;
-            g.co = cv.cout; g.ldo = L.Y.ld;
-            if (L.kind == K_CONV3_S2) { g.ntaps = 9; for (int t = 0; t < 9; ++t) { g.dy[t] = (int8_t)(cv.fwd.ky[t] - 1); g.dx[t] = (int8_t)(cv.fwd.kx[t] - 1); } }
-            else { g.ntaps = 1; g.dy[0] = 0; g.dx[0] = 0; }
-        }
-        bind.conv(L.fwd, g, L.conv, false, 0, cv.cin, cv.cout, L.groups);
+        const bool k3 = L.kind == K_CONV3 || L.kind == K_CONV3_S2;
+        // forward (ldo: the conv output's) and, at stride 1, the weight gradient's (ldo: dY's) geometry; stride 2: a gather (3x3 p1 or 1x1)
+        auto geom_fwd = [&](int ldo) {
+            return stride == 2 ? geom_gather2(L.N, L.Hi, L.Wi, L.K, L.in.ld, L.Ho, L.Wo, cv.cout, ldo, cv.fwd, k3 ? 1 : 0)
+                               : k3 ? geom3(L.N, L.Hi, L.Wi, L.K, L.in.ld, cv.cout, ldo) : geom1(L.N, L.Hi, L.Wi, L.K, L.in.ld, cv.cout, ldo);
+        };
+        bind.conv(L.fwd, geom_fwd(L.Y.ld), L.conv, false, 0, cv.cin, cv.cout, L.groups);
         if (stride == 1) {
-            stcd_conv_geom gw = g; gw.ldo = L.dA.ld;
-            bind.wgrad(L.wg[0], gw, L.conv, L.in.off, L.dA.off);
+            bind.wgrad(L.wg[0], geom_fwd(L.dA.ld), L.conv, L.in.off, L.dA.off);
             L.nwg = 1;
-        } else {
-            // stride 2: input pixel (2m + ky - 1, 2n + kx - 1) lies in parity plane (py, px) at plane coordinates (m + dy, n + dx),
-            // dy = -1 for ky == 0 and 0 otherwise.  A plane is a VIEW of the NHWC tensor: pixel stride 2*ld, and a virtual row
-            // of Wi pixels (= two real rows), of which the first Wi/2 exist -- one stride-1 weight-gradient launch per plane.
-            static const int start[4] = {0, 1, 3, 5}, cnt[4] = {1, 2, 2, 4};
-            const int nph = L.kind == K_CONV3_S2 ? 4 : 1;
-            for (int ph = 0; ph < nph; ++ph) {
-                const int py = ph >> 1, px = ph & 1;
-                stcd_conv_geom gw;
-                memset(&gw, 0, sizeof(gw));
-                gw.n = L.N; gw.hi = L.Hi / 2; gw.wi = L.Wi; gw.ci = L.K; gw.ldi = 2 * L.in.ld;
-                gw.hm = L.Ho; gw.wm = L.Wo; gw.in_stride = 1; gw.ho = L.Ho; gw.wo = L.Wo; gw.out_stride = 1;
-                gw.co = cv.cout; gw.ldo = L.dA.ld;
-                gw.ntaps = L.kind == K_CONV3_S2 ? cnt[ph] : 1;
-                for (int t = 0; t < gw.ntaps; ++t) {
-                    const int ky = L.kind == K_CONV3_S2 ? cv.fwd.ky[start[ph] + t] : 1, kx = L.kind == K_CONV3_S2 ? cv.fwd.kx[start[ph] + t] : 1;
-                    gw.dy[t] = (int8_t)(ky == 0 ? -1 : 0); gw.dx[t] = (int8_t)(kx == 0 ? -1 : 0);
-                }
-                bind.wgrad(L.wg[ph], gw, L.conv, L.in.off + ((int64_t)py * L.Wi + px) * L.in.ld * T, L.dA.off, 0, start[ph], L.Wi / 2);
+        } else {      // one launch per parity plane of the input: the 1 + 2 + 2 + 4 taps of a 3x3, the one plane (0, 0) of a 1x1
+            L.nwg = k3 ? 4 : 1;
+            for (int ph = 0; ph < L.nwg; ++ph) {
+                const int tap0 = k3 ? PHASE3_TAP0[ph] : 0, nt = k3 ? PHASE3_TAP0[ph + 1] - tap0 : 1;
+                bind_plane(L.wg[ph], L, L.K, ph, k3 ? 1 : 0, tap0, nt, cv.fwd.ky + tap0, cv.fwd.kx + tap0, false);
             }
-            L.nwg = nph;
         }
         if (!L.has_dIn) continue;
         if (stride == 1) {
-            stcd_conv_geom gd = L.kind == K_CONV3 ? geom3(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld)
-                                                  : geom1(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld);
-            bind.conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
+            bind.conv(L.dgr[0], k3 ? geom3(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld)
+                                   : geom1(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, cv.cin, L.dIn.ld), L.conv, true, 0, cv.cout, cv.cin);
             L.ndgr = 1;
-        } else if (L.kind == K_CONV3_S2) {      // d(in)(2m+py, 2n+px) = sum_{dy<=py, dx<=px} dY(m+dy, n+dx) W[.][.][py+1-2dy][px+1-2dx]
-            static const int start[4] = {0, 1, 3, 5};
+        } else if (k3) {      // d(in)(2m+py, 2n+px) = sum_{dy<=py, dx<=px} dY(m+dy, n+dx) W[.][.][py+1-2dy][px+1-2dx]
             for (int ph = 0; ph < 4; ++ph) {
-                const int py = ph >> 1, px = ph & 1;
-                stcd_conv_geom gd;
-                memset(&gd, 0, sizeof(gd));
-                gd.n = L.N; gd.hi = L.Ho; gd.wi = L.Wo; gd.ci = cv.dgrad.kpad; gd.ldi = L.dA.ld;
-                gd.hm = L.Ho; gd.wm = L.Wo; gd.in_stride = 1; gd.ho = L.Hi; gd.wo = L.Wi; gd.out_stride = 2; gd.oy0 = py; gd.ox0 = px;
-                gd.co = cv.cin; gd.ldo = L.dIn.ld;
-                int t = 0;
-                for (int dy = 0; dy <= py; ++dy) for (int dx = 0; dx <= px; ++dx) { gd.dy[t] = (int8_t)dy; gd.dx[t] = (int8_t)dx; ++t; }
-                gd.ntaps = t;
-                bind.conv(L.dgr[ph], gd, L.conv, true, start[ph], cv.cout, cv.cin);
+                int tap0;
+                const stcd_conv_geom gd = geom_phase3(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, L.Hi, L.Wi, cv.cin, L.dIn.ld, ph, cv.dgrad, &tap0);
+                bind.conv(L.dgr[ph], gd, L.conv, true, tap0, cv.cout, cv.cin);
             }
             L.ndgr = 4;
-        } else {                                // 1x1 stride 2: only the even positions receive a gradient (the rest is zeroed)
-            stcd_conv_geom gd;
-            memset(&gd, 0, sizeof(gd));
-            gd.n = L.N; gd.hi = L.Ho; gd.wi = L.Wo; gd.ci = cv.dgrad.kpad; gd.ldi = L.dA.ld;
-            gd.hm = L.Ho; gd.wm = L.Wo; gd.in_stride = 1; gd.ho = L.Hi; gd.wo = L.Wi; gd.out_stride = 2;
-            gd.co = cv.cin; gd.ldo = L.dIn.ld; gd.ntaps = 1;
-            bind.conv(L.dgr[0], gd, L.conv, true, 0, cv.cout, cv.cin);
+        } else {              // 1x1 stride 2: only the even positions receive a gradient (the rest is zeroed)
+            bind.conv(L.dgr[0], geom_phase(L.N, L.Ho, L.Wo, cv.dgrad.kpad, L.dA.ld, L.Hi, L.Wi, cv.cin, L.dIn.ld, 0, cv.dgrad, 0, 0, 1), L.conv, true, 0, cv.cout, cv.cin);
             L.ndgr = 1;
         }
     }
@@ -2892,65 +2854,34 @@ static int configure_segcd(stcd_engine& e, int B, int H, int W) {
         bind.wgrad(e.g_pred_wg, geom3(st.N, st.h, st.w, st.C, st.src.ld, 32, st.ddst.ld), e.g_pred_conv, st.src.off, st.ddst.off);
         bind.conv(e.g_pred_dgr, geom3(st.N, st.h, st.w, cv.dgrad.kpad, st.ddst.ld, st.C, st.dsrc.ld), e.g_pred_conv, true, 0, 32, st.C);
     }
-    e.ws_tensors.clear();
     for (const auto& L : e.g_layers) {
-        auto rec = [&](const char* sfx, const TRef& t, int n, int h, int w, int c) {
-            if (t.off < 0) return;
-            stcd_ws_tensor r;
-            memset(&r, 0, sizeof(r));
-            snprintf(r.name, sizeof(r.name), "%s.%s", L.name.c_str(), sfx);
-            r.offset_bytes = t.off; r.n = n; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
-            e.ws_tensors.push_back(r);
-        };
-        rec("in", L.in, L.N, L.Hi, L.Wi, L.K);
-        rec("Y", L.Y, L.N, L.Ho, L.Wo, L.C);
-        rec("A", L.A, L.N, L.Ho, L.Wo, L.C);
-        rec("dY", L.dA, L.N, L.Ho, L.Wo, L.C);
-        if (L.has_dIn) rec("dIn", L.dIn, L.N, L.Hi, L.Wi, L.K);
-        rec("res", L.res, L.N, L.Ho, L.Wo, L.C);
+        ws.tensor(L.name + ".in", L.in, L.N, L.Hi, L.Wi, L.K);
+        ws.tensor(L.name + ".Y", L.Y, L.N, L.Ho, L.Wo, L.C);
+        ws.tensor(L.name + ".A", L.A, L.N, L.Ho, L.Wo, L.C);
+        ws.tensor(L.name + ".dY", L.dA, L.N, L.Ho, L.Wo, L.C);
+        if (L.has_dIn) ws.tensor(L.name + ".dIn", L.dIn, L.N, L.Hi, L.Wi, L.K);
+        ws.tensor(L.name + ".res", L.res, L.N, L.Ho, L.Wo, L.C);
     }
     for (const GStep& st : e.g_fwd) {      // the base_resnet steps that are no layer
         if (st.kind != GS_BCONV && st.kind != GS_BILINEAR) continue;
         const bool cp = st.kind == GS_BCONV;
         const int ho = cp ? st.h : 4 * st.h, wo = cp ? st.w : 4 * st.w;
-        auto rec = [&](const char* name, const TRef& t, int h, int w, int c) {
-            stcd_ws_tensor r;
-            memset(&r, 0, sizeof(r));
-            snprintf(r.name, sizeof(r.name), "%s.%s", cp ? "conv_pred" : "upsamplex4", name);
-            r.offset_bytes = t.off; r.n = st.N; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
-            e.ws_tensors.push_back(r);
-        };
-        rec("in", st.src, st.h, st.w, st.C); rec("Y", st.dst, ho, wo, 32);
-        rec("dY", st.ddst, ho, wo, 32); rec("dIn", st.dsrc, st.h, st.w, st.C);
+        const std::string n = cp ? "conv_pred." : "upsamplex4.";
+        ws.tensor(n + "in", st.src, st.N, st.h, st.w, st.C); ws.tensor(n + "Y", st.dst, st.N, ho, wo, 32);
+        ws.tensor(n + "dY", st.ddst, st.N, ho, wo, 32); ws.tensor(n + "dIn", st.dsrc, st.N, st.h, st.w, st.C);
     }
     for (const GStep& st : e.g_fwd) {      // the BIT token path: the decoder's maps and the tokens around the encoder (fp32)
         if (st.kind != GS_TOKENDEC) continue;
-        auto rec = [&](const char* name, int64_t off, int n, int h, int w, int dtype) {
-            stcd_ws_tensor r;
-            memset(&r, 0, sizeof(r));
-            snprintf(r.name, sizeof(r.name), "%s", name);
-            r.offset_bytes = off; r.n = n; r.h = h; r.w = w; r.c = 32; r.ld = 32; r.dtype = dtype;
-            e.ws_tensors.push_back(r);
-        };
-        rec("bit.dec.in", st.src.off, st.N, st.h, st.w, e.dt); rec("bit.dec.Y", st.dst.off, st.N, st.h, st.w, e.dt);
-        rec("bit.dec.dY", st.ddst.off, st.N, st.h, st.w, e.dt); rec("bit.dec.dIn", st.dsrc.off, st.N, st.h, st.w, e.dt);
-        rec("bit.tokens.in", e.bit.tok_in, st.N, 1, 4, F32); rec("bit.tokens.Y", e.bit.tok_out, st.N, 1, 4, F32);
-        rec("bit.tokens.dY", e.bit.dtok_out, st.N, 1, 4, F32); rec("bit.tokens.dIn", e.bit.dtok_in, st.N, 1, 4, F32);
+        ws.tensor("bit.dec.in", st.src.off, 32, st.N, st.h, st.w, 32); ws.tensor("bit.dec.Y", st.dst.off, 32, st.N, st.h, st.w, 32);
+        ws.tensor("bit.dec.dY", st.ddst.off, 32, st.N, st.h, st.w, 32); ws.tensor("bit.dec.dIn", st.dsrc.off, 32, st.N, st.h, st.w, 32);
+        ws.tensor("bit.tokens.in", e.bit.tok_in, 32, st.N, 1, 4, 32, F32); ws.tensor("bit.tokens.Y", e.bit.tok_out, 32, st.N, 1, 4, 32, F32);
+        ws.tensor("bit.tokens.dY", e.bit.dtok_out, 32, st.N, 1, 4, 32, F32); ws.tensor("bit.tokens.dIn", e.bit.dtok_in, 32, st.N, 1, 4, 32, F32);
     }
     e.slab = ws.take(e.slab_floats * 4);
-    e.bias_jobs.clear();
-    {
-        BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[e.g_head_conv].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
-        e.bias_jobs.push_back(jb);
-        if (e.bres && e.dt == BF16) {      // conv_pred's bias gradient: summed in the integer accumulator (launch_bias_grad), converted at the end
-            BiasJob jp{}; jp.acc_off = e.g_pred_bias_acc; jp.out_off = e.convs[e.g_pred_conv].b_off; jp.C = 32; jp.valid = 32; jp.scale = BN_BS;
-            e.bias_jobs.push_back(jp);
-        }
-        e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
-    }
-    build_pack_jobs(e, ws);
-    e.jobs_uploaded_ws = nullptr;
-    e.ws_bytes = ws.cur;
+    ws.bias_job(e.final_bias_acc, e.g_head_conv, 8, e.label);
+    // conv_pred's bias gradient: summed in the integer accumulator (launch_bias_grad), converted at the end
+    if (e.bres && e.dt == BF16) ws.bias_job(e.g_pred_bias_acc, e.g_pred_conv, 32, 32);
+    ws.tables();
     return 0;
 }
 
@@ -3184,6 +3115,18 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
 
 #include "engine_cf.inl"
 
+// The shape-bound state every configure_* rebuilds from empty, reset in ONE place (stcd_configure) -- a vector left out here lets a
+// table grow with every re-configure (tests/test_lifecycle_cpu.py).  Per-layer fields of the table-time vectors (sn_blocks, g_layers,
+// xc) are reset by their family's own loops; build_pack_jobs clears the job tables it owns.
+static void reset_plan(stcd_engine& e) {
+    e.enc.clear(); e.dec.clear(); e.ups.clear();
+    e.drops.clear(); e.drop_floats = 0;
+    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0;
+    e.ws_tensors.clear(); e.bias_jobs.clear();
+    e.g_fwd.clear(); e.sn_order.clear();
+    if (e.cf) cf_reset_plan(*e.cf);
+}
+
 }  // namespace stcd
 
 // ================================================================================================ C ABI
@@ -3347,6 +3290,7 @@ int stcd_configure(stcd_engine* e, int batch, int height, int width) {
     e->configured = false;
     e->packed_tag = 0; e->packed_ws = nullptr; e->packed_level = -1;
     e->B = batch; e->H = height; e->W = width;
+    reset_plan(*e);
     if (is_cf(e->arch)) {
         STCD_CHECK(height % 32 == 0 && width % 32 == 0, "ChangeFormer needs height and width divisible by 32 (stride-4 patch embedding, sr_ratio 8)");
         if (configure_cf(*e, batch, height, width)) return 1;

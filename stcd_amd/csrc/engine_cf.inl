@@ -227,35 +227,28 @@ static void build_cf_tables(stcd_engine& e) {
     P.nsites = site;
 }
 
+// the ChangeFormer part of reset_plan (stcd_configure): dropout sites and the column-sum job tables
+static void cf_reset_plan(CfPlan& P) {
+    P.sites.clear();
+    for (int st = 0; st < 2; ++st) { P.cjobs[st].clear(); P.cj_blocks[st] = 0; P.cj_fin[st] = 0; }
+}
+
 static int configure_cf(stcd_engine& e, int B, int H, int W) {
     CfPlan& P = *e.cf;
     const int64_t T = (int64_t)dsize(e.dt);
     const int D = P.D, N2 = 2 * B;
-    e.drops.clear(); e.drop_floats = 0;
-    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0;
-    e.ws_tensors.clear();
-    P.sites.clear();
     std::vector<CfDiff*> aux_pending;      // the auxiliary heads' backward launches are bound once the zero arena exists
-    Bump ws;
+    Planner ws(e);
     auto mk = [&](int n, int h, int w, int c, bool grad = true) {
         CfT t; t.n = n; t.h = h; t.w = w; t.c = c;
-        t.v.off = ws.take((int64_t)n * h * w * c * T); t.v.ld = c;
-        if (grad) { t.g.off = ws.take((int64_t)n * h * w * c * T); t.g.ld = c; }
+        t.v = ws.plain(n, h, w, c);
+        if (grad) t.g = ws.plain(n, h, w, c);
         return t;
     };
-    auto rec = [&](const std::string& name, const TRef& t, int n, int h, int w, int c) {
-        if (t.off < 0) return;
-        stcd_ws_tensor r;
-        memset(&r, 0, sizeof(r));
-        snprintf(r.name, sizeof(r.name), "%s", name.c_str());
-        r.offset_bytes = t.off; r.n = n; r.h = h; r.w = w; r.c = c; r.ld = t.ld; r.dtype = e.dt;
-        e.ws_tensors.push_back(r);
-    };
-    auto recT = [&](const std::string& name, const CfT& t) { rec(name, t.v, t.n, t.h, t.w, t.c); rec(name + ".grad", t.g, t.n, t.h, t.w, t.c); };
+    auto recT = [&](const std::string& name, const CfT& t) { ws.tensor(name, t.v, t.n, t.h, t.w, t.c); ws.tensor(name + ".grad", t.g, t.n, t.h, t.w, t.c); };
     int64_t scratch_floats = 4096;
     auto need = [&](int64_t f) { scratch_floats = std::max(scratch_floats, f); };
     int64_t cpart_floats[2] = {0, 0};
-    P.cjobs[0].clear(); P.cjobs[1].clear(); P.cj_blocks[0] = P.cj_blocks[1] = 0; P.cj_fin[0] = P.cj_fin[1] = 0;
     auto add_colsum = [&](int stage, const TRef& dy, int64_t M, int C, int64_t out_off) {
         ColsumJob j{};
         j.x_off = dy.off; j.M = M; j.out_off = out_off; j.ld = dy.ld; j.C = C;
@@ -288,7 +281,7 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
         P.sites.push_back(s);
     };
 
-    e.X0 = TRef(); e.X0.off = ws.take((int64_t)N2 * H * W * 8 * T); e.X0.ld = 8;
+    e.X0 = ws.plain(N2, H, W, 8);
     // ------------------------------------------------------------------------------------------ encoder
     int hin = H, win = W;
     TRef in_v = e.X0, in_g;
@@ -417,33 +410,22 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
     auto bind_up = [&](CfUp& U, const CfT& in, int h, int w) {
         U.in = in;
         U.out = mk(B, 2 * h, 2 * w, D);
-        U.dtmp = TRef(); U.dtmp.off = ws.take((int64_t)B * h * w * D * T); U.dtmp.ld = D;
+        U.dtmp = ws.plain(B, h, w, D);
         add_colsum(0, U.out.g, (int64_t)B * 4 * h * w, D, U.b_off);
-        for (int ph = 0; ph < 4; ++ph) {
-            const int py = ph >> 1, px = ph & 1;
-            const ConvW& cv = e.convs[U.conv[ph]];
-            stcd_conv_geom g;
-            memset(&g, 0, sizeof(g));
-            g.n = B; g.hi = h; g.wi = w; g.ci = D; g.ldi = in.v.ld; g.hm = h; g.wm = w; g.in_stride = 1;
-            g.ho = 2 * h; g.wo = 2 * w; g.out_stride = 2; g.oy0 = py; g.ox0 = px; g.co = D; g.ldo = D; g.ntaps = 4;
-            for (int t = 0; t < 4; ++t) { g.dy[t] = (int8_t)((py + 1 - cv.fwd.ky[t]) / 2); g.dx[t] = (int8_t)((px + 1 - cv.fwd.kx[t]) / 2); }
+        for (int ph = 0; ph < 4; ++ph) {      // phase ph: the four taps of its own ConvW (build_cf_tables), padding 1
+            const stcd_conv_geom g = geom_phase(B, h, w, D, in.v.ld, 2 * h, 2 * w, D, D, ph, e.convs[U.conv[ph]].fwd, 1, 0, 4);
             bind.conv(U.fwd[ph], g, U.conv[ph], false, 0, D, D);
             bind.wgrad(U.wg[ph], g, U.conv[ph], in.v.off, U.out.g.off, 0);
         }
-        for (int k = 0; k < 2; ++k) {
+        for (int k = 0; k < 2; ++k) {         // data gradient: the 16-tap stride-2 gather over d(out) in two 8-tap launches
             const ConvW& cv = e.convs[U.conv[k]];
-            stcd_conv_geom g;
-            memset(&g, 0, sizeof(g));
-            g.n = B; g.hi = 2 * h; g.wi = 2 * w; g.ci = cv.dgrad.kpad; g.ldi = D; g.hm = h; g.wm = w; g.in_stride = 2;
-            g.ho = h; g.wo = w; g.out_stride = 1; g.co = D; g.ldo = D; g.ntaps = 8;
-            for (int t = 0; t < 8; ++t) { g.dy[t] = (int8_t)(cv.dgrad.ky[t] - 1); g.dx[t] = (int8_t)(cv.dgrad.kx[t] - 1); }
-            bind.conv(U.dgr[k], g, U.conv[k], true, 0, D, D);
+            bind.conv(U.dgr[k], geom_gather2(B, 2 * h, 2 * w, cv.dgrad.kpad, D, h, w, D, D, cv.dgrad, 1), U.conv[k], true, 0, D, D);
         }
     };
     auto bind_res = [&](CfRes& R, const CfT& x, int h, int w) {
         R.x = x;
         R.r1 = mk(B, h, w, D); R.y2 = mk(B, h, w, D); R.out = mk(B, h, w, D);
-        R.dtmp = TRef(); R.dtmp.off = ws.take((int64_t)B * h * w * D * T); R.dtmp.ld = D;
+        R.dtmp = ws.plain(B, h, w, D);
         bind_3x3(R.c1, x.v, R.dtmp, D, B, h, w, R.r1.v, R.r1.g, 0);
         bind_3x3(R.c2, R.r1.v, R.r1.g, D, B, h, w, R.y2.v, R.y2.g, 0);
     };
@@ -454,7 +436,7 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
     recT("dec.up2", P.up2.out); recT("dec.res2", P.res2.out); recT("dec.up1", P.up1.out); recT("dec.res1", P.res1.out);
     recT("dec.res1.r1", P.res1.r1); recT("dec.res2.r1", P.res2.r1);
     need(colsum_scratch_floats((int64_t)B * H * W, D)); need(bn_precise_scratch_floats((int64_t)B * h1 * w1, D));
-    e.G = TRef(); e.G.off = ws.take((int64_t)B * H * W * 8 * T); e.G.ld = 8;
+    e.G = ws.plain(B, H, W, 8);
     {
         const ConvW& cv = e.convs[P.head_conv];
         bind.conv(P.head_fwd, geom3(B, H, W, D, D, e.label, e.label), P.head_conv, false, 0, D, e.label);
@@ -482,19 +464,9 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
     for (int st = 0; st < 2; ++st) P.cjobs_off[st] = ws.take((int64_t)P.cjobs[st].size() * sizeof(ColsumJob) + 16);
     take_ref_images(e, ws, !(e.dt == BF16 && e.use_mfma));      // (fp64 accumulators: the reference weight-gradient path only)
     e.slab = ws.take(e.slab_floats * 4);
-    e.bias_jobs.clear();
-    {
-        BiasJob jb{}; jb.acc_off = e.final_bias_acc; jb.out_off = e.convs[P.head_conv].b_off; jb.C = 8; jb.valid = e.label; jb.scale = BN_BS;
-        e.bias_jobs.push_back(jb);
-        for (int k = 0; k < 4 && P.aux_bwd; ++k) {       // the auxiliary heads' first-conv biases
-            BiasJob ja{}; ja.acc_off = P.df[k].aux_bias_acc; ja.out_off = e.convs[P.df[k].aux_conv0].b_off; ja.C = 8; ja.valid = e.label; ja.scale = BN_BS;
-            e.bias_jobs.push_back(ja);
-        }
-        e.bias_jobs_off = ws.take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
-    }
-    build_pack_jobs(e, ws);
-    e.jobs_uploaded_ws = nullptr;
-    e.ws_bytes = ws.cur;
+    ws.bias_job(e.final_bias_acc, P.head_conv, 8, e.label);
+    for (int k = 0; k < 4 && P.aux_bwd; ++k) ws.bias_job(P.df[k].aux_bias_acc, P.df[k].aux_conv0, 8, e.label);      // the auxiliary heads' first-conv biases
+    ws.tables();
     return 0;
 }
 

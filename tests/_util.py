@@ -1,12 +1,51 @@
 """Shared helpers of the parity tests."""
+import ctypes as C
+import hashlib
+import json
 import re
 
 import numpy as np
 import torch
 
+from stcd_amd import _lib
+
 
 def t(a):
     return torch.from_numpy(np.asarray(a))
+
+
+def plan_values(m):
+    """Everything the ABI tells about the current configuration."""
+    l, eng = _lib.lib(), m._engine
+    h = eng._h
+    v = {"workspace_bytes": l.stcd_workspace_bytes(h), "dropout_floats": l.stcd_dropout_floats(h), "output_floats": l.stcd_output_floats(h)}
+    di = _lib.DropoutInfo()
+    v["dropout"] = []
+    for i in range(l.stcd_num_dropout(h)):
+        _lib.check(l.stcd_dropout_info_get(h, i, C.byref(di)))
+        v["dropout"].append((di.name.decode(), di.rows, di.channels, di.offset))
+    wt = _lib.WsTensor()
+    v["ws_tensors"] = []
+    for i in range(l.stcd_ws_tensor_count(h)):
+        _lib.check(l.stcd_ws_tensor_get(h, i, C.byref(wt)))
+        v["ws_tensors"].append((wt.name.decode(), wt.offset_bytes, wt.n, wt.h, wt.w, wt.c, wt.ld, wt.dtype))
+    if eng.arch == "changeformer":
+        v["cf_outputs"], v["cf_sites"] = eng.cf_outputs(), eng.cf_sites()
+    v["stage_ranges"] = []
+    for stage in (0, 1):
+        b, e = C.c_int64(), C.c_int64()
+        _lib.check(l.stcd_grad_stage_range(h, stage, C.byref(b), C.byref(e)))
+        v["stage_ranges"].append((b.value, e.value))
+    return v
+
+
+def plan_layout(m):
+    """What tests/golden/plan_layout.json pins of a configured module: three sizes, the number of named workspace tensors and a
+    SHA-256 over the canonical text (JSON, sorted keys, no spaces) of plan_values()."""
+    v = plan_values(m)
+    text = json.dumps(v, sort_keys=True, separators=(",", ":"))
+    return {"workspace_bytes": v["workspace_bytes"], "dropout_floats": v["dropout_floats"], "output_floats": v["output_floats"],
+            "ws_tensors": len(v["ws_tensors"]), "sha256": hashlib.sha256(text.encode()).hexdigest()}
 
 
 def grad_summary(g):

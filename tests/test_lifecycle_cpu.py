@@ -3,8 +3,9 @@
 Every row of tests/lifecycle_spec.py is created through the C ABI and configured S1, S2, S1: every call succeeds (so the table of
 shapes is one the GPU test can run), the plan differs between S1 and S2, and the second S1 reproduces the first S1's plan exactly
 -- workspace bytes, the Dropout2d table, every named workspace tensor, ChangeFormer's output layout and dropout sites, the
-gradient stage ranges.  Each configure_* rebuilds about a dozen vectors behind its own list of .clear() calls: one forgotten
-clear that lets a table grow fails here (tried: without `e.ws_tensors.clear()` in configure_fcsiam the twelve FC-Siam cases fail).
+gradient stage ranges.  stcd_configure resets the dozen vectors and counters every configure_* rebuilds in one place
+(reset_plan); a vector left out of that reset lets a table grow and fails here (tried: without `e.ws_tensors.clear()` all 32
+cases fail).
 The two lifecycle guards that need no device answer as well.
 """
 import ctypes as C
@@ -13,31 +14,7 @@ import pytest
 
 from stcd_amd import _lib
 from tests import lifecycle_spec as L
-
-
-def plan_values(m):
-    """Everything the ABI tells about the current configuration."""
-    l, eng = _lib.lib(), m._engine
-    h = eng._h
-    v = {"workspace_bytes": l.stcd_workspace_bytes(h), "dropout_floats": l.stcd_dropout_floats(h), "output_floats": l.stcd_output_floats(h)}
-    di = _lib.DropoutInfo()
-    v["dropout"] = []
-    for i in range(l.stcd_num_dropout(h)):
-        _lib.check(l.stcd_dropout_info_get(h, i, C.byref(di)))
-        v["dropout"].append((di.name.decode(), di.rows, di.channels, di.offset))
-    wt = _lib.WsTensor()
-    v["ws_tensors"] = []
-    for i in range(l.stcd_ws_tensor_count(h)):
-        _lib.check(l.stcd_ws_tensor_get(h, i, C.byref(wt)))
-        v["ws_tensors"].append((wt.name.decode(), wt.offset_bytes, wt.n, wt.h, wt.w, wt.c, wt.ld, wt.dtype))
-    if eng.arch == "changeformer":
-        v["cf_outputs"], v["cf_sites"] = eng.cf_outputs(), eng.cf_sites()
-    v["stage_ranges"] = []
-    for stage in (0, 1):
-        b, e = C.c_int64(), C.c_int64()
-        _lib.check(l.stcd_grad_stage_range(h, stage, C.byref(b), C.byref(e)))
-        v["stage_ranges"].append((b.value, e.value))
-    return v
+from tests._util import plan_values
 
 
 @pytest.mark.parametrize("debug", [0, 1])
