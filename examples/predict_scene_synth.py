@@ -31,6 +31,10 @@ parser.add_argument("--tta", type=str, default="none", choices=("none", "flip", 
                     help="test-time augmentation: average the 4 mirror views or all 8 symmetries of the square")
 parser.add_argument("--load_path", type=str, default="", help="state_dict of a trained SiamUnet_diff(3, 2)")
 parser.add_argument("--seed", type=int, default=7)
+parser.add_argument("--vector", type=str, default="", metavar="OUT.geojson",
+                    help="also write the predicted change objects as GeoJSON polygons (pixel coordinates)")
+parser.add_argument("--min_area", type=int, default=4, help="with --vector: objects below this many pixels are dropped")
+parser.add_argument("--max_hole", type=int, default=4, help="with --vector: holes of at most this many pixels are filled")
 
 
 def main(argv=None):
@@ -58,6 +62,14 @@ def main(argv=None):
     print(f"change pixels predicted {int(res.mask.sum())} / labelled {int((label >= 1).sum())}; mean change probability {float(res.prob.mean()):.4f}")
     print(f"confusion matrix [label, pred]: {res.cm.tolist()}")
     print(f"OA {s['oa']:.4f}  precision {s['precision'][1]:.4f}  recall {s['recall'][1]:.4f}  F1 {s['f1'][1]:.4f}  IoU {s['iou'][1]:.4f}")
+    if args.vector:
+        # the mask as vector data: small objects and small holes removed, the rest numbered, outlined and written as polygons
+        from stcd_amd import objects
+        clean = objects.filter_objects(res.mask.contiguous(), args.min_area, args.max_hole)
+        comp = objects.label_components(clean)
+        rings = objects.object_rings(comp)
+        doc = objects.rings_to_geojson(rings, path=args.vector, properties=objects.object_table(comp))
+        print(f"{len(doc['features'])} polygons ({rings.count} rings, {int(rings.vertices.shape[0])} vertices) written to {args.vector}")
     return res
 
 

@@ -518,6 +518,45 @@ int stcd_objects_table(const int32_t* labels, int height, int width, int n, cons
 int stcd_mask_filter_objects(const uint8_t* in, int height, int width, int connectivity, int64_t min_area, int64_t max_hole,
                              int mask_value, uint8_t* out, void* scratch, int64_t scratch_bytes, void* hip_stream);
 
+/* ---- change polygons: the boundary rings of the objects of a label image (labels int32 [height,width]: <= 0 is background, as
+ *      stcd_objects_label numbers them or any other labelling).  tests/rings_spec.py states every output.  Lattice: vertex (y, x)
+ *      with 0 <= y <= height, 0 <= x <= width; pixel (i, j) is the unit square between (i, j) and (i + 1, j + 1) and owns one
+ *      directed unit edge per side whose neighbour carries another label: top east, right south, bottom west, left north, so an
+ *      outer ring runs (i,j), (i,j+1), (i+1,j+1), (i+1,j).  The successor of an edge is the edge of the same label that leaves its
+ *      head; where two diagonal pixels of a label meet (the other two carrying other labels) the ring crosses to the other pixel
+ *      under connectivity 8 and stays with its own pixel under connectivity 4.  The cycles of that map are the rings; only their
+ *      corners are kept (the tails of the edges whose predecessor has another direction), in travel order from the ring's smallest
+ *      edge in (tail y, tail x, direction) order; rings are ordered by that edge, i.e. in raster order of their first vertex.
+ *      Two phases with one host read between them: the count entry leaves R (rings), V (vertices) and a status word on the device;
+ *      the caller reads them, allocates, and hands R and V to the write entry.  The scratch buffer carries the state from the one
+ *      to the other.  Integers only, every output a pure function of the input; neither entry allocates, copies to the host or
+ *      synchronises; height * width must be below 2^31 and connectivity be 4 or 8; height == 0 or width == 0 launches nothing.
+ *      No thread walks a ring: corners are found from the 2 x 2 pixels round a vertex, numbered by a three-launch prefix sum, linked
+ *      to the next corner along the straight run (at most max(height, width) unit steps, under an iteration cap), and the ring's
+ *      first corner and every corner's rank come from pointer jumping, one launch per round.
+ *      max_corners (below 2^31) is the capacity of the per-corner part of the scratch buffer: R cannot be known before the rings
+ *      are ranked, so the caller sizes that part before V is known.  If V exceeds it the count entry still writes the exact V, sets
+ *      status bit 4 and computes nothing else; the caller repeats the call with max_corners >= V.
+ *      Status word: 0, or bits 1 / 2: an iteration cap or an impossible link (a bug, never a property of the input), 4: V is above
+ *      max_corners, 8 (write entry, in the scratch header only): R / V are not what the count phase left. ---- */
+/* Bytes of the scratch buffer of the two entries below (8-byte aligned): 32 + 4 per lattice vertex ((height + 1) * (width + 1), about
+ * 4 per pixel) + 8 per 4096 vertices + 37 per corner of capacity (+ 16 per 4096 of them); 0 for arguments they refuse. */
+int64_t stcd_rings_scratch_bytes(int height, int width, int64_t max_corners);
+/* counts: int64 [3] on the device = (R, V, status).  Launches: the three-launch prefix sum over the corners, the links,
+ * ceil(log2 max_corners) pointer-jumping rounds (a round past ceil(log2 V) returns at once), the count of the ring starts. */
+int stcd_rings_count(const int32_t* labels, int height, int width, int connectivity, int64_t max_corners, int64_t* counts, void* scratch,
+                     int64_t scratch_bytes, void* hip_stream);
+/* After stcd_rings_count on the same labels, shape, connectivity, max_corners and scratch, with the R and V it left:
+ * vertices int32 [V,2] = (y, x), the first vertex of a ring not repeated; offsets int64 [R+1], ring r is vertices[offsets[r] ..
+ * offsets[r+1]); object int32 [R], the ring's label; area2 int64 [R] = sum over consecutive vertices of x_t * y_h - x_h * y_t, twice
+ * the area: positive for an outer ring, negative for a hole (one 64-bit integer atomic per run of a ring within 64 consecutive
+ * corners).  Refused before any launch: n_vertices above max_corners, or an (n_rings, n_vertices) pair no count phase can leave
+ * (negative, n_vertices odd or below 4 * n_rings, one of them 0 alone).  A pair that passes those checks but is not the one in
+ * the scratch header is found on the device: nothing is written and bit 8 of the header's status word (scratch byte 20) is set.
+ * n_rings == 0 writes offsets[0] = 0 alone. */
+int stcd_rings_write(const int32_t* labels, int height, int width, int connectivity, int64_t max_corners, int64_t n_rings, int64_t n_vertices,
+                     int32_t* vertices, int64_t* offsets, int32_t* object, int64_t* area2, void* scratch, int64_t scratch_bytes, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

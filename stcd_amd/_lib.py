@@ -167,6 +167,9 @@ _PROTOS = {
     "stcd_objects_label": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "stcd_objects_table": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "stcd_mask_filter_objects": (_i, [_vp, _i, _i, _i, _i64, _i64, _i, _vp, _vp, _i64, _vp]),
+    "stcd_rings_scratch_bytes": (_i64, [_i, _i, _i64]),
+    "stcd_rings_count": (_i, [_vp, _i, _i, _i, _i64, _vp, _vp, _i64, _vp]),
+    "stcd_rings_write": (_i, [_vp, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv_fused": (_i, [C.POINTER(ConvGeom), C.POINTER(ConvFused), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),

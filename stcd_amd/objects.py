@@ -5,10 +5,15 @@ No counterpart in the reference: the pseudo-label cleaning of ``selftrain.mask_c
 GPU (the checks of ``selftrain._check_mask``), raises ``StcdError`` and has no CPU fallback; the kernels are
 stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_table`` and ``stcd_mask_filter_objects``
 (include/stcd_hip.h).  All outputs are integers: tests/objects_spec.py states them in numpy and the tests ask for equality.
+
+``object_rings`` goes on from numbered objects to vector data: the boundary rings of every object with their holes, on the device
+(stcd_amd/csrc/kernels_rings.hip behind ``stcd_rings_count`` and ``stcd_rings_write``; tests/rings_spec.py is the specification),
+and ``rings_to_geojson`` writes them as polygons on the host.
 """
 from __future__ import annotations
 
 import ctypes as C
+import json
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -32,6 +37,14 @@ class ObjectTable(NamedTuple):
     area: torch.Tensor                  # int64 [n] on the device
     bbox: torch.Tensor                  # int32 [n,4] on the device: (y0, x0, y1, x1), inclusive
     overlap: Optional[torch.Tensor]     # int64 [n,2] on the device: (pixels not ignored by the overlay, those where it is set)
+
+
+class Rings(NamedTuple):
+    vertices: torch.Tensor              # int32 [V,2] on the device: (y, x) lattice corners, ring after ring, the first not repeated
+    offsets: torch.Tensor               # int64 [count+1] on the device: ring r is vertices[offsets[r]:offsets[r + 1]]
+    object: torch.Tensor                # int32 [count] on the device: the label of the ring's object
+    area2: torch.Tensor                 # int64 [count] on the device: twice the signed area, > 0 outer ring, < 0 hole
+    count: int
 
 
 class ObjectScores(NamedTuple):
@@ -149,6 +162,147 @@ def filter_objects(mask: torch.Tensor, min_area: int = 0, max_hole: int = 0, con
         if check:
             _raise_if_status(int(scratch[-4:].cpu().numpy().view(np.int32)[0]), "filter_objects")
     return out
+
+
+def _check_components(components):
+    labels, n = components.labels, int(components.count)
+    if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.dim() != 2 or not labels.is_cuda or not labels.is_contiguous():
+        raise StcdError("components.labels must be a contiguous int32 [H,W] tensor on the GPU")
+    H, W = (int(v) for v in labels.shape)
+    _check_shape(H, W)
+    if not 0 <= n <= H * W:
+        raise StcdError(f"components.count must be in [0, {H * W}], got {n}")
+    return labels, n, H, W
+
+
+def _ring_scratch_for(device, height: int, width: int, max_corners: int) -> torch.Tensor:
+    nbytes = int(_lib.lib().stcd_rings_scratch_bytes(int(height), int(width), int(max_corners)))
+    key = (str(device), "rings", nbytes)
+    t = _SCRATCH.get(key)
+    if t is None:
+        t = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+def object_rings(components: Components, connectivity: int = 8, max_corners: Optional[int] = None) -> Rings:
+    """The boundary rings of every object of ``components`` (``label_components``' result, or any int32 label image with its
+    largest label as ``count``), on the device: for each object its outer ring (``area2 > 0``) and one ring per hole
+    (``area2 < 0``), as corner vertices ``(y, x)`` on the pixel lattice, in raster order of each ring's first vertex (include/stcd_hip.h,
+    ``stcd_rings_count`` / ``stcd_rings_write``; tests/rings_spec.py is the specification).  ``connectivity`` decides where two
+    diagonal pixels of one object meet: 8 joins them into one ring, 4 keeps them apart; use the connectivity the labels were made
+    with (with 4 on labels made with 8 an object can have several outer rings).
+
+    One host read, of ring count, vertex count and status (24 bytes), between the two phases.  ``max_corners`` is the capacity of
+    the per-corner scratch, which has to be sized before the vertex count is known: by default a quarter of the pixel count plus
+    4096; if the scene has more corners the count phase is repeated once with the exact number (a second host read)."""
+    labels, n, H, W = _check_components(components)
+    connectivity = _check_connectivity(connectivity)
+    dev = labels.device
+    bound = 4 * (H + 1) * (W + 1)
+    if max_corners is None:
+        max_corners = H * W // 4 + 4096
+    max_corners = int(max_corners)
+    if max_corners < 0:
+        raise StcdError(f"max_corners must be >= 0, got {max_corners}")
+    max_corners = min(max_corners, bound, 2 ** 31 - 1)
+    with torch.cuda.device(dev):
+        if n == 0 or H == 0 or W == 0:
+            return Rings(torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                         torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), 0)
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+        for attempt in range(2):
+            scratch = _ring_scratch_for(dev, H, W, max_corners)
+            _lib.check(_lib.lib().stcd_rings_count(_ptr(labels), H, W, connectivity, max_corners, _ptr(counts), _ptr(scratch), scratch.numel(),
+                                                   _stream(dev)))
+            R, V, status = (int(v) for v in counts.cpu().numpy())
+            if not status & 4 or attempt == 1:
+                break
+            if V >= 2 ** 31:
+                raise StcdError(f"object_rings: the scene has {V} ring vertices: corner ids are int32")
+            max_corners = V
+        if status:
+            raise StcdError(f"object_rings: the count phase reports status {status} (bit 1 / 2: an iteration cap or an impossible link, "
+                            "bit 4: the corner capacity); this is a bug in the kernels, not a property of the labels")
+        vertices = torch.empty((V, 2), dtype=torch.int32, device=dev)
+        offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        obj = torch.empty(R, dtype=torch.int32, device=dev)
+        area2 = torch.empty(R, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_rings_write(_ptr(labels), H, W, connectivity, max_corners, R, V, _ptr(vertices), _ptr(offsets), _ptr(obj),
+                                               _ptr(area2), _ptr(scratch), scratch.numel(), _stream(dev)))
+    return Rings(vertices, offsets, obj, area2, R)
+
+
+def _host_array(x, dtype):
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype)
+
+
+def rings_to_geojson(rings, path=None, transform=None, properties: Optional[ObjectTable] = None) -> dict:
+    """A GeoJSON ``FeatureCollection`` (a dict; written to ``path`` if given) with one ``Polygon`` per object of ``rings``
+    (``object_rings``' result, or the same five fields as numpy arrays or CPU tensors): the outer ring first, then the object's
+    holes in stored order, every ring closed by repeating its first vertex, coordinates as ``[x, y]``.  Host side.
+
+    ``transform=(a, b, c, d, e, f)`` maps lattice coordinates to ``x' = a x + b y + c``, ``y' = d x + e y + f``, the usual affine
+    geotransform.  In output coordinates read with y pointing up, the stored travel order is RFC 7946's: exterior rings
+    counter-clockwise (positive signed area), holes clockwise.  A transform that mirrors (``a e - b d < 0``: the north-up case,
+    ``e < 0``) would turn every ring round, so its rings are listed in reverse travel order, the first vertex staying first: the
+    exterior is counter-clockwise with and without a transform.  ``properties``, an ``ObjectTable`` of the same
+    components, adds ``area``, ``bbox`` and, where present, ``overlap`` to each feature's ``label``.  An object with more than one
+    outer ring raises ``StcdError``: that happens only when the labels were made with connectivity 8 and the rings with 4.
+    The rings are exact pixel outlines; simplification (Douglas-Peucker) is out of scope."""
+    vertices = _host_array(rings.vertices, np.int64).reshape(-1, 2)
+    offsets = _host_array(rings.offsets, np.int64).reshape(-1)
+    obj = _host_array(rings.object, np.int64).reshape(-1)
+    area2 = _host_array(rings.area2, np.int64).reshape(-1)
+    R = int(rings.count)
+    if offsets.shape[0] != R + 1 or obj.shape[0] != R or area2.shape[0] != R or (R and int(offsets[-1]) != vertices.shape[0]):
+        raise StcdError("rings_to_geojson: the fields of `rings` do not fit together")
+    mirrored = False
+    if transform is not None:
+        a, b, c, d, e, f = (float(v) for v in transform)
+        mirrored = a * e - b * d < 0
+    table = None
+    if properties is not None:
+        table = (_host_array(properties.area, np.int64), _host_array(properties.bbox, np.int64),
+                 None if properties.overlap is None else _host_array(properties.overlap, np.int64))
+    polygons = {}                                               # label -> [outer ring or None, holes], in order of first appearance
+    for r in range(R):
+        ring = vertices[offsets[r]:offsets[r + 1]]
+        ys, xs = ring[:, 0].tolist(), ring[:, 1].tolist()
+        if transform is None:
+            coords = [[x, y] for x, y in zip(xs, ys)]
+        else:
+            coords = [[a * x + b * y + c, d * x + e * y + f] for x, y in zip(xs, ys)]
+        if mirrored:
+            coords = coords[:1] + coords[:0:-1]
+        coords.append(list(coords[0]))
+        entry = polygons.setdefault(int(obj[r]), [None, []])
+        if area2[r] > 0:
+            if entry[0] is not None:
+                raise StcdError(f"rings_to_geojson: object {int(obj[r])} has more than one outer ring: the labels and the rings' connectivity disagree")
+            entry[0] = coords
+        else:
+            entry[1].append(coords)
+    features = []
+    for label in sorted(polygons):
+        outer, holes = polygons[label]
+        if outer is None:
+            raise StcdError(f"rings_to_geojson: object {label} has holes and no outer ring")
+        props = {"label": label}
+        if table is not None:
+            if not 1 <= label <= table[0].shape[0]:
+                raise StcdError(f"rings_to_geojson: `properties` has no row for object {label}")
+            props["area"] = int(table[0][label - 1])
+            props["bbox"] = [int(v) for v in table[1][label - 1]]
+            if table[2] is not None:
+                props["overlap"] = [int(v) for v in table[2][label - 1]]
+        features.append({"type": "Feature", "properties": props, "geometry": {"type": "Polygon", "coordinates": [outer] + holes}})
+    collection = {"type": "FeatureCollection", "features": features}
+    if path is not None:
+        with open(path, "w") as fh:
+            json.dump(collection, fh)
+    return collection
 
 
 def score_tables(pred_overlap: np.ndarray, label_overlap: np.ndarray, min_overlap: float = 0.5):
