@@ -255,7 +255,13 @@ int stcd_grad_stage_range(const stcd_engine* e, int stage, int64_t* begin, int64
  *      producer gathers it) instead of in place into the producer's gradient tensor, so ".dIn" survives the backward.
  *      SNUNet: the bit adds copies of the two values its backward overwrites, in buffers of their own at the end of the
  *      workspace -- "convL_J.dOut", the gathered output gradient before bn2's backward runs in place on it, and "ecam.dIn" /
- *      "head.dIn", the head's data gradient before conv0_1..conv0_4 gather into it; without the bit neither exists. */
+ *      "head.dIn", the head's data gradient before conv0_1..conv0_4 gather into it; without the bit neither exists.
+ *      stcd_set_debug bit 1 (value 2; FC-Siam family, for tests and A/B runs): the step's entry work goes out as the separate
+ *      launches it was before they were merged -- dropout masks, weight pack, arena memset and input pack in front of the forward
+ *      (otherwise one k_step_prologue launch), the memset of the gradient buffer in front of the backward (otherwise extra blocks
+ *      of the k_gout_pack launch), and ONE slab-reduce launch for all of stage 1's weight gradients behind the last of them, on the
+ *      side stream (otherwise the reduce of the groups that go out early follows them there, and the last group and its reduce run
+ *      on the caller's stream).  Same workspace layout, same bits in every result. */
 typedef struct stcd_ws_tensor {
     char name[96];
     int64_t offset_bytes;
@@ -263,6 +269,14 @@ typedef struct stcd_ws_tensor {
     int dtype;
 } stcd_ws_tensor;
 int stcd_set_debug(stcd_engine* e, int flags);
+/* Test introspection of the step's entry and tail, as the last stcd_configure planned them and the last backward ran them:
+ *   entry_fused        1: the forward opens with one k_step_prologue launch and the backward's k_gout_pack clears the gradient buffer
+ *                      (FC-Siam family without stcd_set_debug bit 1); 0: separate launches
+ *   reduce_early_jobs, reduce_final_jobs   slab-reduce jobs of backward stage 1 that are summed behind the groups that go out early /
+ *                      behind the final group; both 0: one reduce launch for the stage (debug bit 1, other families, no MFMA plan)
+ *   last_tail          the last backward's stage-1 tail: bit 0 the early part went out behind its groups, bit 1 the final group and its
+ *                      reduce ran on the caller's stream (single-call backward with the side stream); 0 before any backward */
+int stcd_seam_plan(const stcd_engine* e, int* entry_fused, int* reduce_early_jobs, int* reduce_final_jobs, int* last_tail);
 int stcd_ws_tensor_count(const stcd_engine* e);
 int stcd_ws_tensor_get(const stcd_engine* e, int index, stcd_ws_tensor* out);
 

@@ -132,6 +132,7 @@ _PROTOS = {
     "stcd_grad_stage_range": (_i, [_vp, _i, C.POINTER(_i64), C.POINTER(_i64)]),
     "stcd_set_weights_tag": (_i, [_vp, C.c_uint64]),
     "stcd_set_debug": (_i, [_vp, _i]),
+    "stcd_seam_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "stcd_ws_tensor_count": (_i, [_vp]),
     "stcd_ws_tensor_get": (_i, [_vp, _i, C.POINTER(WsTensor)]),
     "stcd_profile_enable": (_i, [_vp, _i]),

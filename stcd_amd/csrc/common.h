@@ -97,6 +97,53 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// ------------------------------------------------------------------ bodies shared by a launch of their own and k_step_prologue
+// element i of the dropout masks from a counter hash: (u(seed, i) >= p) / (1 - p)
+__device__ __forceinline__ void dropout_gen_body(float* __restrict__ mask, int64_t i, int64_t n, uint64_t seed, float p) {
+    if (i >= n) return;
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);   // splitmix64
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    float u = (float)(z >> 40) * (1.0f / 16777216.0f);
+    mask[i] = u >= p ? 1.0f / (1.0f - p) : 0.f;
+}
+// pixel i of the packed input X [images][H][W][8] from the fp32 NCHW pair
+template <typename T>
+__device__ __forceinline__ void in_pack_body(const float* __restrict__ x1, const float* __restrict__ x2, T* __restrict__ X, int B, int cin,
+                                             int64_t HW, int64_t total, int concat, int64_t i) {
+    if (i >= total) return;
+    int n = (int)(i / HW);
+    int64_t p = i - (int64_t)n * HW;
+    float v[8];
+    if (concat) {       // image n = cat(x1[n], x2[n]) along the channels (FC-EF, Unet.py:94)
+        const float* s1 = x1 + (int64_t)n * cin * HW + p;
+        const float* s2 = x2 + (int64_t)n * cin * HW + p;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = c < cin ? s1[(int64_t)c * HW] : c < 2 * cin ? s2[(int64_t)(c - cin) * HW] : 0.f;
+    } else {
+        const float* src = (n < B ? x1 + (int64_t)n * cin * HW : x2 + (int64_t)(n - B) * cin * HW) + p;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) v[c] = c < cin ? src[(int64_t)c * HW] : 0.f;
+    }
+    store8<T>(X + i * 8, v);
+}
+// Zero-fill as extra blocks of another launch: block b (256 threads) of zero_fill_blocks(bytes) clears its ZERO_BLOCK_BYTES of
+// [p, p + bytes) with 16-byte stores.  p is 16-byte aligned and bytes a multiple of 4 (zero_fill_ok); the words behind the last
+// full 16 bytes go out as 4-byte stores.
+constexpr int64_t ZERO_BLOCK_BYTES = 256 * 16 * 8;
+inline bool zero_fill_ok(const void* p, int64_t bytes) { return ((uintptr_t)p & 15) == 0 && bytes % 4 == 0; }
+inline int64_t zero_fill_blocks(int64_t bytes) { return bytes > 0 ? (bytes + ZERO_BLOCK_BYTES - 1) / ZERO_BLOCK_BYTES : 0; }
+__device__ __forceinline__ void zero_fill_body(char* __restrict__ p, int64_t bytes, int64_t b) {
+    const int64_t lo = b * ZERO_BLOCK_BYTES;
+    const int64_t hi = bytes < lo + ZERO_BLOCK_BYTES ? bytes : lo + ZERO_BLOCK_BYTES;
+    for (int64_t o = lo + (int64_t)threadIdx.x * 16; o < hi; o += 256 * 16) {
+        if (o + 16 <= hi) *reinterpret_cast<uint4*>(p + o) = make_uint4(0u, 0u, 0u, 0u);
+        else
+            for (int64_t q = o; q < hi; q += 4) *reinterpret_cast<uint32_t*>(p + q) = 0u;
+    }
+}
+
 // ------------------------------------------------------------------ BatchNorm sum accumulators
 // Per-channel sums (forward: sum y, sum y^2; backward: sum dz, sum dz*xhat) meet in 64-bit FIXED-POINT integer
 // accumulators through global atomic adds: integer addition is exact and order-independent, so the result is
@@ -236,8 +283,11 @@ __device__ __forceinline__ void xf_fold8(const float* __restrict__ tab_sc, const
 
 // x1,x2 fp32 NCHW [B,cin,H,W] -> X [2B,H,W,8] (channels >= cin zero)
 void launch_in_pack(int dt, const float* x1, const float* x2, void* X, int B, int cin, int H, int W, hipStream_t s, int dates = 2);
-// g fp32 NCHW [B,L,H,W] -> G [B,H,W,8]; optional bias_acc (int64 [BN_REP][1][2][8], scale BN_BS): per-channel sums of g
-void launch_gout_pack(int dt, const float* g, void* G, int B, int L, int H, int W, hipStream_t s, long long* bias_acc = nullptr);
+// g fp32 NCHW [B,L,H,W] -> G [B,H,W,8]; optional bias_acc (int64 [BN_REP][1][2][8], scale BN_BS): per-channel sums of g;
+// optional zero_p: [zero_p, zero_p + zero_bytes) is cleared by extra blocks of the same launch (the backward's gradient buffer).
+// -> 1 and nothing launched when zero_fill_ok(zero_p, zero_bytes) does not hold or the grid would not fit; 0 otherwise
+int launch_gout_pack(int dt, const float* g, void* G, int B, int L, int H, int W, hipStream_t s, long long* bias_acc = nullptr,
+                     void* zero_p = nullptr, int64_t zero_bytes = 0);
 // bias gradients that conv / pack kernels accumulated as integer sums -> fp32 gradient entries (one launch per stage)
 struct BiasJob { int64_t acc_off; int64_t out_off; int C, valid; float scale; int pad_; };
 void launch_bias_finish(const BiasJob* jobs_dev, int njobs, const char* ws, float* grads, hipStream_t s);
@@ -453,6 +503,27 @@ struct PackJob {
     int aux;                  // kind 2 (7x7 stem as a 7-tap GEMM over 8-pixel rows): real input channels
 };
 void launch_pack_jobs(const PackJob* jobs_dev, int njobs, int64_t total, const float* params, char* ws, hipStream_t s);
+// bytes of the image a job writes at dst_off, per kind as pack_jobs_body writes it (-1: a kind this function does not know -- a new
+// kind is added HERE with its body): 0 fp32 [tap][kpad][wld]; 1 bf16 fragments, one thread per element (mode B) or per (ci, co) for all
+// taps (mode A); 2 bf16 fragments of the 7-tap stem
+inline int64_t pack_job_bytes(const PackJob& j) {
+    switch (j.kind) {
+        case 0: return j.count * 4;
+        case 1: return (j.modeB ? j.count : j.count * j.ps.ntaps) * 2;
+        case 2: return j.count * 2;
+        default: return -1;
+    }
+}
+// k_step_prologue (kernels_conv_mfma.hip): dropout masks, filter pack, arena zero-fill and input pack of a step in one launch.
+// The caller fills the four parts (a part it leaves at zero size is skipped); the launcher sets the block boundaries.
+struct StepPrologue {
+    float* mask; int64_t drop_n; uint64_t seed; float p;                                   // as launch_dropout_gen
+    const PackJob* jobs; int njobs; int64_t pack_total; const float* params; char* ws;     // as launch_pack_jobs
+    char* zero_p; int64_t zero_bytes;                                                      // zero_fill_ok(zero_p, zero_bytes)
+    const float* x1; const float* x2; void* X; int B, cin; int64_t HW, in_total; int concat;   // as k_in_pack
+    int drop_end, pack_end, zero_end;                                                      // first block behind each of the first three parts
+};
+int launch_step_prologue(int dt, StepPrologue a, hipStream_t s);      // -> 1 and nothing launched: the grid does not fit 2^31 - 1 blocks
 
 // batch-norm (train): per-(group, channel) sums of y and y^2 over a group's pixels, added into acc (see BN accumulators)
 int bn_stats_chunks(int64_t pixels_per_group, int C);

@@ -280,6 +280,15 @@ struct stcd_engine_impl {
     std::vector<WgradGroup> wgroups[2];                 // per backward stage: grouped weight-gradient launches
     std::vector<ReduceJob> rjobs[2];                    // per backward stage
     int64_t rjobs_total[2] = {0, 0}, rjobs_off[2] = {-1, -1};
+    // FC-Siam, stage 1: the reduce table is split by weight-gradient group.  Jobs [0, rj_split) belong to the groups that go out
+    // before the stage's last one (wg_final_group: the group of wg_last_op, conv11's weight gradient, the backward's last launch)
+    // and are reduced right behind the last of them; jobs [rj_split, n) are the final group's, reduced on the tail.  Each part's
+    // `start`s count from 0.  rj_split == 0: one launch on the tail for the whole table.
+    const WgradOp* wg_last_op = nullptr;
+    int rj_split = 0, wg_final_group = -1;
+    int64_t rj_total_early = 0, rj_total_final = 0;
+    bool rj_early_done = false, wg_final_on_main = false;      // run time, per backward
+    int last_tail = 0;      // what the last stage-1 tail found: bit 0 the early part was reduced behind its groups, bit 1 the final group ran on the caller's stream
     // batched filter repacking: [0] = forward-only job list (eval), [1] = forward + data-gradient filters (training)
     std::vector<PackJob> jobs[2];
     int64_t jobs_total[2] = {0, 0}, jobs_off[2] = {-1, -1};
@@ -757,6 +766,7 @@ static void build_pack_jobs(stcd_engine& e, Planner& ws) {
     // ---- per-launch slab regions + the batched reduce job tables (MFMA path only)
     for (int st = 0; st < 2; ++st) { e.rjobs[st].clear(); e.rjobs_total[st] = 0; }
     for (int st = 0; st < 2; ++st) e.wgroups[st].clear();
+    e.rj_split = 0; e.wg_final_group = -1; e.rj_early_done = false; e.wg_final_on_main = false;
     if (e.dt == BF16 && e.use_mfma) {
         // ---- grouped weight-gradient launches: one grid per (stage, kernel variant).  The K split (gx) of every layer is
         //      chosen for the GROUP: about two resident rounds of blocks over all its layers, each block owning at least
@@ -838,6 +848,7 @@ static void build_pack_jobs(stcd_engine& e, Planner& ws) {
                 }
         }
         int64_t cur[2] = {0, 0};
+        std::vector<int> rj_group1;      // stage 1: the group of every reduce job's launch (-1: a launch of its own)
         for (WgradOp* op : e.wgrad_ops) {
             if (!op->plan.ok) continue;
             const ConvW& cv = e.convs[op->conv];
@@ -884,6 +895,28 @@ static void build_pack_jobs(stcd_engine& e, Planner& ws) {
             j.start = cur[op->stage];
             cur[op->stage] += (j.count + 255) & ~(int64_t)255;     // block-aligned: one job per block
             e.rjobs[op->stage].push_back(j);
+            if (op->stage == 1) rj_group1.push_back(op->grouped ? op->group : -1);
+        }
+        // stage 1's table by group: the final group's jobs last, each part counting from 0 (the order of summation of every output is
+        // its job's own; the split only partitions jobs across launches).  stcd_set_debug bit 1: one table, one launch on the tail.
+        e.rj_split = 0; e.wg_final_group = -1; e.rj_total_early = e.rj_total_final = 0;
+        if (e.wg_last_op && e.wg_last_op->plan.ok && e.wg_last_op->grouped && e.wg_last_op->stage == 1 && !(e.debug_flags & 2)) {
+            const int gf = e.wg_last_op->group;
+            std::vector<ReduceJob> part[2];
+            bool all_grouped = true;
+            for (size_t i = 0; i < e.rjobs[1].size(); ++i) {
+                all_grouped = all_grouped && rj_group1[i] >= 0;
+                part[rj_group1[i] == gf ? 1 : 0].push_back(e.rjobs[1][i]);
+            }
+            if (all_grouped && !part[0].empty() && !part[1].empty()) {
+                int64_t tot[2] = {0, 0};
+                for (int k = 0; k < 2; ++k)
+                    for (ReduceJob& j : part[k]) { j.start = tot[k]; tot[k] += (j.count + 255) & ~(int64_t)255; }
+                e.rjobs[1] = part[0];
+                e.rjobs[1].insert(e.rjobs[1].end(), part[1].begin(), part[1].end());
+                e.rj_split = (int)part[0].size(); e.wg_final_group = gf;
+                e.rj_total_early = tot[0]; e.rj_total_final = tot[1];
+            }
         }
         for (int st = 0; st < 2; ++st) {
             e.rjobs_total[st] = cur[st];
@@ -1253,7 +1286,29 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
         rec_layer(R);
     }
 
+    e.wg_last_op = &e.enc[0].wg;      // conv11's weight gradient: the last launch the backward chain makes ready
     ws.tables();
+    // k_step_prologue writes the masks, the filter images, the zero range and the packed input from one grid, in no order: the four
+    // outputs must not overlap (byte ranges of the workspace)
+    {
+        struct Rng { int64_t a, b; const char* what; };
+        std::vector<Rng> out;
+        out.push_back({e.X0.off, e.X0.off + (int64_t)ND * B * H * W * 8 * T, "packed input"});
+        out.push_back({e.zero_begin, e.zero_end, "zero range"});
+        if (e.drop_floats > 0) out.push_back({e.masks, e.masks + e.drop_floats * 4, "dropout masks"});
+        const size_t fixed = out.size();
+        for (const PackJob& j : e.jobs[1]) {
+            const int64_t bytes = pack_job_bytes(j);
+            if (bytes < 0) { set_error("internal: a filter pack job of a kind pack_job_bytes does not size"); return 1; }
+            out.push_back({j.dst_off, j.dst_off + bytes, "filter image"});
+        }
+        for (size_t i = 0; i < fixed; ++i)
+            for (size_t k = i + 1; k < out.size(); ++k)
+                if (out[i].a < out[k].b && out[k].a < out[i].b) {
+                    set_error(std::string("internal: the step prologue's outputs overlap (") + out[i].what + " / " + out[k].what + ")");
+                    return 1;
+                }
+    }
     return 0;
 }
 
@@ -1497,8 +1552,11 @@ static void exec_wgrad(const Ctx& c, const WgradOp& op, const void* in, const vo
     launch_unpack_dw(sub, dwe, c.grads + cv.w_off, c.s);
 }
 
-static int pack_all_weights(const Ctx& c, bool with_dgrad) {
+// what comes before the pack launch: uploads the job tables on first use of a workspace, then says whether the filter images must be
+// (re)packed -- and books them as packed, so the caller launches the pack (on its own or inside k_step_prologue) when *need is set
+static int pack_prepare(const Ctx& c, bool with_dgrad, bool* need) {
     stcd_engine& e = c.e;
+    *need = false;
     if (e.jobs_uploaded_ws != (const void*)c.ws) {      // first use of this workspace: upload both job tables
         for (int k = 0; k < 2; ++k) {
             if (!e.jobs[k].empty())
@@ -1520,9 +1578,18 @@ static int pack_all_weights(const Ctx& c, bool with_dgrad) {
     // Training forwards always repack and never vouch for the next call (an optimizer step follows them).
     if (k == 0 && e.weights_tag != 0 && e.weights_tag == e.packed_tag && e.packed_ws == (const void*)c.ws && e.packed_params == (const void*)c.params)
         return 0;
+    e.packed_tag = k == 0 ? e.weights_tag : 0; e.packed_ws = c.ws; e.packed_params = c.params; e.packed_level = k;
+    *need = true;
+    return 0;
+}
+static int pack_all_weights(const Ctx& c, bool with_dgrad) {
+    stcd_engine& e = c.e;
+    bool need = false;
+    if (pack_prepare(c, with_dgrad, &need)) return 1;
+    if (!need) return 0;
+    const int k = with_dgrad ? 1 : 0;
     ProfScope prof(c, PC_PACK, 0.0, 0.0);
     launch_pack_jobs(c.at<PackJob>(e.jobs_off[k]), (int)e.jobs[k].size(), e.jobs_total[k], c.params, c.ws, c.s);
-    e.packed_tag = k == 0 ? e.weights_tag : 0; e.packed_ws = c.ws; e.packed_params = c.params; e.packed_level = k;
     return 0;
 }
 
@@ -1551,17 +1618,35 @@ static void launch_wgroup(const Ctx& c, WgradGroup& G) {
 // FC-Siam backward with early launches (e.wg_early): a member's operands (X stored by the forward, dY final) exist when the chain
 // calls exec_wgrad for it; the group's grid goes out with its LAST member -- on the side stream, behind an event of the chain's
 // stream, when there is one -- instead of at the end of the stage
+// stage 1 with a split reduce table: once every group but the final one has gone out, their slabs are summed right behind them (on the
+// stream they went out on), under the chain's last kernels instead of on the tail
+static void reduce_early_if_due(const Ctx& c) {
+    stcd_engine& e = c.e;
+    if (e.rj_split <= 0 || e.rj_early_done) return;
+    if (e.prof.on) return;      // instrumented steps run serially on one stream: both parts go out on the tail, timed as one record
+    for (size_t g = 0; g < e.wgroups[1].size(); ++g)
+        if ((int)g != e.wg_final_group && !e.wgroups[1][g].launched) return;
+    launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]), e.rj_split, e.rj_total_early, c.ws, c.grads, c.s);
+    e.rj_early_done = true;
+}
 static void wgroup_member_ready(const Ctx& c, const WgradOp& op) {
     stcd_engine& e = c.e;
     if (op.group < 0 || op.group >= (int)e.wgroups[op.stage].size()) return;
     WgradGroup& G = e.wgroups[op.stage][op.group];
     if (++G.seen < (int)G.jobs.size() || G.launched) return;
-    if (e.wg_cur_side) {
+    // stage 1's final group (conv11, conv12) becomes ready when the chain has nothing left to run beside it: it goes out on the
+    // caller's stream, and its slab reduce and the optimizer behind it need no cross-stream hand-off (stage_tail; measured in
+    // DESIGN.md section 4, "Step seams")
+    const bool final_group = op.stage == 1 && e.rj_split > 0 && op.group == e.wg_final_group;
+    if (e.wg_cur_side && !final_group) {
         if (hipEventRecord(e.wg_fork, c.s) != hipSuccess || hipStreamWaitEvent(e.wg_cur_side, e.wg_fork, 0) != hipSuccess) { set_error("side-stream fork failed"); return; }
         Ctx cs{e, c.ws, c.params, c.grads, e.wg_cur_side};
         launch_wgroup(cs, G);
+        if (op.stage == 1) reduce_early_if_due(cs);
     } else {
         launch_wgroup(c, G);
+        if (final_group && e.wg_cur_side) e.wg_final_on_main = true;
+        else if (op.stage == 1) reduce_early_if_due(c);
     }
 }
 
@@ -1573,6 +1658,14 @@ static void reduce_stage(const Ctx& c, int stage) {
         G.launched = false; G.seen = 0;
     }
     if (e.rjobs[stage].empty()) return;
+    if (stage == 1 && e.rj_split > 0) {      // split table: whatever of the early part is still open, then the final group's jobs
+        ProfScope prof(c, PC_PACK, 0.0, 0.0, "k_reduce_jobs");
+        if (!e.rj_early_done) launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]), e.rj_split, e.rj_total_early, c.ws, c.grads, c.s);
+        e.last_tail = (e.rj_early_done ? 1 : 0) | (e.wg_final_on_main ? 2 : 0);      // (stcd_seam_plan)
+        e.rj_early_done = false; e.wg_final_on_main = false;
+        launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]) + e.rj_split, (int)e.rjobs[1].size() - e.rj_split, e.rj_total_final, c.ws, c.grads, c.s);
+        return;
+    }
     ProfScope prof(c, PC_PACK, 0.0, 0.0, "k_reduce_jobs");
     launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[stage]), (int)e.rjobs[stage].size(), e.rjobs_total[stage], c.ws, c.grads, c.s);
 }
@@ -1754,17 +1847,50 @@ static int forward_fcsiam(stcd_engine& e, const float* x1, const float* x2, cons
     Ctx c{e, (char*)workspace, params, nullptr, s};
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt);
+    // ---- the step's entry: dropout masks, filter images, the zero arena, the packed input.  They write disjoint buffers
+    //      (configure_fcsiam checks it) and read only the caller's tensors: ONE launch (k_step_prologue) with a block range each;
+    //      stcd_set_debug bit 1: the four launches they were.  Explicit masks are copied in either way.
+    float gen_p = -1.f;                                  // >= 0: masks from the counter hash with this p
     if (training && e.drop_p > 0.f) {
         if (masks) STCD_HIP(hipMemcpyAsync(c.at(e.masks), masks, e.drop_floats * 4, hipMemcpyDeviceToDevice, s));
-        else launch_dropout_gen(c.at<float>(e.masks), e.drop_floats, seed, e.drop_p, s);
+        else gen_p = e.drop_p;
     } else if (training && e.fc_virt_layers > 0) {
         // p == 0 with virtual activations: the weight-gradient job table addresses the mask buffer unconditionally (it is built at
         // configure time), so the buffer must read as all ones (k_dropout_gen with p = 0 writes 1 / (1 - 0) everywhere)
-        launch_dropout_gen(c.at<float>(e.masks), e.drop_floats, seed, 0.f, s);
+        gen_p = 0.f;
     }
-    if (pack_all_weights(c, training != 0)) return 1;
-    if (training) STCD_HIP(hipMemsetAsync(c.at(e.zero_begin), 0, e.zero_end - e.zero_begin, s));   // the step's ONE workspace memset
-    launch_in_pack(dt, x1, x2, c.at(e.X0.off), B, e.in_ch, e.H, e.W, s, e.arch == STCD_ARCH_FCEF ? 0 : 2);      // 0: cat(x1, x2) along the channels
+    const int in_dates = e.arch == STCD_ARCH_FCEF ? 0 : 2;      // 0: cat(x1, x2) along the channels
+    if (e.debug_flags & 2) {
+        if (gen_p >= 0.f) launch_dropout_gen(c.at<float>(e.masks), e.drop_floats, seed, gen_p, s);
+        if (pack_all_weights(c, training != 0)) return 1;
+        if (training) STCD_HIP(hipMemsetAsync(c.at(e.zero_begin), 0, e.zero_end - e.zero_begin, s));   // the step's ONE workspace memset
+        launch_in_pack(dt, x1, x2, c.at(e.X0.off), B, e.in_ch, e.H, e.W, s, in_dates);
+    } else {
+        StepPrologue a{};
+        if (gen_p >= 0.f) { a.mask = c.at<float>(e.masks); a.drop_n = e.drop_floats; a.seed = seed; a.p = gen_p; }
+        bool need_pack = false;
+        if (pack_prepare(c, training != 0, &need_pack)) return 1;
+        if (need_pack) {
+            const int k = training ? 1 : 0;
+            a.jobs = c.at<PackJob>(e.jobs_off[k]); a.njobs = (int)e.jobs[k].size(); a.pack_total = e.jobs_total[k];
+            a.params = params; a.ws = c.ws;
+        }
+        if (training) {
+            if (zero_fill_ok(c.at(e.zero_begin), e.zero_end - e.zero_begin)) { a.zero_p = c.at<char>(e.zero_begin); a.zero_bytes = e.zero_end - e.zero_begin; }
+            else STCD_HIP(hipMemsetAsync(c.at(e.zero_begin), 0, e.zero_end - e.zero_begin, s));      // (a workspace the 16-byte stores cannot take)
+        }
+        a.x1 = x1; a.x2 = x2; a.X = c.at(e.X0.off); a.B = B; a.cin = e.in_ch; a.HW = (int64_t)e.H * e.W;
+        a.concat = in_dates == 0 ? 1 : 0;
+        a.in_total = (int64_t)(a.concat ? 1 : in_dates) * B * a.HW;
+        int rc;
+        if (need_pack) {      // instrumented steps: the launch stands where the pack launch stood, in its class and under its name
+            ProfScope prof(c, PC_PACK, 0.0, 0.0);
+            rc = launch_step_prologue(dt, a, s);
+        } else {
+            rc = launch_step_prologue(dt, a, s);
+        }
+        STCD_CHECK(rc == 0, "the step prologue's grid exceeds 2^31 - 1 blocks");
+    }
     for (auto& L : e.enc) cbrd_forward(c, L, bn_running, training != 0);
     size_t di = 0;
     for (int k = 0; k < 4; ++k) {
@@ -1832,6 +1958,15 @@ template <typename Extra>
 static int stage_tail(const Ctx& c, int stage, hipStream_t side, bool wait_join, Extra extra) {
     stcd_engine& e = c.e;
     if (!side) { reduce_stage(c, stage); extra(c); return 0; }
+    if (stage == 1 && e.wg_final_on_main && e.rj_early_done) {
+        // the stage's final group went out on the caller's stream, and everything the side stream holds went out long ago (the earlier
+        // stage's tail, the early groups, their reduce): join it first, then the final group's reduce follows that group on this stream
+        STCD_HIP(hipEventRecord(e.wg_join, side));
+        STCD_HIP(hipStreamWaitEvent(c.s, e.wg_join, 0));
+        reduce_stage(c, stage);
+        extra(c);
+        return 0;
+    }
     STCD_HIP(hipEventRecord(e.wg_fork, c.s));
     STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
     Ctx cs{e, c.ws, c.params, c.grads, side};
@@ -1858,14 +1993,23 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
     for (int st = 0; st < 2; ++st)
         if (stage < 0 || stage == st)
             for (WgradGroup& G : e.wgroups[st]) { G.seen = 0; G.launched = false; }      // (a failed call may have left them set)
+    if (stage != 0) { e.rj_early_done = false; e.wg_final_on_main = false; e.last_tail = 0; }
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt);
     if (stage <= 0) {
-        STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
+        // the gradient buffer is cleared by extra blocks of the pack launch (every writer of it follows in stream order; the zeros
+        // stay in the biases in front of a train-mode BatchNorm); stcd_set_debug bit 1: by a memset of its own, as it was
+        // (or the caller's buffer is one the 16-byte stores cannot take)
+        const bool sep = (e.debug_flags & 2) != 0 || !zero_fill_ok(grads, e.param_floats * 4);
+        if (sep) STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
         if (!mfma_on(e)) STCD_HIP(hipMemsetAsync(c.at(e.dwe_begin), 0, e.dwe_end - e.dwe_begin, s));
         // (the date-0 half of dP[3] and every accumulator were zeroed by the forward's arena memset)
         // conv11d: its bias gradient = per-channel sum of d(logits), formed while the gradient is packed
-        launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
+        if (launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc),
+                             sep ? nullptr : grads, e.param_floats * 4)) {
+            set_error("internal: k_gout_pack rejected the gradient buffer's zero-fill");
+            return 1;
+        }
         exec_wgrad(c, e.final_wg, c.at(e.finalIn.off), c.at(e.G.off));
         {
             BwdSum bs;
@@ -3121,7 +3265,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
 static void reset_plan(stcd_engine& e) {
     e.enc.clear(); e.dec.clear(); e.ups.clear();
     e.drops.clear(); e.drop_floats = 0;
-    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0;
+    e.conv_ops.clear(); e.wgrad_ops.clear(); e.slab_floats = 0; e.wg_last_op = nullptr;
     e.ws_tensors.clear(); e.bias_jobs.clear();
     e.g_fwd.clear(); e.sn_order.clear();
     if (e.cf) cf_reset_plan(*e.cf);
@@ -3379,6 +3523,15 @@ int stcd_set_debug(stcd_engine* e, int flags) {
     STCD_CHECK(e != nullptr, "engine is null");
     e->debug_flags = flags;
     e->configured = false;      // takes effect at the next stcd_configure
+    return 0;
+}
+int stcd_seam_plan(const stcd_engine* e, int* entry_fused, int* reduce_early_jobs, int* reduce_final_jobs, int* last_tail) {
+    STCD_CHECK(e && entry_fused && reduce_early_jobs && reduce_final_jobs && last_tail, "null argument");
+    STCD_CHECK(e->configured, "stcd_configure first");
+    *entry_fused = (fc_family(*e) && !(e->debug_flags & 2)) ? 1 : 0;
+    *reduce_early_jobs = e->rj_split;
+    *reduce_final_jobs = e->rj_split > 0 ? (int)e->rjobs[1].size() - e->rj_split : 0;
+    *last_tail = e->last_tail;
     return 0;
 }
 int stcd_ws_tensor_count(const stcd_engine* e) { return e ? (int)e->ws_tensors.size() : 0; }

@@ -321,9 +321,10 @@ __device__ __forceinline__ float ref_weight(const PackSpec& ps, const float* src
     return src[(a_ * ps.ks + ps.ky[t]) * ps.ks + ps.kx[t]];
 }
 
-__global__ void __launch_bounds__(256)
-k_pack_jobs(const PackJob* __restrict__ jobs, int njobs, int64_t total, const float* __restrict__ params, char* __restrict__ ws) {
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x, i = i0 + threadIdx.x;
+// block `blk` (256 threads) of the pack launch's element index space
+__device__ __forceinline__ void pack_jobs_body(const PackJob* __restrict__ jobs, int njobs, const float* __restrict__ params,
+                                               char* __restrict__ ws, int64_t blk) {
+    const int64_t i0 = blk * 256, i = i0 + threadIdx.x;
     int lo = 0, hi = njobs - 1;            // last job with start <= i0: jobs start on 256-element boundaries, so the
     while (lo < hi) {                      // whole block shares it (uniform search: scalar loads)
         const int mid = (lo + hi + 1) >> 1;
@@ -383,8 +384,40 @@ k_pack_jobs(const PackJob* __restrict__ jobs, int njobs, int64_t total, const fl
         reinterpret_cast<bf16*>(ws + jb.dst_off)[e] = (bf16)v;
     }
 }
+__global__ void __launch_bounds__(256)
+k_pack_jobs(const PackJob* __restrict__ jobs, int njobs, int64_t total, const float* __restrict__ params, char* __restrict__ ws) {
+    pack_jobs_body(jobs, njobs, params, ws, (int64_t)blockIdx.x);
+}
 void launch_pack_jobs(const PackJob* jobs_dev, int njobs, int64_t total, const float* params, char* ws, hipStream_t s) {
     if (njobs > 0 && total > 0) k_pack_jobs<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(jobs_dev, njobs, total, params, ws);
+}
+
+// The entry of an FC-Siam step as ONE launch.  Its four parts write disjoint buffers and read only what the caller hands in, so none
+// depends on another: the grid is cut into four block ranges by block-uniform boundaries (any range may be empty), and each block
+// runs the body of the launch it replaces -- dropout masks (k_dropout_gen), filter images (k_pack_jobs), the zero arena (16-byte
+// stores instead of a memset) and the packed input (k_in_pack).  Same functions, same element per thread: same bits.
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_step_prologue(StepPrologue a) {
+    const int b = (int)blockIdx.x;
+    if (b < a.drop_end) dropout_gen_body(a.mask, (int64_t)b * 256 + threadIdx.x, a.drop_n, a.seed, a.p);
+    else if (b < a.pack_end) pack_jobs_body(a.jobs, a.njobs, a.params, a.ws, (int64_t)(b - a.drop_end));
+    else if (b < a.zero_end) zero_fill_body(a.zero_p, a.zero_bytes, (int64_t)(b - a.pack_end));
+    else in_pack_body<T>(a.x1, a.x2, (T*)a.X, a.B, a.cin, a.HW, a.in_total, a.concat, (int64_t)(b - a.zero_end) * 256 + threadIdx.x);
+}
+int launch_step_prologue(int dt, StepPrologue a, hipStream_t s) {
+    if (a.drop_n <= 0 || !a.mask) a.drop_n = 0;
+    if (a.njobs <= 0 || a.pack_total <= 0) { a.njobs = 0; a.pack_total = 0; }
+    if (!a.zero_p || a.zero_bytes <= 0) a.zero_bytes = 0;
+    if (a.in_total < 0) a.in_total = 0;
+    const int64_t b0 = (a.drop_n + 255) / 256, b1 = b0 + (a.pack_total + 255) / 256, b2 = b1 + zero_fill_blocks(a.zero_bytes),
+                  grid = b2 + (a.in_total + 255) / 256;
+    if (grid > 0x7fffffff) return 1;      // (the block boundaries are ints)
+    a.drop_end = (int)b0; a.pack_end = (int)b1; a.zero_end = (int)b2;
+    if (grid <= 0) return 0;
+    if (dt == BF16) k_step_prologue<bf16><<<(unsigned)grid, 256, 0, s>>>(a);
+    else k_step_prologue<float><<<(unsigned)grid, 256, 0, s>>>(a);
+    return 0;
 }
 
 void launch_pack_frag(const stcd_conv_geom& g, const ConvMfmaPlan& p, const float* w, int kpad, int wld, void* dst,
@@ -805,6 +838,8 @@ k_reduce_dw(const float* __restrict__ slab, int gx, int64_t slab_stride, int nta
 // `parts` threads OF ONE BLOCK each sum a contiguous range of slabs (4 independent chains, fixed association) and thread 0 of the
 // output adds the parts in index order through LDS; tiled filters: one block walks all slabs of its tile.  Rounds 1-3 cut
 // many-slab jobs into parts of other blocks that met through float atomicAdd: two runs of one step differed by ~1e-6.
+// A launch takes any contiguous part of a stage's table whose `start`s count from 0 (the FC-Siam engine splits stage 1's table by
+// weight-gradient group): every output belongs to one job, so the split changes no sum.
 __global__ void __launch_bounds__(256)
 k_reduce_jobs(const ReduceJob* __restrict__ jobs, int njobs, int64_t total, const char* __restrict__ ws, float* __restrict__ grads) {
     __shared__ float tile[9 * 16 * 33];            // [tap][k][33] (ntaps > 1: TK = 16) or [32][33]; small filters: [parts][outs] partials

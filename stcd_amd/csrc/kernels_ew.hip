@@ -97,22 +97,7 @@ struct GV {
 template <typename T>
 __global__ void k_in_pack(const float* __restrict__ x1, const float* __restrict__ x2, T* __restrict__ X, int B, int cin,
                           int64_t HW, int64_t total, int concat) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int n = (int)(i / HW);
-    int64_t p = i - (int64_t)n * HW;
-    float v[8];
-    if (concat) {       // image n = cat(x1[n], x2[n]) along the channels (FC-EF, Unet.py:94)
-        const float* s1 = x1 + (int64_t)n * cin * HW + p;
-        const float* s2 = x2 + (int64_t)n * cin * HW + p;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = c < cin ? s1[(int64_t)c * HW] : c < 2 * cin ? s2[(int64_t)(c - cin) * HW] : 0.f;
-    } else {
-        const float* src = (n < B ? x1 + (int64_t)n * cin * HW : x2 + (int64_t)(n - B) * cin * HW) + p;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = c < cin ? src[(int64_t)c * HW] : 0.f;
-    }
-    store8<T>(X + i * 8, v);
+    in_pack_body<T>(x1, x2, X, B, cin, HW, total, concat, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // dates = 2: images [x1; x2] (2B of them); dates = 1: x1 alone (single-image networks: x2 is not read); dates = 0: B images of
@@ -124,10 +109,17 @@ void launch_in_pack(int dt, const float* x1, const float* x2, void* X, int B, in
     else k_in_pack<float><<<cdiv(n, 256), 256, 0, s>>>(x1, x2, (float*)X, B, cin, HW, n, concat);
 }
 
+// blocks [0, pack_blocks): g fp32 NCHW -> G [B,H,W,8] (+ the per-channel sums of g, keyed by the block index as before the zero blocks
+// existed); blocks behind them: zero-fill of [zero_p, zero_p + zero_bytes), the backward's gradient buffer, instead of a memset launch
 template <typename T>
 __global__ void __launch_bounds__(256)
-k_gout_pack(const float* __restrict__ g, T* __restrict__ G, int B, int L, int64_t HW, long long* __restrict__ bias_acc) {
+k_gout_pack(const float* __restrict__ g, T* __restrict__ G, int B, int L, int64_t HW, long long* __restrict__ bias_acc,
+            int pack_blocks, char* __restrict__ zero_p, int64_t zero_bytes) {
     __shared__ float red[4][8];
+    if ((int)blockIdx.x >= pack_blocks) {      // the blocks behind the pack's clear [zero_p, zero_p + zero_bytes): the backward's gradient buffer
+        zero_fill_body(zero_p, zero_bytes, (int64_t)blockIdx.x - pack_blocks);
+        return;
+    }
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float v[8];
 #pragma unroll
@@ -152,10 +144,17 @@ k_gout_pack(const float* __restrict__ g, T* __restrict__ G, int B, int L, int64_
     }
 }
 
-void launch_gout_pack(int dt, const float* g, void* G, int B, int L, int H, int W, hipStream_t s, long long* bias_acc) {
+int launch_gout_pack(int dt, const float* g, void* G, int B, int L, int H, int W, hipStream_t s, long long* bias_acc, void* zero_p,
+                     int64_t zero_bytes) {
     int64_t HW = (int64_t)H * W, n = (int64_t)B * HW;
-    if (dt == BF16) k_gout_pack<bf16><<<cdiv(n, 256), 256, 0, s>>>(g, (bf16*)G, B, L, HW, bias_acc);
-    else k_gout_pack<float><<<cdiv(n, 256), 256, 0, s>>>(g, (float*)G, B, L, HW, bias_acc);
+    if (!zero_p || zero_bytes <= 0) { zero_p = nullptr; zero_bytes = 0; }
+    else if (!zero_fill_ok(zero_p, zero_bytes)) return 1;      // (the caller clears such a buffer with a memset of its own)
+    const int64_t blocks = (n + 255) / 256 + zero_fill_blocks(zero_bytes);
+    if (blocks > 0x7fffffff) return 1;
+    const int pb = cdiv(n, 256), grid = (int)blocks;
+    if (dt == BF16) k_gout_pack<bf16><<<grid, 256, 0, s>>>(g, (bf16*)G, B, L, HW, bias_acc, pb, (char*)zero_p, zero_bytes);
+    else k_gout_pack<float><<<grid, 256, 0, s>>>(g, (float*)G, B, L, HW, bias_acc, pb, (char*)zero_p, zero_bytes);
+    return 0;
 }
 
 __global__ void k_bias_finish(const BiasJob* __restrict__ jobs, const char* __restrict__ ws, float* __restrict__ grads) {
@@ -1124,14 +1123,7 @@ void launch_bias_grad(int dt, const void* dY, int ld, int64_t pixels, int C, flo
 
 // ------------------------------------------------------------------ dropout masks, fill
 __global__ void k_dropout_gen(float* __restrict__ mask, int64_t n, uint64_t seed, float p) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);   // splitmix64
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    float u = (float)(z >> 40) * (1.0f / 16777216.0f);
-    mask[i] = u >= p ? 1.0f / (1.0f - p) : 0.f;
+    dropout_gen_body(mask, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, seed, p);
 }
 void launch_dropout_gen(float* mask, int64_t n, uint64_t seed, float p, hipStream_t s) {
     if (n > 0) k_dropout_gen<<<cdiv(n, 256), 256, 0, s>>>(mask, n, seed, p);

@@ -193,9 +193,16 @@ class Engine:
 
     # ------------------------------------------------------------------ test introspection
     def set_debug(self, flags: int):
-        """bit 0: every layer keeps its input gradient in a buffer of its own (see include/stcd_hip.h)."""
+        """bit 0: every layer keeps its input gradient in a buffer of its own; bit 1 (value 2): the step's entry work as the separate
+        launches it replaced (see include/stcd_hip.h)."""
         _lib.check(self._l.stcd_set_debug(self._h, int(flags)))
         self.shape = None
+
+    def seam_plan(self):
+        """-> (entry_fused, reduce_early_jobs, reduce_final_jobs, last_tail) of stcd_seam_plan (see include/stcd_hip.h)."""
+        v = [C.c_int() for _ in range(4)]
+        _lib.check(self._l.stcd_seam_plan(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def ws_tensors(self):
         """-> {name: NHWC view [n, h, w, c] of the live workspace} for the current configuration (the families include/stcd_hip.h lists)."""

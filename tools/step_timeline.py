@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Launch-by-launch timeline of one training step from a rocprofv3 --kernel-trace CSV directory:
     python3 tools/step_timeline.py <trace dir> [out.txt]
-Steps are delimited by k_in_pack (the step's first engine launch after the packing prologue); every position of the step takes the
+Steps are delimited by the step's first engine launch (k_step_prologue; k_dropout_gen or k_pack_jobs in older traces); every position of the step takes the
 MEDIAN duration over the steady-state steps (launch sequences of equal length), so one disturbed step does not show."""
 import csv, glob, re, sys
 
@@ -16,7 +16,8 @@ def short(n):
     return (m.group(1) if m else n)[:64]
 
 
-idx = [i for i, r in enumerate(rows) if 'k_dropout_gen' in r['Kernel_Name']] or [i for i, r in enumerate(rows) if 'k_pack_jobs' in r['Kernel_Name']]
+idx = ([i for i, r in enumerate(rows) if 'k_step_prologue' in r['Kernel_Name']] or [i for i, r in enumerate(rows) if 'k_dropout_gen' in r['Kernel_Name']]
+       or [i for i, r in enumerate(rows) if 'k_pack_jobs' in r['Kernel_Name']])
 steps = [rows[idx[k]:idx[k + 1]] for k in range(len(idx) - 1)]
 L = len(steps[-1])
 steps = [s for s in steps if len(s) == L][-5:]
