@@ -302,6 +302,70 @@ void launch_wgrad_ref(int dt, const stcd_conv_geom& g, const void* in, const voi
 void launch_wgrad_ref_f64(int dt, const stcd_conv_geom& g, const void* in, const void* dout, double* dw, int kpad, int wld,
                           hipStream_t s);
 
+// ---- one conv-shaped launch as its caller states it.  Every launch_conv_* below is (geometry, its plan(s), const ConvArgs&).
+// A request for per-channel sums of the launch's output, fused into the conv's epilogue: BatchNorm statistics of a forward
+// conv (all channels, sum and sum of squares) or the sum of a channel slice of a data gradient (a bias gradient).
+struct StatReq { long long* acc = nullptr; int groups = 1; int c0 = 0; int C = 0; float s1 = BN_FS1, s2 = BN_FS2; };
+struct ConvEpi;
+struct BwdSum;
+struct ConvArgs {
+    const void* in = nullptr;
+    const void* wf = nullptr;          // fragment-order filter image (exec_conv: the op's own)
+    const float* bias = nullptr;
+    void* out = nullptr;
+    bool nchw = false;                 // fp32 NCHW output (a network output)
+    int groups = 1;                    // tile groups of the launch (exec_conv: the plan's, or k_conv_small's own rule)
+    StatReq sums;                      // acc == nullptr: none
+    const ConvEpi* epi = nullptr;
+    const XfSrc* xf = nullptr;         // virtual-activation input (active when xf->on)
+    const BwdSum* bs = nullptr;
+    hipStream_t s = nullptr;
+    bool xf_on() const { return xf && xf->on; }
+    // BatchNorm statistics of all `co` channels at the forward scales (else: some slice, some scales)
+    bool bn_form(int co) const { return sums.c0 == 0 && sums.C == co && sums.s1 == BN_FS1 && sums.s2 == BN_FS2; }
+};
+// ---- what each kernel can take or fuse: THE table (DESIGN.md section 3's "fuses" column restates it).  conv_kernel's precedence,
+//      exec_conv's delivery report, stcd_op_conv_fused's refusals and launch_conv's all read it; a launcher checks only what
+//      depends on its plan or the shape.
+enum class ConvKernel { REF, MFMA, SMALL, RES, TILE, GEMM, HALO, DMA };
+enum : unsigned {
+    CAP_SUMS = 1,        // per-channel sums of all channels at the BatchNorm scales
+    CAP_SUM_SLICE = 2,   // ... of any channel slice at any scales
+    CAP_EPI = 4,         // ConvEpi
+    CAP_BWDSUM = 8,      // BwdSum
+    CAP_XF = 16,         // virtual-activation input
+    CAP_NCHW = 32,       // fp32 NCHW output
+    CAP_GROUPS = 64      // more than one tile group
+};
+constexpr unsigned conv_caps(ConvKernel k) {
+    return k == ConvKernel::SMALL ? CAP_SUMS | CAP_BWDSUM | CAP_XF | CAP_NCHW | CAP_GROUPS
+         : k == ConvKernel::RES   ? CAP_SUMS | CAP_SUM_SLICE | CAP_BWDSUM | CAP_XF | CAP_GROUPS
+         : k == ConvKernel::TILE  ? CAP_SUMS | CAP_SUM_SLICE | CAP_GROUPS
+         : k == ConvKernel::GEMM  ? CAP_SUMS | CAP_SUM_SLICE | CAP_EPI | CAP_GROUPS
+         : k == ConvKernel::HALO || k == ConvKernel::DMA ? CAP_EPI
+                                                         : CAP_NCHW | CAP_GROUPS;      // MFMA, REF
+}
+inline const char* conv_kernel_str(ConvKernel k) {
+    static const char* const N[] = {"k_conv_ref", "k_conv_mfma", "k_conv_small", "k_conv_res", "k_conv_tile", "k_conv_gemm", "k_conv_halo", "k_conv_dma"};
+    return N[(int)k];
+}
+// whether a kernel with `caps` can form the sums `a` requests; co: the launch's output channels
+inline bool conv_sums_ok(unsigned caps, const ConvArgs& a, int co) { return (caps & CAP_SUMS) && ((caps & CAP_SUM_SLICE) || a.bn_form(co)); }
+// the first thing `a` asks that kernel k cannot deliver (nullptr: none)
+inline const char* conv_refusal(ConvKernel k, const ConvArgs& a, int co) {
+    const unsigned caps = conv_caps(k);
+    if (a.sums.acc && !conv_sums_ok(caps, a, co))
+        return (caps & CAP_SUMS) ? "sums of a channel slice or at other than the BatchNorm scales (2^26, 2^18)" : "fused per-channel sums";
+    if (a.epi && !(caps & CAP_EPI)) return "a ConvEpi epilogue";
+    if (a.bs && !(caps & CAP_BWDSUM)) return "BatchNorm-backward sums";
+    if (a.xf_on() && !(caps & CAP_XF)) return "a virtual-activation input";
+    if (a.nchw && !(caps & CAP_NCHW)) return "fp32 NCHW output";
+    if (a.groups > 1 && !(caps & CAP_GROUPS)) return "more than one group";
+    // (not a kernel's limit but the request's: a data gradient with BatchNorm-backward sums carries nothing else)
+    if (a.bs && (a.sums.acc || a.xf_on() || a.nchw)) return "forward sums, a virtual input or NCHW output beside BatchNorm-backward sums";
+    return nullptr;
+}
+
 // ---- MFMA (bf16) implementations, kernels_conv_mfma.hip
 struct ConvMfmaPlan {
     int CiB = 0, nchunks = 0, KS = 0, modeB = 0, NT = 0, NTtot = 0;
@@ -312,8 +376,7 @@ ConvMfmaPlan conv_mfma_plan(const stcd_conv_geom& g);
 // w fp32 [ntaps][kpad][wld] (the engine's packed layout) -> fragment-order bf16 image
 void launch_pack_frag(const stcd_conv_geom& g, const ConvMfmaPlan& p, const float* w, int kpad, int wld, void* dst,
                       hipStream_t s);
-int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const void* in, const void* wf, const float* bias,
-                     void* out, bool out_nchw_f32, hipStream_t s);
+int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvArgs& c);
 bool conv_mfma_x4_ok(const stcd_conv_geom g[4], const ConvMfmaPlan p[4]);      // the four phases share one launch shape
 int launch_conv_mfma_x4(const stcd_conv_geom g[4], const ConvMfmaPlan p[4], const void* in, const void* const wf[4],
                         const float* bias, void* out, hipStream_t s);
@@ -334,9 +397,7 @@ struct BwdSum {
     long long* acc = nullptr;                      // its backward accumulators (scale BN_BS)
     int groups = 1;
 };
-int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvResPlan& rp, const void* in, const void* wf,
-                    const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
-                    float s1_scale = BN_FS1, float s2_scale = BN_FS2, const XfSrc* xf = nullptr, const BwdSum* bs = nullptr);
+int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvResPlan& rp, const ConvArgs& c);
 bool conv_res_bwdsum_ok(const stcd_conv_geom& g, const ConvResPlan& rp);
 bool conv_res_xf_ok(const stcd_conv_geom& g, const ConvResPlan& rp, int groups, const XfSrc& xf);      // a virtual input on this plan
 // k_conv_res's tile and epilogue for 3x3 stride-1 convs with Ci % 64 == 0, Co % 16 == 0 on SMALL maps, staged by LDS-DMA: the filter
@@ -348,9 +409,7 @@ struct ConvTilePlan {
     bool ok = false;
 };
 ConvTilePlan conv_tile_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int groups);
-int launch_conv_tile(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvTilePlan& tp, const void* in, const void* wf,
-                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
-                     float s1_scale = BN_FS1, float s2_scale = BN_FS2);
+int launch_conv_tile(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvTilePlan& tp, const ConvArgs& c);
 // Tap-list convolutions with Ci % 64 == 0, Co % 64 == 0 as a tiled GEMM [positions x (taps * Ci)] . [(taps * Ci) x Co]: 128x128
 // or 64x64 block tiles staged through LDS in (64-channel chunk, tap) steps, fused bias + BN statistics, LDS-transposed 16-B
 // output stores.  1x1 convolutions of any stride, and the wide layers the resident-filter kernel cannot take.
@@ -371,9 +430,7 @@ struct ConvEpi {
     const void* res = nullptr; int ldr = 0;
     float alpha = 1.f, beta = 1.f;
 };
-int launch_conv_gemm(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvGemmPlan& gp, const void* in, const void* wf,
-                   const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0 = 0,
-                   float s1_scale = BN_FS1, float s2_scale = BN_FS2, const ConvEpi* epi = nullptr);
+int launch_conv_gemm(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvGemmPlan& gp, const ConvArgs& c);
 // 3x3 stride-1 convolutions of wide layers on large maps (Ci % 64 == 0, Co % 128 == 0): resident 18 x 18 x 64-channel halo, the
 // filter streamed per (chunk, tap) stage; 16 x 16-pixel x 128/256-channel block tiles, persistent blocks (kernels_conv_halo.hip).
 // Reads the CiB = 64 fragment image (the one k_conv_gemm reads); ConvEpi as k_conv_gemm; no fused BN statistics.
@@ -383,8 +440,7 @@ struct ConvHaloPlan {
     bool ok = false;
 };
 ConvHaloPlan conv_halo_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p);
-int launch_conv_halo(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvHaloPlan& hp, const void* in, const void* wf,
-                     const float* bias, void* out, hipStream_t s, const ConvEpi* epi = nullptr);
+int launch_conv_halo(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvHaloPlan& hp, const ConvArgs& c);
 
 // Wide layers on large maps (Ci % 64 == 0, Co % 256 == 0, an even number >= 4 of (chunk, tap) K-tiles) as an implicit GEMM on a
 // 256 x 256 block tile staged by LDS-DMA with counted vmcnt (8 waves, 4 phases per K-tile; kernels_conv_dma.hip).  Reads the
@@ -394,16 +450,13 @@ struct ConvDmaPlan {
     bool ok = false;
 };
 ConvDmaPlan conv_dma_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p);
-int launch_conv_dma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvDmaPlan& dp, const void* in, const void* wf,
-                    const float* bias, void* out, hipStream_t s, const ConvEpi* epi = nullptr);
+int launch_conv_dma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvDmaPlan& dp, const ConvArgs& c);
 
 // small-channel persistent kernel (filter in registers, double-buffered halo, optional fused BN statistics);
 // uses the mode-B fragment image of conv_mfma_plan.
 bool conv_small_ok(const stcd_conv_geom& g, const ConvMfmaPlan& p);
 int conv_small_blocks(const stcd_conv_geom& g, int groups);
-int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_modeB, const float* bias, void* out,
-                      bool out_nchw_f32, int groups, long long* stat_acc, int cpad, hipStream_t s, const XfSrc* xf = nullptr,
-                      const BwdSum* bs = nullptr);
+int launch_conv_small(const stcd_conv_geom& g, const ConvArgs& c);      // (no plan of its own; c.wf: the mode-B image)
 bool conv_small_call_ok(const stcd_conv_geom& g, int groups, const XfSrc* xf);      // what a call's groups / virtual input add to conv_small_ok
 bool conv_small_bwdsum_ok(const stcd_conv_geom& g);      // shapes the fused form handles (16 channels out, whole 8 x 16 tiles, 3 / 5 k-steps)
 struct WgradMfmaPlan {

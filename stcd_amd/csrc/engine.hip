@@ -55,6 +55,7 @@ struct ConvOp {
     int conv = -1; bool dgrad = false;   // which packed filter of which ConvW
     int tap0 = 0;                        // first tap inside that filter's PackSpec (sub-pixel phases)
     int kreal = 0, nreal = 0;            // un-padded channels (algorithmic work accounting)
+    double flops = 0.0, bytes = 0.0;     // ... of the launch, as its profile record reports it (Binder: conv_work; the stem's own)
     ConvMfmaPlan plan; int64_t wf = -1;  // MFMA path: plan + fragment-order weight image (workspace offset)
     bool small = false;                  // eligible for the small-channel persistent kernel
     ConvResPlan res; int res_groups = 1; // resident-filter persistent kernel (3x3 stride 1, Ci % 32 == 0)
@@ -710,6 +711,7 @@ struct Binder {
     void conv(ConvOp& op, const stcd_conv_geom& g, int conv, bool dgrad, int tap0, int kreal, int nreal, int groups = 1) const {
         op = ConvOp();
         op.g = g; op.conv = conv; op.dgrad = dgrad; op.tap0 = tap0; op.kreal = kreal; op.nreal = nreal; op.res_groups = groups;
+        conv_work(e, g, kreal, nreal, &op.flops, &op.bytes);
         if (e.dt == BF16) plan_conv(e, op, groups, with_tile);
         if (op.plan.ok) op.wf = ws.take(op.plan.wf_elems * 2);
         e.conv_ops.push_back(&op);
@@ -719,6 +721,7 @@ struct Binder {
     void stem(ConvOp& op, const stcd_conv_geom& g, int conv, int groups) const {
         op = ConvOp();
         op.g = g; op.conv = conv; op.kreal = e.convs[conv].cin; op.nreal = g.co; op.res_groups = groups;
+        op.flops = 2.0 * g.n * g.ho * g.wo * 49.0 * op.kreal * op.nreal;      // the whole 7x7 filter, not the 7 row taps of g
         op.plan = conv_mfma_plan(g);
         if (g.ldi == 8 && g.co % 64 == 0) op.gemm = conv_gemm_plan(g, op.plan, groups);
         op.gemm.pix_chunks = 1;
@@ -1352,45 +1355,36 @@ static void conv_work(const stcd_engine& e, const stcd_conv_geom& g, int kreal, 
 
 static bool mfma_on(const stcd_engine& e) { return e.dt == BF16 && e.use_mfma; }
 
-// A request for per-channel sums of the launch's output, fused into the conv's epilogue: BatchNorm statistics of a forward
-// conv (all channels, sum and sum of squares) or the sum of a channel slice of a data gradient (a bias gradient).
-struct StatReq { long long* acc = nullptr; int groups = 1; int c0 = 0; int C = 0; float s1 = BN_FS1, s2 = BN_FS2; };
-
-// ---- which kernel a conv-shaped launch runs on.  Decided HERE and nowhere else: exec_conv and the per-op ABI (stcd_op_conv impl 1)
-//      ask conv_kernel once per call and dispatch on the answer; a launcher that then rejects is an error, not a reason to try the
-//      next kernel.  The plans it reads were made by plan_conv at configure time; the precedence below is the table in DESIGN.md
-//      section 3.  Without statistics (eval, data gradients) k_conv_dma / k_conv_halo come before k_conv_gemm; with them they cannot.
-enum class ConvKernel { REF, MFMA, SMALL, RES, TILE, GEMM, HALO, DMA };
+// ---- which kernel a conv-shaped launch runs on.  The CHOICE is made here and nowhere else, and the one switch that launches the
+//      answer is launch_conv below: exec_conv and the per-op ABI (stcd_op_conv, stcd_op_conv_fused) all go through it, and a launcher
+//      that then rejects is an error, not a reason to try the next kernel.  The plans conv_kernel reads were made by plan_conv at
+//      configure time; the precedence is the table in DESIGN.md section 3, and where it depends on what a kernel can take, that is
+//      read from conv_caps (common.h): a kernel without fused sums or NCHW output is passed over by a call that needs them.
+//      (A ConvEpi does not steer the choice: exec_conv reports it as not fused and the caller runs it element-wise.)
 constexpr unsigned conv_kernel_bit(ConvKernel k) { return 1u << (int)k; }
-struct ConvCall {                         // the facts about one call that the choice consults
-    bool nchw = false;                    // fp32 NCHW output (a network output)
-    int stat_groups = 0;                  // fused per-channel sums requested: their group count (0: none) ...
-    bool bn_form = false;                 // ... and whether they are BatchNorm statistics of all channels (k_conv_small sums nothing else)
-    const XfSrc* xf = nullptr;            // virtual-activation input (active when xf->on)
-    bool bwd = false;                     // BwdSum: the launch also forms BatchNorm-backward sums
-    unsigned allowed = ~0u;               // conv_kernel_bit mask of the kernels the caller can run
-    // (a ConvEpi does not steer the choice: kernels without the fused epilogue report epi_fused = 0 and the caller runs it element-wise)
-};
-// tile groups of a k_conv_small launch: a virtual input partitions the tiles by the PRODUCER's BatchNorm groups, statistics or not
-// (eval mode has none); else the groups of the BatchNorm statistics it sums
-static int conv_small_groups(const ConvCall& k) {
-    return (k.xf && k.xf->on) ? k.xf->groups : (k.stat_groups > 0 && k.bn_form) ? k.stat_groups : 1;
+// tile groups of a k_conv_small launch: the destination layer's for a BwdSum; a virtual input partitions the tiles by the PRODUCER's
+// BatchNorm groups, statistics or not (eval mode has none); else the groups of the BatchNorm statistics it sums
+static int conv_small_groups(const ConvArgs& a, int co) {
+    return a.bs ? a.bs->groups : a.xf_on() ? a.xf->groups : (a.sums.acc && a.bn_form(co)) ? a.sums.groups : 1;
 }
-static ConvKernel conv_kernel(bool mfma, bool use_small, const ConvOp& op, const ConvCall& k) {
-    auto may = [&](ConvKernel x) { return (k.allowed & conv_kernel_bit(x)) != 0; };
+// allowed: conv_kernel_bit mask of the kernels the caller can run
+static ConvKernel conv_kernel(bool mfma, bool use_small, const ConvOp& op, const ConvArgs& a, unsigned allowed = ~0u) {
+    auto may = [&](ConvKernel x) { return (allowed & conv_kernel_bit(x)) != 0; };
+    auto takes = [](ConvKernel x, unsigned need) { return (need & ~conv_caps(x)) == 0; };
     if (conv_on_ref(mfma, op)) return ConvKernel::REF;
-    const bool xf_on = k.xf && k.xf->on, stats = k.stat_groups > 0;
+    const unsigned nchw = a.nchw ? CAP_NCHW : 0, sums = a.sums.acc ? CAP_SUMS : 0, xf = a.xf_on() ? CAP_XF : 0;
+    const unsigned grp = op.res_groups > 1 ? CAP_GROUPS : 0;
     const bool small = op.small && use_small;
-    if (k.bwd) return small ? ConvKernel::SMALL : ConvKernel::RES;
-    if (op.gemm.ok && !k.nchw) {
-        if (op.dma.ok && op.res_groups == 1 && !stats && may(ConvKernel::DMA)) return ConvKernel::DMA;
-        if (op.halo.ok && !stats && may(ConvKernel::HALO)) return ConvKernel::HALO;
+    if (a.bs) return small ? ConvKernel::SMALL : ConvKernel::RES;
+    if (op.gemm.ok && takes(ConvKernel::GEMM, nchw)) {
+        if (op.dma.ok && takes(ConvKernel::DMA, grp | sums) && may(ConvKernel::DMA)) return ConvKernel::DMA;
+        if (op.halo.ok && takes(ConvKernel::HALO, sums) && may(ConvKernel::HALO)) return ConvKernel::HALO;
         return ConvKernel::GEMM;
     }
-    if (small && conv_small_call_ok(op.g, conv_small_groups(k), k.xf)) return ConvKernel::SMALL;
-    if (op.res.ok && !k.nchw && !small) {
-        if (op.tile.ok && !xf_on && may(ConvKernel::TILE)) return ConvKernel::TILE;
-        if (!xf_on || conv_res_xf_ok(op.g, op.res, op.res_groups, *k.xf)) return ConvKernel::RES;
+    if (small && conv_small_call_ok(op.g, conv_small_groups(a, op.g.co), a.xf)) return ConvKernel::SMALL;
+    if (op.res.ok && takes(ConvKernel::RES, nchw) && !small) {
+        if (op.tile.ok && takes(ConvKernel::TILE, xf) && may(ConvKernel::TILE)) return ConvKernel::TILE;
+        if (!xf || conv_res_xf_ok(op.g, op.res, op.res_groups, *a.xf)) return ConvKernel::RES;
     }
     return ConvKernel::MFMA;
 }
@@ -1399,7 +1393,10 @@ static void conv_kernel_name(ConvKernel kern, const ConvOp& op, bool bwd, char (
     switch (kern) {
         case ConvKernel::DMA: snprintf(kname, sizeof(kname), "k_conv_dma"); break;
         case ConvKernel::HALO: snprintf(kname, sizeof(kname), "k_conv_halo"); break;
-        case ConvKernel::GEMM: snprintf(kname, sizeof(kname), "k_conv_gemm<%d>", op.gemm.W); break;
+        case ConvKernel::GEMM:
+            if (op.gemm.pix_chunks) snprintf(kname, sizeof(kname), "k_conv_gemm<stem>");
+            else snprintf(kname, sizeof(kname), "k_conv_gemm<%d>", op.gemm.W);
+            break;
         case ConvKernel::TILE: snprintf(kname, sizeof(kname), "k_conv_tile<%d>", op.tile.NT); break;
         case ConvKernel::RES:
             if (bwd) snprintf(kname, sizeof(kname), "k_conv_res<bwd>");
@@ -1414,85 +1411,69 @@ static void conv_kernel_name(ConvKernel kern, const ConvOp& op, bool bwd, char (
     }
 }
 
-// *stat_chunks receives 1 when the kernel delivered the sums, 0 when the caller must run the separate pass; *epi_fused likewise
-static void exec_conv(const Ctx& c, const ConvOp& op, const void* in, const float* bias, void* out, bool nchw,
-                      const StatReq* sr = nullptr, int* stat_chunks = nullptr, const ConvEpi* epi = nullptr, int* epi_fused = nullptr,
-                      const XfSrc* xf = nullptr, const BwdSum* bs = nullptr) {
+// THE switch that launches a chosen kernel: `a` as the kernel is to run it (a.wf its filter image, a.groups its tile groups).
+// 1: the kernel cannot deliver something `a` asks (conv_refusal) or its launcher rejected the plan / shape; nothing was launched.
+static int launch_conv(ConvKernel kern, const ConvOp& op, const ConvArgs& args) {
+    if (conv_refusal(kern, args, op.g.co)) return 1;
+    ConvArgs a = args;
+    if (!a.sums.acc) { a.sums = StatReq(); a.sums.C = op.g.co; }      // (what the kernels' argument structs hold without a request)
+    switch (kern) {
+        case ConvKernel::DMA: return launch_conv_dma(op.g, op.plan, op.dma, a);
+        case ConvKernel::HALO: return launch_conv_halo(op.g, op.plan, op.halo, a);
+        case ConvKernel::GEMM: return launch_conv_gemm(op.g, op.plan, op.gemm, a);
+        case ConvKernel::SMALL: return launch_conv_small(op.g, a);
+        case ConvKernel::TILE: return launch_conv_tile(op.g, op.plan, op.tile, a);
+        case ConvKernel::RES: return launch_conv_res(op.g, op.plan, op.res, a);
+        case ConvKernel::MFMA: return launch_conv_mfma(op.g, op.plan, a);
+        case ConvKernel::REF: break;      // (reads the fp32 filter image, not a.wf: exec_conv, stcd_op_conv)
+    }
+    return 1;
+}
+
+// What exec_conv delivered of what the caller asked to have fused; the caller runs the separate pass for the rest.  The rules:
+//   sums: by a kernel with CAP_SUMS, and only when the request's groups equal the launch's -- the plan's (res_groups), or for
+//         k_conv_small its own rule (conv_small_groups); k_conv_small sums only full-channel BatchNorm-form requests (no
+//         CAP_SUM_SLICE).  With a BwdSum the launch sums the backward terms instead (their scales, all channels): not delivered.
+//   epi:  by a kernel with CAP_EPI.
+struct ConvDone { bool sums = false, epi = false; };
+static ConvArgs conv_args(const void* in, void* out, const float* bias = nullptr, bool nchw = false) {
+    ConvArgs a;
+    a.in = in; a.out = out; a.bias = bias; a.nchw = nchw;
+    return a;
+}
+// args: in / bias / out / nchw and the features asked for; wf, groups and the stream are filled in here
+static ConvDone exec_conv(const Ctx& c, const ConvOp& op, const ConvArgs& args) {
     const ConvW& cv = c.e.convs[op.conv];
-    long long* stat_acc = sr ? sr->acc : nullptr;
-    ConvCall call;
-    call.nchw = nchw; call.xf = xf; call.bwd = bs != nullptr;
-    call.stat_groups = stat_acc ? sr->groups : 0;
-    call.bn_form = sr && sr->c0 == 0 && sr->C == op.g.co && sr->s1 == BN_FS1 && sr->s2 == BN_FS2;
-    const ConvKernel kern = conv_kernel(mfma_on(c.e), c.e.use_small, op, call);
-    double fl, by;
-    conv_work(c.e, op.g, op.kreal, op.nreal, &fl, &by);
-    if (bs) by += (double)op.g.n * op.g.ho * op.g.wo * op.g.co * 2.0;
+    const ConvKernel kern = conv_kernel(mfma_on(c.e), c.e.use_small, op, args);
+    const unsigned caps = conv_caps(kern);
     char kname[64];
-    conv_kernel_name(kern, op, bs != nullptr, kname);
-    ProfScope prof(c, PC_CONV, fl, by, kname);
-    if (stat_chunks) *stat_chunks = 0;
-    if (epi_fused) *epi_fused = 0;
-    if (xf && xf->on && kern != ConvKernel::SMALL && kern != ConvKernel::RES) {
+    conv_kernel_name(kern, op, args.bs != nullptr, kname);
+    ProfScope prof(c, PC_CONV, op.flops, op.bytes + (args.bs ? (double)op.g.n * op.g.ho * op.g.wo * op.g.co * 2.0 : 0.0), kname);
+    ConvDone done;
+    if (args.xf_on() && !(caps & CAP_XF)) {
         // planned at configure time for a kernel that applies the transform: no other can (and none may run on raw Y)
         set_error("internal: a virtual-activation input reached a convolution kernel without the staging transform");
-        return;
+        return done;
     }
-    const void* wf = op.wf >= 0 ? c.at(op.wf) : nullptr;
-    // statistics as the resident-filter family sums them: any channel slice, partitioned by the launch's own groups
-    const bool want = call.stat_groups > 0 && call.stat_groups == op.res_groups;
-    long long* sp = want ? stat_acc : nullptr;
-    const int sC = want ? sr->C : op.g.co, sc0 = want ? sr->c0 : 0;
-    const float s1 = want ? sr->s1 : BN_FS1, s2 = want ? sr->s2 : BN_FS2;
-    int rc = 0;
-    switch (kern) {
-        case ConvKernel::DMA:
-        case ConvKernel::HALO:
-            rc = kern == ConvKernel::DMA ? launch_conv_dma(op.g, op.plan, op.dma, in, wf, bias, out, c.s, epi)
-                                         : launch_conv_halo(op.g, op.plan, op.halo, in, wf, bias, out, c.s, epi);
-            if (epi_fused && epi) *epi_fused = 1;
-            break;
-        case ConvKernel::GEMM:
-            rc = launch_conv_gemm(op.g, op.plan, op.gemm, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2, epi);
-            if (stat_chunks && want) *stat_chunks = 1;
-            if (epi_fused && epi) *epi_fused = 1;
-            break;
-        case ConvKernel::SMALL:
-            if (bs) {
-                rc = launch_conv_small(op.g, in, wf, bias, out, nchw, bs->groups, nullptr, op.g.co, c.s, nullptr, bs);
-            } else {
-                const int groups = conv_small_groups(call);
-                long long* ssp = (call.stat_groups > 0 && call.bn_form && call.stat_groups == groups) ? stat_acc : nullptr;
-                rc = launch_conv_small(op.g, in, wf, bias, out, nchw, groups, ssp, op.g.co, c.s, xf);
-                if (stat_chunks && ssp) *stat_chunks = 1;
-            }
-            break;
-        case ConvKernel::TILE:
-            rc = launch_conv_tile(op.g, op.plan, op.tile, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2);
-            if (stat_chunks && want) *stat_chunks = 1;
-            break;
-        case ConvKernel::RES:
-            if (bs) {
-                rc = launch_conv_res(op.g, op.plan, op.res, in, wf, bias, out, op.res_groups, nullptr, op.g.co, c.s, 0, BN_BS, BN_BS, nullptr, bs);
-            } else {
-                rc = launch_conv_res(op.g, op.plan, op.res, in, wf, bias, out, op.res_groups, sp, sC, c.s, sc0, s1, s2, xf);
-                if (stat_chunks && want) *stat_chunks = 1;
-            }
-            break;
-        case ConvKernel::MFMA:
-            rc = launch_conv_mfma(op.g, op.plan, in, wf, bias, out, nchw, c.s);
-            break;
-        case ConvKernel::REF: {
-            const PackSpec& ps = op.dgrad ? cv.dgrad : cv.fwd;
-            const float* w = c.at<float>(op.dgrad ? cv.wpk_dgrad : cv.wpk_fwd) + (int64_t)op.tap0 * ps.kpad * ps.wld;
-            launch_conv_ref(c.e.dt, op.g, in, w, ps.kpad, ps.wld, bias, out, nchw, c.s);
-            break;
-        }
+    ConvArgs a = args;
+    a.s = c.s;
+    if (kern == ConvKernel::REF) {
+        const PackSpec& ps = op.dgrad ? cv.dgrad : cv.fwd;
+        const float* w = c.at<float>(op.dgrad ? cv.wpk_dgrad : cv.wpk_fwd) + (int64_t)op.tap0 * ps.kpad * ps.wld;
+        launch_conv_ref(c.e.dt, op.g, a.in, w, ps.kpad, ps.wld, a.bias, a.out, a.nchw, a.s);
+        return done;
     }
-    if (rc != 0)
-        set_error(bs ? std::string("fused BatchNorm-backward sums: the data-gradient launch of ") + cv.name + " does not fit " + kname
-                     : std::string("internal: ") + kname + " rejected the " + (op.dgrad ? "data-gradient" : "forward") + " launch of " +
-                           cv.name + " it was chosen for");
+    a.wf = op.wf >= 0 ? c.at(op.wf) : nullptr;
+    a.groups = !(caps & CAP_GROUPS) ? 1 : kern == ConvKernel::SMALL ? conv_small_groups(a, op.g.co) : op.res_groups;
+    done.sums = a.sums.acc && !a.bs && conv_sums_ok(caps, a, op.g.co) && a.sums.groups == a.groups;
+    done.epi = a.epi && (caps & CAP_EPI);
+    if (!done.sums) a.sums = StatReq();
+    if (!done.epi) a.epi = nullptr;
+    if (launch_conv(kern, op, a) != 0)
+        set_error(a.bs ? std::string("fused BatchNorm-backward sums: the data-gradient launch of ") + cv.name + " does not fit " + kname
+                       : std::string("internal: ") + kname + " rejected the " + (op.dgrad ? "data-gradient" : "forward") + " launch of " +
+                             cv.name + " it was chosen for");
+    return done;
 }
 
 // the four sub-pixel phases of a stride-2 transposed convolution as one launch; false: not applicable (caller loops)
@@ -1503,9 +1484,7 @@ static bool exec_conv_x4(const Ctx& c, const ConvOp ops[4], const void* in, cons
     for (int k = 0; k < 4; ++k) {
         if (!ops[k].plan.ok || ops[k].wf < 0) return false;
         g[k] = ops[k].g; p[k] = ops[k].plan; wf[k] = c.at(ops[k].wf);
-        double f1, b1;
-        conv_work(c.e, ops[k].g, ops[k].kreal, ops[k].nreal, &f1, &b1);
-        fl += f1; by += b1;
+        fl += ops[k].flops; by += ops[k].bytes;
     }
     if (!conv_mfma_x4_ok(g, p)) return false;
     char kname[64];
@@ -1670,6 +1649,27 @@ static void reduce_stage(const Ctx& c, int stage) {
     launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[stage]), (int)e.rjobs[stage].size(), e.rjobs_total[stage], c.ws, c.grads, c.s);
 }
 
+// the Dropout2d factors of drop entry `drop` (nullptr: the layer has none, or dropout is off)
+static const float* drop_mask(const Ctx& c, int drop, bool on = true) {
+    return (on && c.e.drop_p > 0.f && drop >= 0) ? c.at<float>(c.e.masks) + c.e.drops[drop].off : nullptr;
+}
+// the BatchNorm fields of an activation launch: it derives scale / shift itself, from the accumulators `facc` in training mode,
+// from the running statistics in eval mode (facc == nullptr) -- no finalize / prepare launch either way
+static void bn_fields(BnActArgs& a, const Ctx& c, const BnP& bn, int C, float* bn_running, long long* facc) {
+    a.facc = facc;
+    a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
+    a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + C;
+}
+// conv, then the BatchNorm statistics of its output Y in `facc` (nullptr: eval, none): summed by the conv kernel where it delivers
+// them (exec_conv), else by the separate pass
+static void exec_conv_stats(const Ctx& c, const ConvOp& op, ConvArgs a, long long* facc, int groups, int C, const TRef& Y, int64_t ppg,
+                            double act_bytes) {
+    a.sums.acc = facc; a.sums.groups = groups; a.sums.C = C;
+    if (exec_conv(c, op, a).sums || !facc) return;
+    ProfScope ps(c, PC_BN_STATS, 0.0, act_bytes);
+    launch_bn_stats(c.e.dt, c.at(Y.off), Y.ld, C, groups, ppg, facc, c.s);
+}
+
 // the producer P as its consumer's staging transform sees it (XfSrc, common.h): training -> batch statistics from P's accumulators,
 // the consumer's block 0 publishes P.stat and updates the running statistics; eval -> the running statistics, nothing written
 static XfSrc xf_source(const Ctx& c, const Cbrd& P, float* bn_running, bool training) {
@@ -1681,7 +1681,7 @@ static XfSrc xf_source(const Ctx& c, const Cbrd& P, float* bn_running, bool trai
     x.gamma = c.params + bn.g_off; x.beta = c.params + bn.b_off;
     x.rmean = bn_running + bn.run_off; x.rvar = bn_running + bn.run_off + x.C;
     x.stat = c.at<float>(P.stat);
-    x.mask = (training && e.drop_p > 0.f && P.drop >= 0) ? c.at<float>(e.masks) + e.drops[P.drop].off : nullptr;
+    x.mask = drop_mask(c, P.drop, training);
     x.publish = training ? 1 : 0;
     x.on = 1;
     return x;
@@ -1692,33 +1692,24 @@ static void cbrd_forward(const Ctx& c, const Cbrd& L, float* bn_running, bool tr
     const ConvW& cv = e.convs[L.conv];
     const BnP& bn = e.bns[L.bn];
     const int C = cv.cout;
-    int fused_chunks = 0;
-    StatReq sr; sr.acc = training ? c.at<long long>(L.facc) : nullptr; sr.groups = L.groups; sr.C = C;
-    XfSrc xf;
-    if (L.xsrc) xf = xf_source(c, *L.xsrc, bn_running, training);
-    exec_conv(c, L.fwd, c.at(L.in.off), c.params + cv.b_off, c.at(L.Y.off), false, &sr, &fused_chunks, nullptr, nullptr, L.xsrc ? &xf : nullptr);
     const int64_t ppg = (int64_t)L.npg * L.H * L.W;
     const double act_bytes = (double)L.N * L.H * L.W * C * (double)dsize(e.dt);
+    long long* const facc = training ? c.at<long long>(L.facc) : nullptr;
+    XfSrc xf;                // (on == 0: a materialised input)
+    if (L.xsrc) xf = xf_source(c, *L.xsrc, bn_running, training);
+    ConvArgs ca = conv_args(c.at(L.in.off), c.at(L.Y.off), c.params + cv.b_off);
+    ca.xf = &xf;
+    exec_conv_stats(c, L.fwd, ca, facc, L.groups, C, L.Y, ppg, act_bytes);
     float* stat = c.at<float>(L.stat);
-    if (training) {
-        if (!fused_chunks) {
-            ProfScope ps(c, PC_BN_STATS, 0.0, act_bytes);
-            launch_bn_stats(e.dt, c.at(L.Y.off), L.Y.ld, C, L.groups, ppg, c.at<long long>(L.facc), c.s);
-        }
-    }
     if (L.virt) return;      // the consumer applies scale / shift / ReLU / Dropout2d while staging Y (and publishes the statistics)
     BnActArgs a;
     a.Y = c.at(L.Y.off); a.ldy = L.Y.ld;
     a.A = skip_recomputed(e, L) ? nullptr : c.at(L.A.off); a.lda = L.A.ld; a.a_group_off = L.A.goff;
     a.P = L.pool ? c.at(L.P.off) : nullptr; a.ldp = L.P.ld;
     a.stat = stat;
-    a.mask = (training && e.drop_p > 0.f && L.drop >= 0) ? c.at<float>(e.masks) + e.drops[L.drop].off : nullptr;
+    a.mask = drop_mask(c, L.drop, training);
     a.C = C; a.groups = L.groups; a.npg = L.npg; a.H = L.H; a.W = L.W; a.relu = 1;
-    // the activation kernel derives scale / shift itself: from the accumulators in training mode, from the running statistics in
-    // eval mode (no finalize / prepare launch either way)
-    a.facc = training ? c.at<long long>(L.facc) : nullptr;
-    a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-    a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + C;
+    bn_fields(a, c, bn, C, bn_running, facc);
     if (L.fuse_dst.off >= 0 && e.use_act_fuse && L.groups == 2) {
         ProfScope ps(c, PC_BN_ACT, 0.0, act_bytes * (a.A ? 2.75 : 1.75), "k_bn_act_pair");
         launch_bn_act_pair(e.dt, a, c.at(L.fuse_dst.off), L.fuse_dst.ld, e.arch == STCD_ARCH_DIFF ? 0 : 1, c.s);
@@ -1733,7 +1724,7 @@ static BwdSum bwd_sum_of(const Ctx& c, const Cbrd& P) {
     stcd_engine& e = c.e;
     BwdSum b;
     b.Y = c.at(P.Y.off); b.ldy = P.Y.ld; b.stat = c.at<float>(P.stat);
-    b.mask = (e.drop_p > 0.f && P.drop >= 0) ? c.at<float>(e.masks) + e.drops[P.drop].off : nullptr;
+    b.mask = drop_mask(c, P.drop);
     b.acc = c.at<long long>(P.bacc); b.groups = P.groups;
     return b;
 }
@@ -1746,7 +1737,7 @@ static void cbrd_backward(const Ctx& c, const Cbrd& L, int skip_chunks = 0) {
     const int C = cv.cout;
     const int64_t HW = (int64_t)L.H * L.W, ppg = (int64_t)L.npg * HW;
     const float* stat = c.at<float>(L.stat);
-    const float* mask = (e.drop_p > 0.f && L.drop >= 0) ? c.at<float>(e.masks) + e.drops[L.drop].off : nullptr;
+    const float* mask = drop_mask(c, L.drop);
     long long* bacc = c.at<long long>(L.bacc);
     const double act_bytes = (double)L.N * HW * C * (double)dsize(e.dt);
     (void)ppg;
@@ -1763,12 +1754,11 @@ static void cbrd_backward(const Ctx& c, const Cbrd& L, int skip_chunks = 0) {
     // weight gradient (the conv bias feeds only a train-mode BN: its gradient is exactly zero and stays zero)
     exec_wgrad(c, L.wg, c.at(L.in.off), c.at(L.dY.off));
     if (L.has_dIn) {
-        StatReq sr;
-        if (L.dgr_sum_acc >= 0) { sr.acc = c.at<long long>(L.dgr_sum_acc); sr.groups = 1; sr.c0 = L.dgr_sum_c0; sr.C = L.dgr_sum_C; sr.s1 = sr.s2 = BN_BS; }
+        ConvArgs a = conv_args(c.at(L.dY.off), c.at(L.dIn.off));
+        if (L.dgr_sum_acc >= 0) a.sums = StatReq{c.at<long long>(L.dgr_sum_acc), 1, L.dgr_sum_c0, L.dgr_sum_C, BN_BS, BN_BS};
         BwdSum bs;
-        if (L.dgr_bwd) bs = bwd_sum_of(c, *L.dgr_bwd);
-        exec_conv(c, L.dgr, c.at(L.dY.off), nullptr, c.at(L.dIn.off), false, L.dgr_sum_acc >= 0 ? &sr : nullptr, nullptr, nullptr, nullptr, nullptr,
-                  L.dgr_bwd ? &bs : nullptr);
+        if (L.dgr_bwd) { bs = bwd_sum_of(c, *L.dgr_bwd); a.bs = &bs; }
+        exec_conv(c, L.dgr, a);
     }
 }
 
@@ -1776,7 +1766,7 @@ static void upconv_forward(const Ctx& c, const UpConv& U) {
     stcd_engine& e = c.e;
     const ConvW& cv = e.convs[U.conv];
     if (!exec_conv_x4(c, U.fwd, c.at(U.in.off), c.params + cv.b_off, c.at(U.out.off)))
-        for (int ph = 0; ph < 4; ++ph) exec_conv(c, U.fwd[ph], c.at(U.in.off), c.params + cv.b_off, c.at(U.out.off), false);
+        for (int ph = 0; ph < 4; ++ph) exec_conv(c, U.fwd[ph], conv_args(c.at(U.in.off), c.at(U.out.off), c.params + cv.b_off));
     launch_rep_pad(e.dt, c.at(U.out.off), U.out.ld, U.N, U.Ho, U.Wo, 2 * U.h, 2 * U.w, U.C, c.s);
 }
 
@@ -1798,7 +1788,7 @@ static void upconv_backward(const Ctx& c, const UpConv& U) {
                                  2 * U.w, U.C, c.grads + cv.b_off, c.s, e.dt == BF16 ? c.at<long long>(U.bias_acc) : nullptr);
     }
     for (int ph = 0; ph < 4; ++ph) exec_wgrad(c, U.wg[ph], c.at(U.in.off), c.at(U.dOut.off));
-    exec_conv(c, U.dgr, c.at(U.dOut.off), nullptr, c.at(U.dIn.off), false);
+    exec_conv(c, U.dgr, conv_args(c.at(U.dOut.off), c.at(U.dIn.off)));
 }
 
 // cross_conc block (SiamUnet_crossconc.py:24-33): skip slice of the level's concat buffer = relu(bn(conv(relu(bn(pairdw(x1, x2))))))
@@ -1818,9 +1808,7 @@ static void xconc_forward(const Ctx& c, const XConc& X, const Cbrd& skip, float*
     a.stat = c.at<float>(X.stat1);
     a.mask = nullptr;
     a.C = C; a.groups = 1; a.npg = B; a.H = h; a.W = w; a.relu = 1;
-    a.facc = training ? c.at<long long>(X.facc1) : nullptr;
-    a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-    a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + C;
+    bn_fields(a, c, bn, C, bn_running, training ? c.at<long long>(X.facc1) : nullptr);
     launch_bn_act(e.dt, a, c.s);
     cbrd_forward(c, X.res, bn_running, training);
 }
@@ -1910,10 +1898,11 @@ static int forward_fcsiam(stcd_engine& e, const float* x1, const float* x2, cons
         }
     }
     {
-        XfSrc xf;
+        XfSrc xf;                // (on == 0: a materialised input)
         if (e.final_xsrc) xf = xf_source(c, *e.final_xsrc, bn_running, training != 0);
-        exec_conv(c, e.final_fwd, c.at(e.finalIn.off), params + e.convs[e.final_conv].b_off, logits, true, nullptr, nullptr, nullptr, nullptr,
-                  e.final_xsrc ? &xf : nullptr);
+        ConvArgs a = conv_args(c.at(e.finalIn.off), logits, params + e.convs[e.final_conv].b_off, true);
+        a.xf = &xf;
+        exec_conv(c, e.final_fwd, a);
     }
     STCD_HIP(hipGetLastError());
     return 0;
@@ -2012,10 +2001,10 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
         }
         exec_wgrad(c, e.final_wg, c.at(e.finalIn.off), c.at(e.G.off));
         {
+            ConvArgs a = conv_args(c.at(e.G.off), c.at(e.dFinalIn.off));
             BwdSum bs;
-            if (e.final_dgr_bwd) bs = bwd_sum_of(c, *e.final_dgr_bwd);
-            exec_conv(c, e.final_dgr, c.at(e.G.off), nullptr, c.at(e.dFinalIn.off), false, nullptr, nullptr, nullptr, nullptr, nullptr,
-                      e.final_dgr_bwd ? &bs : nullptr);
+            if (e.final_dgr_bwd) { bs = bwd_sum_of(c, *e.final_dgr_bwd); a.bs = &bs; }
+            exec_conv(c, e.final_dgr, a);
         }
         int di = (int)e.dec.size() - 1;
         for (int k = 3; k >= 0; --k) {
@@ -2045,7 +2034,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
                 const int C = e.convs[L.conv].cout;
                 int lvl = 0;
                 while (lvl < 4 && SKIP_IDX[lvl] != li) ++lvl;
-                const float* mk = e.drop_p > 0.f ? c.at<float>(e.masks) + e.drops[L.drop].off : nullptr;
+                const float* mk = drop_mask(c, L.drop);
                 if (skip_recomputed(e, L)) {
                     ProfScope ps(c, PC_POOL_FUSE, 0.0, 2.75 * L.N * L.H * L.W * C * (double)T, "k_skip_bwd_pair");
                     launch_skip_bwd_pair(dt, e.arch == STCD_ARCH_DIFF ? 0 : 1, c.at(L.Y.off), L.Y.ld, c.at<char>(e.dD[lvl].off) + C * T,
@@ -2055,8 +2044,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
                 ProfScope ps(c, PC_POOL_FUSE, 0.0, 4.75 * L.N * L.H * L.W * C * (double)T, "k_skip_bwd");
                 launch_skip_bwd(dt, e.arch == STCD_ARCH_DIFF ? 0 : 1, c.at(L.A.off), L.A.ld, L.A.goff, c.at(L.Y.off), L.Y.ld,
                                 c.at<char>(e.dD[lvl].off) + C * T, e.dD[lvl].ld, c.at(L.dPool.off), L.dPool.ld, c.at(L.dA.off), L.dA.ld,
-                                L.dA.goff, c.at<float>(L.stat), e.drop_p > 0.f ? c.at<float>(e.masks) + e.drops[L.drop].off : nullptr,
-                                L.npg, L.H, L.W, C, c.at<long long>(L.bacc), s);
+                                L.dA.goff, c.at<float>(L.stat), mk, L.npg, L.H, L.W, C, c.at<long long>(L.bacc), s);
                 }
                 skip_chunks = 1;
             } else if (L.pool) {  // dA_skip += gradient routed back through the 2x2 max-pool
@@ -2376,26 +2364,12 @@ static void sn_block_forward(const Ctx& c, const NBlock& b, float* bn_running, b
     const double act_bytes = (double)px * b.C * (double)T;
     (void)px; (void)T;      // (the concat prefix of b.in was written by the producers: NBlock::extra_dst)
     BnActArgs a;
-    auto bn_stage = [&](const ConvOp& f, const void* in, int conv, int bni, const TRef& Y, int64_t stat_off, int64_t facc_off) {
-        const ConvW& cv = e.convs[conv];
-        const BnP& bn = e.bns[bni];
-        int fused = 0;
-        StatReq sr; sr.acc = training ? c.at<long long>(facc_off) : nullptr; sr.groups = b.groups; sr.C = b.C;
-        exec_conv(c, f, in, c.params + cv.b_off, c.at(Y.off), false, &sr, &fused);
-        float* stat = c.at<float>(stat_off);
-        if (training) {
-            if (!fused) {
-                ProfScope ps(c, PC_BN_STATS, 0.0, act_bytes);
-                launch_bn_stats(e.dt, c.at(Y.off), Y.ld, b.C, b.groups, ppg, c.at<long long>(facc_off), c.s);
-            }
-            a.facc = c.at<long long>(facc_off); a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-            a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + b.C;
-        } else {      // eval: the activation kernel reads the running statistics itself
-            a.facc = nullptr; a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-            a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + b.C;
-        }
+    auto bn_stage = [&](const ConvOp& f, const void* in, int conv, int bni, const TRef& Y, int64_t facc_off) {
+        long long* const facc = training ? c.at<long long>(facc_off) : nullptr;
+        exec_conv_stats(c, f, conv_args(in, c.at(Y.off), c.params + e.convs[conv].b_off), facc, b.groups, b.C, Y, ppg, act_bytes);
+        bn_fields(a, c, e.bns[bni], b.C, bn_running, facc);
     };
-    bn_stage(b.f1, c.at(b.in.off), b.c1, b.bn1, b.Y1, b.stat1, b.facc1);
+    bn_stage(b.f1, c.at(b.in.off), b.c1, b.bn1, b.Y1, b.facc1);
     a.Y = c.at(b.Y1.off); a.ldy = b.Y1.ld; a.A = c.at(b.A1.off); a.lda = b.A1.ld; a.a_group_off = ppg * b.A1.ld;
     a.P = nullptr; a.ldp = 0; a.stat = c.at<float>(b.stat1); a.mask = nullptr;
     a.C = b.C; a.groups = b.groups; a.npg = b.npg; a.H = b.H; a.W = b.W; a.relu = 1;
@@ -2403,7 +2377,7 @@ static void sn_block_forward(const Ctx& c, const NBlock& b, float* bn_running, b
         ProfScope ps(c, PC_BN_ACT, 0.0, 2.0 * act_bytes);
         launch_bn_act(e.dt, a, c.s);
     }
-    bn_stage(b.f2, c.at(b.A1.off), b.c2, b.bn2, b.Y2, b.stat2, b.facc2);
+    bn_stage(b.f2, c.at(b.A1.off), b.c2, b.bn2, b.Y2, b.facc2);
     a.Y = c.at(b.Y2.off); a.ldy = b.Y2.ld; a.A = c.at(b.Out.off); a.lda = b.Out.ld; a.a_group_off = ppg * b.Out.ld;
     a.P = b.pool ? c.at(b.P.off) : nullptr; a.ldp = b.P.ld; a.stat = c.at<float>(b.stat2);
     a.res = c.at(b.Y1.off); a.ldres = b.Y1.ld;        // identity = conv1's raw output (SNUNet.py:19,25)
@@ -2449,7 +2423,7 @@ static void sn_block_backward(const Ctx& c, const NBlock& b) {
                             c.grads + e.convs[b.c1].b_off);
     }
     exec_wgrad(c, b.w2, c.at(b.A1.off), c.at(b.dOut.off));                   // dOut now holds dY2
-    exec_conv(c, b.d2, c.at(b.dOut.off), nullptr, c.at(b.dA1.off), false);
+    exec_conv(c, b.d2, conv_args(c.at(b.dOut.off), c.at(b.dA1.off)));
     {
         ProfScope ps(c, PC_BN_BWD_REDUCE, 0.0, 2.0 * act_bytes);
         launch_bn_bwd_reduce(e.dt, c.at(b.dA1.off), b.dA1.ld, goff_a1, c.at(b.Y1.off), b.Y1.ld, c.at<float>(b.stat1), nullptr, b.C,
@@ -2466,16 +2440,16 @@ static void sn_block_backward(const Ctx& c, const NBlock& b) {
     // kernel wrote it to both places (a 128-byte hipMemcpyAsync cost three copy kernels per block, 44 launches per step)
     exec_wgrad(c, b.w1, c.at(b.in.off), c.at(b.dA1.off));                   // dA1 now holds dY1
     if (b.dIn.off >= 0) {
-        StatReq sr;
-        if (b.d1_sum_acc >= 0) { sr.acc = c.at<long long>(b.d1_sum_acc); sr.groups = 1; sr.c0 = b.d1_sum_c0; sr.C = b.d1_sum_C; sr.s1 = sr.s2 = BN_BS; }
-        exec_conv(c, b.d1, c.at(b.dA1.off), nullptr, c.at(b.dIn.off), false, b.d1_sum_acc >= 0 ? &sr : nullptr);
+        ConvArgs a = conv_args(c.at(b.dA1.off), c.at(b.dIn.off));
+        if (b.d1_sum_acc >= 0) a.sums = StatReq{c.at<long long>(b.d1_sum_acc), 1, b.d1_sum_c0, b.d1_sum_C, BN_BS, BN_BS};
+        exec_conv(c, b.d1, a);
     }
 }
 
 static void sn_up_forward(const Ctx& c, const SnUp& u) {
     const ConvW& cv = c.e.convs[u.conv];
     if (exec_conv_x4(c, u.fwd, c.at(u.src.off), c.params + cv.b_off, c.at(u.out.off))) return;
-    for (int ph = 0; ph < 4; ++ph) exec_conv(c, u.fwd[ph], c.at(u.src.off), c.params + cv.b_off, c.at(u.out.off), false);
+    for (int ph = 0; ph < 4; ++ph) exec_conv(c, u.fwd[ph], conv_args(c.at(u.src.off), c.at(u.out.off), c.params + cv.b_off));
 }
 static void sn_up_backward(const Ctx& c, const SnUp& u) {
     stcd_engine& e = c.e;
@@ -2485,7 +2459,7 @@ static void sn_up_backward(const Ctx& c, const SnUp& u) {
         launch_bias_grad(e.dt, c.at(u.dOut.off), u.dOut.ld, (int64_t)u.N * 4 * u.h * u.w, u.C, c.grads + cv.b_off, c.s,
                          e.dt == BF16 ? c.at<long long>(u.bias_acc) : nullptr);
     for (int ph = 0; ph < 4; ++ph) exec_wgrad(c, u.wg[ph], c.at(u.src.off), c.at(u.dOut.off));
-    exec_conv(c, u.dgr, c.at(u.dOut.off), nullptr, c.at(u.tmp.off), false);     // summed into the lower block's dOut by ITS reduction
+    exec_conv(c, u.dgr, conv_args(c.at(u.dOut.off), c.at(u.tmp.off)));     // summed into the lower block's dOut by ITS reduction
     (void)T;
 }
 
@@ -2519,7 +2493,7 @@ static int forward_snunet(stcd_engine& e, const float* x1, const float* x2, cons
     launch_ecam_forward(e.dt, c.at(e.snE.off), e.snE.ld, c.at(e.snZ.off), e.snZ.ld, e.B, (int64_t)e.H * e.W, c4, params + e.sn_w[0],
                         params + e.sn_w[1], params + e.sn_w[2], params + e.sn_w[3], c.at<float>(e.sn_pool), c.at<int64_t>(e.sn_argm),
                         c.at<float>(e.sn_att), c.at<float>(e.sn_hid), c.at<float>(e.sn_part), s);
-    exec_conv(c, e.sn_final_fwd, c.at(e.snZ.off), params + e.convs[e.sn_final].b_off, logits, true);
+    exec_conv(c, e.sn_final_fwd, conv_args(c.at(e.snZ.off), logits, params + e.convs[e.sn_final].b_off, true));
     STCD_HIP(hipGetLastError());
     return 0;
 }
@@ -2553,7 +2527,7 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
     } else {
         launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
         exec_wgrad(c, e.sn_final_wg, c.at(e.snZ.off), c.at(e.G.off));
-        exec_conv(c, e.sn_final_dgr, c.at(e.G.off), nullptr, c.at(e.sndZ.off), false);
+        exec_conv(c, e.sn_final_dgr, conv_args(c.at(e.G.off), c.at(e.sndZ.off)));
         launch_ecam_backward(dt, c.at(e.snE.off), e.snE.ld, c.at(e.sndZ.off), e.sndZ.ld, c.at(e.sndE.off), e.sndE.ld, B, (int64_t)e.H * e.W, c4,
                              params + e.sn_w[0], params + e.sn_w[1], params + e.sn_w[2], params + e.sn_w[3], grads + e.sn_w[0],
                              grads + e.sn_w[1], grads + e.sn_w[2], grads + e.sn_w[3], c.at<float>(e.sn_pool), c.at<int64_t>(e.sn_argm),
@@ -3042,29 +3016,20 @@ static void glayer_forward(const Ctx& c, GLayer& L, float* bn_running, bool trai
     const BnP& bn = e.bns[L.bn];
     const int64_t ppg = (int64_t)L.npg * L.Ho * L.Wo;
     float* stat = c.at<float>(L.stat);
-    int fused = 0;
-    if (L.kind == K_STEM7 && mfma_on(e) && L.fwd.gemm.ok && L.fwd.wf >= 0) {
-        ProfScope ps(c, PC_CONV, 2.0 * L.N * L.Ho * L.Wo * 49.0 * cv.cin * cv.cout, 0.0, "k_conv_gemm<stem>");
-        long long* sp = training ? c.at<long long>(L.facc) : nullptr;
-        if (launch_conv_gemm(L.fwd.g, L.fwd.plan, L.fwd.gemm, c.at(L.in.off), c.at(L.fwd.wf), nullptr, c.at(L.Y.off), L.groups, sp, L.C, c.s) != 0)
-            set_error("internal: k_conv_gemm<stem> rejected the stem it was bound for");
-        fused = sp ? 1 : 0;
-    } else if (L.kind == K_STEM7) {
+    long long* const facc = training ? c.at<long long>(L.facc) : nullptr;
+    bool fused = false;
+    if (L.kind == K_STEM7 && conv_on_ref(mfma_on(e), L.fwd)) {      // an unbound stem (Binder::stem): the dedicated fp32 kernel
         ProfScope ps(c, PC_CONV, 2.0 * L.N * L.Ho * L.Wo * 49.0 * cv.cin * cv.cout, 0.0, "k_stem_fwd");
         launch_stem_fwd(e.dt, c.at(L.in.off), c.params + cv.w_off, c.at(L.Y.off), L.N, L.Hi, L.Wi, cv.cin, cv.cout, c.s);
     } else {
-        StatReq sr; sr.acc = training ? c.at<long long>(L.facc) : nullptr; sr.groups = L.groups; sr.C = L.C;
-        exec_conv(c, L.fwd, c.at(L.in.off), nullptr, c.at(L.Y.off), false, &sr, &fused);
+        ConvArgs ca = conv_args(c.at(L.in.off), c.at(L.Y.off));
+        ca.sums.acc = facc; ca.sums.groups = L.groups; ca.sums.C = L.C;
+        fused = exec_conv(c, L.fwd, ca).sums;
     }
+    // (the separate pass carries no profile record here, so this is not exec_conv_stats)
+    if (facc && !fused) launch_bn_stats(e.dt, c.at(L.Y.off), L.Y.ld, L.C, L.groups, ppg, facc, c.s);
     BnActArgs a;
-    if (training) {
-        if (!fused) launch_bn_stats(e.dt, c.at(L.Y.off), L.Y.ld, L.C, L.groups, ppg, c.at<long long>(L.facc), c.s);
-        a.facc = c.at<long long>(L.facc); a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-        a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + L.C;
-    } else {      // eval: the activation kernel reads the running statistics itself
-        a.gamma = c.params + bn.g_off; a.beta = c.params + bn.b_off;
-        a.running_mean = bn_running + bn.run_off; a.running_var = bn_running + bn.run_off + L.C;
-    }
+    bn_fields(a, c, bn, L.C, bn_running, facc);
     a.Y = c.at(L.Y.off); a.ldy = L.Y.ld; a.A = c.at(L.A.off); a.lda = L.A.ld; a.a_group_off = ppg * L.A.ld;
     a.P = nullptr; a.ldp = 0; a.stat = stat; a.mask = nullptr;
     a.C = L.C; a.groups = L.groups; a.npg = L.npg; a.H = L.Ho; a.W = L.Wo; a.relu = L.relu ? 1 : 0;
@@ -3110,9 +3075,9 @@ static void glayer_backward(const Ctx& c, GLayer& L) {
         (void)hipMemsetAsync(c.at(L.dIn.off), 0, (size_t)L.N * L.Hi * L.Wi * L.dIn.ld * dsize(e.dt), c.s);
     if (L.ndgr == 4) {
         if (!exec_conv_x4(c, L.dgr, c.at(L.dA.off), nullptr, c.at(L.dIn.off)))
-            for (int ph = 0; ph < 4; ++ph) exec_conv(c, L.dgr[ph], c.at(L.dA.off), nullptr, c.at(L.dIn.off), false);
+            for (int ph = 0; ph < 4; ++ph) exec_conv(c, L.dgr[ph], conv_args(c.at(L.dA.off), c.at(L.dIn.off)));
     } else {
-        exec_conv(c, L.dgr[0], c.at(L.dA.off), nullptr, c.at(L.dIn.off), false);
+        exec_conv(c, L.dgr[0], conv_args(c.at(L.dA.off), c.at(L.dIn.off)));
     }
 }
 
@@ -3133,7 +3098,7 @@ static int forward_segcd(stcd_engine& e, const float* x1, const float* x2, const
             launch_fuse(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * hw * st.src.ld,
                         c.at<char>(st.src.off) + (int64_t)2 * st.N * hw * st.src.ld * T, st.src.ld, st.N, hw, st.C, s);
         } else if (st.kind == GS_BCONV)
-            exec_conv(c, e.g_pred_fwd, c.at(st.src.off), params + e.convs[e.g_pred_conv].b_off, c.at(st.dst.off), false);
+            exec_conv(c, e.g_pred_fwd, conv_args(c.at(st.src.off), c.at(st.dst.off), params + e.convs[e.g_pred_conv].b_off));
         else if (st.kind == GS_ABSPAIR) {
             ProfScope ps(c, PC_POOL_FUSE, 0.0, 3.0 * st.N * st.h * st.w * st.C * (double)T, "k_fuse");
             launch_fuse(dt, 0, c.at(st.src.off), st.src.ld, (int64_t)st.N * st.h * st.w * st.src.ld, c.at(st.dst.off), st.dst.ld, st.N,
@@ -3161,14 +3126,14 @@ static int forward_segcd(stcd_engine& e, const float* x1, const float* x2, const
         else launch_upsample2(dt, c.at(st.src.off), st.src.ld, c.at(st.dst.off), st.dst.ld, st.N, st.h, st.w, st.C, s);
     }
     if (e.seg_dates == 1 || e.bres) {      // UnetSeg: masks = head(decoder output); base_resnet: logits = classifier.3(classifier's ReLU)
-        exec_conv(c, e.g_head_fwd, c.at(e.gX3.off), params + e.convs[e.g_head_conv].b_off, logits, true);
+        exec_conv(c, e.g_head_fwd, conv_args(c.at(e.gX3.off), logits, params + e.convs[e.g_head_conv].b_off, true));
         STCD_HIP(hipGetLastError());
         return 0;
     }
     // head: X3[2B:3B] = |d1 - d2| ; raw = conv(X3) = [m1; m2; diffea] ; logits = [m1; m2; min(diffea, |m1 - m2|)]
     // (FFCTLCD: X3[2B:3B] is the decoder's output on |f1 - f2|, already in place)
     if (!e.seg_ffc) launch_fuse(dt, 0, c.at(e.gX3.off), 16, (int64_t)B * HW * 16, c.at<char>(e.gX3.off) + (int64_t)2 * B * HW * 16 * T, 16, B, HW, 16, s);
-    exec_conv(c, e.g_head_fwd, c.at(e.gX3.off), params + e.convs[e.g_head_conv].b_off, c.at(e.g_raw3), true);
+    exec_conv(c, e.g_head_fwd, conv_args(c.at(e.gX3.off), c.at(e.g_raw3), params + e.convs[e.g_head_conv].b_off, true));
     launch_segcd_combine(c.at<float>(e.g_raw3), logits, (int64_t)B * e.label * HW, s);
     STCD_HIP(hipGetLastError());
     return 0;
@@ -3185,12 +3150,12 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
     if (e.seg_dates == 1 || e.bres) {
         launch_gout_pack(dt, grad_logits, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
         exec_wgrad(c, e.g_head_wg, c.at(e.gX3.off), c.at(e.G.off));
-        exec_conv(c, e.g_head_dgr, c.at(e.G.off), nullptr, c.at(e.gdX3.off), false);
+        exec_conv(c, e.g_head_dgr, conv_args(c.at(e.G.off), c.at(e.gdX3.off)));
     } else {
         launch_segcd_combine_bwd(c.at<float>(e.g_raw3), grad_logits, c.at<float>(e.g_draw3), (int64_t)B * e.label * HW, s);
         launch_gout_pack(dt, c.at<float>(e.g_draw3), c.at(e.G.off), 3 * B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
         exec_wgrad(c, e.g_head_wg, c.at(e.gX3.off), c.at(e.G.off));
-        exec_conv(c, e.g_head_dgr, c.at(e.G.off), nullptr, c.at(e.gdX3.off), false);
+        exec_conv(c, e.g_head_dgr, conv_args(c.at(e.G.off), c.at(e.gdX3.off)));
         // d(d1), d(d2) += -/+ sign(d1 - d2) * d|d1 - d2| : written to a contribution buffer the last decoder layer gathers
         if (!e.seg_ffc) launch_fuse_bwd(dt, 0, c.at(e.gX3.off), 16, (int64_t)B * HW * 16, c.at<char>(e.gdX3.off) + (int64_t)2 * B * HW * 16 * T, 16,
                         c.at(e.gFuseTmp.off), 16, (int64_t)B * HW * 16, B, HW, 16, s);
@@ -3243,7 +3208,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
             launch_bias_grad(dt, c.at(st.ddst.off), st.ddst.ld, (int64_t)st.N * st.h * st.w, 32, grads + e.convs[e.g_pred_conv].b_off, s,
                              dt == BF16 ? c.at<long long>(e.g_pred_bias_acc) : nullptr); }
             exec_wgrad(c, e.g_pred_wg, c.at(st.src.off), c.at(st.ddst.off));
-            exec_conv(c, e.g_pred_dgr, c.at(st.ddst.off), nullptr, c.at(st.dsrc.off), false);
+            exec_conv(c, e.g_pred_dgr, conv_args(c.at(st.ddst.off), c.at(st.dsrc.off)));
         }
         else {      // max-pool: d(P0) = conv1 contribution (written in place) + identity-branch contribution of layer1.0 (its
                     // down-sample's data gradient for Bottleneck encoders, the gated residual gradient itself for BasicBlock ones)
@@ -3771,56 +3736,41 @@ int stcd_op_conv(int dtype, int impl, const stcd_conv_geom* g, const void* in, c
     STCD_CHECK(in && w && out, "null pointer argument");
     if (impl == 1 || impl == 2 || impl == 3 || impl == 6 || impl == 8) {
         STCD_CHECK(dtype == STCD_DTYPE_BF16, "the MFMA implementation is bf16 only");
-        ConvMfmaPlan p = conv_mfma_plan(*g);
+        ConvOp op;      // the planners' answers for this geometry
+        op.g = *g;
+        op.plan = conv_mfma_plan(*g);
+        const ConvMfmaPlan& p = op.plan;
         STCD_CHECK(p.ok, "geometry not supported by the MFMA kernel");
         STCD_CHECK(scratch && scratch_bytes >= p.wf_elems * 2, "scratch too small for the fragment-order filter");
         launch_pack_frag(*g, p, w, g->ci, g->co, scratch, (hipStream_t)hip_stream);
+        ConvArgs a;      // one group, no statistics, no epilogue, NHWC; the filter image is `scratch`
+        a.in = in; a.wf = scratch; a.bias = bias; a.out = out; a.s = (hipStream_t)hip_stream;
+        ConvKernel kern = ConvKernel::MFMA;      // impl 2
+        const char* const fail = impl == 2 ? "LDS budget exceeded" : impl == 1 ? "the chosen kernel rejected the geometry" : "launch failed";
         if (impl == 3) {      // resident-halo / streamed-filter kernel of the wide 3x3 layers (Ci % 64 == 0, Co % 128 == 0)
-            const ConvHaloPlan hp = conv_halo_plan(*g, p);
-            STCD_CHECK(hp.ok, "geometry not supported by the resident-halo kernel (3x3 stride 1, Ci % 64 == 0, Co % 128 == 0)");
-            STCD_CHECK(launch_conv_halo(*g, p, hp, in, scratch, bias, out, (hipStream_t)hip_stream) == 0, "launch failed");
-            STCD_HIP(hipGetLastError());
-            return 0;
-        }
-        if (impl == 6) {      // 256 x 256 implicit-GEMM tile staged by LDS-DMA (Ci % 64 == 0, Co % 256 == 0, an even number >= 4 of K-tiles)
-            const ConvDmaPlan dp = conv_dma_plan(*g, p);
-            STCD_CHECK(dp.ok, "geometry not supported by the LDS-DMA kernel (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
-            STCD_CHECK(launch_conv_dma(*g, p, dp, in, scratch, bias, out, (hipStream_t)hip_stream) == 0, "launch failed");
-            STCD_HIP(hipGetLastError());
-            return 0;
-        }
-        if (impl == 8) {      // k_conv_res's tile staged by LDS-DMA (3x3 stride 1, Ci % 64 == 0, Co % 16 == 0; the engine's choice on small maps)
-            const ConvTilePlan tp = conv_tile_plan(*g, p, 1);
-            STCD_CHECK(tp.ok, "geometry not supported by the LDS-DMA tile kernel (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
-            STCD_CHECK(launch_conv_tile(*g, p, tp, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream) == 0, "launch failed");
-            STCD_HIP(hipGetLastError());
-            return 0;
-        }
-        if (impl == 1) {
-            // the engine's plans and the engine's choice (one group, no statistics, no epilogue, NHWC) with a fresh engine's switches;
-            // the kernels with an impl number of their own (3 halo, 6 dma, 8 tile) stay behind those numbers
+            op.halo = conv_halo_plan(*g, p);
+            STCD_CHECK(op.halo.ok, "geometry not supported by the resident-halo kernel (3x3 stride 1, Ci % 64 == 0, Co % 128 == 0)");
+            kern = ConvKernel::HALO;
+        } else if (impl == 6) {      // 256 x 256 implicit-GEMM tile staged by LDS-DMA (Ci % 64 == 0, Co % 256 == 0, an even number >= 4 of K-tiles)
+            op.dma = conv_dma_plan(*g, p);
+            STCD_CHECK(op.dma.ok, "geometry not supported by the LDS-DMA kernel (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
+            kern = ConvKernel::DMA;
+        } else if (impl == 8) {      // k_conv_res's tile staged by LDS-DMA (3x3 stride 1, Ci % 64 == 0, Co % 16 == 0; the engine's choice on small maps)
+            op.tile = conv_tile_plan(*g, p, 1);
+            STCD_CHECK(op.tile.ok, "geometry not supported by the LDS-DMA tile kernel (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
+            kern = ConvKernel::TILE;
+        } else if (impl == 1) {
+            // the engine's plans and the engine's choice with a fresh engine's switches; the kernels with an impl number of their own
+            // (3 halo, 6 dma, 8 tile) stay behind those numbers
             stcd_engine sw;
             sw.dt = BF16;
             engine_env_switches(&sw);
-            ConvOp op;
-            op.g = *g;
             plan_conv(sw, op, 1, false);
-            op.wf = 0;      // (the image is `scratch`)
-            ConvCall call;
-            call.allowed = ~(conv_kernel_bit(ConvKernel::DMA) | conv_kernel_bit(ConvKernel::HALO) | conv_kernel_bit(ConvKernel::TILE));
-            int rc = 1;
-            switch (conv_kernel(true, sw.use_small, op, call)) {
-                case ConvKernel::SMALL: rc = launch_conv_small(*g, in, scratch, bias, out, false, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
-                case ConvKernel::RES: rc = launch_conv_res(*g, p, op.res, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
-                case ConvKernel::GEMM: rc = launch_conv_gemm(*g, p, op.gemm, in, scratch, bias, out, 1, nullptr, g->co, (hipStream_t)hip_stream); break;
-                case ConvKernel::MFMA: rc = launch_conv_mfma(*g, p, in, scratch, bias, out, false, (hipStream_t)hip_stream); break;
-                default: break;
-            }
-            STCD_CHECK(rc == 0, "the chosen kernel rejected the geometry");
-            STCD_HIP(hipGetLastError());
-            return 0;
+            op.wf = 0;      // (not the reference kernel's launch: there is an image)
+            kern = conv_kernel(true, sw.use_small, op, a,
+                               ~(conv_kernel_bit(ConvKernel::DMA) | conv_kernel_bit(ConvKernel::HALO) | conv_kernel_bit(ConvKernel::TILE)));
         }
-        STCD_CHECK(launch_conv_mfma(*g, p, in, scratch, bias, out, false, (hipStream_t)hip_stream) == 0, "LDS budget exceeded");
+        STCD_CHECK(launch_conv(kern, op, a) == 0, fail);
         STCD_HIP(hipGetLastError());
         return 0;
     }
@@ -3842,21 +3792,24 @@ int stcd_op_conv_fused(const stcd_conv_geom* g, stcd_conv_fused* f, const void* 
     STCD_CHECK(f->kernel >= STCD_CONV_SMALL && f->kernel <= STCD_CONV_DMA, "kernel must be one of STCD_CONV_*");
     const int groups = f->groups;
     STCD_CHECK(groups >= 1 && g->n % groups == 0, "groups must be >= 1 and divide n (whole images per BatchNorm group)");
+    static const ConvKernel OF_ID[] = {ConvKernel::SMALL, ConvKernel::RES, ConvKernel::TILE,      // STCD_CONV_* -> ConvKernel, here alone
+                                       ConvKernel::GEMM, ConvKernel::HALO, ConvKernel::DMA};
+    static_assert(STCD_CONV_SMALL == 0 && STCD_CONV_RES == 1 && STCD_CONV_TILE == 2 && STCD_CONV_GEMM == 3 && STCD_CONV_HALO == 4 && STCD_CONV_DMA == 5, "OF_ID");
+    const ConvKernel kern = OF_ID[f->kernel];
     const bool sums = f->sum_acc != nullptr, epi_on = f->use_epi != 0, bwd = f->bw_acc != nullptr;
-    const bool k_small = f->kernel == STCD_CONV_SMALL, k_res = f->kernel == STCD_CONV_RES, k_tile = f->kernel == STCD_CONV_TILE;
-    const bool k_gemm = f->kernel == STCD_CONV_GEMM, k_halo = f->kernel == STCD_CONV_HALO, k_dma = f->kernel == STCD_CONV_DMA;
-    STCD_CHECK(!sums || k_small || k_res || k_tile || k_gemm, "fused sums: k_conv_small, k_conv_res, k_conv_tile and k_conv_gemm only");
-    STCD_CHECK(!epi_on || k_gemm || k_halo || k_dma, "ConvEpi: k_conv_gemm, k_conv_halo and k_conv_dma only");
-    STCD_CHECK(!bwd || k_small || k_res, "BatchNorm-backward sums: k_conv_small and k_conv_res only");
-    STCD_CHECK(!(k_halo || k_dma) || groups == 1, "k_conv_halo and k_conv_dma know one group");
-    STCD_CHECK(!(bwd && sums), "a data gradient with BatchNorm-backward sums carries no forward sums");
+    ConvEpi epi;
+    BwdSum bs;
+    ConvArgs a;      // the filter image is `scratch`
+    a.in = in; a.wf = scratch; a.bias = bias; a.out = out; a.groups = groups; a.s = (hipStream_t)hip_stream;
+    if (sums) a.sums = StatReq{(long long*)f->sum_acc, groups, f->sum_c0, f->sum_c, f->sum_scale1, f->sum_scale2};
+    if (epi_on) a.epi = &epi;
+    if (bwd) a.bs = &bs;
+    const char* const refused = conv_refusal(kern, a, g->co);      // what the capability table says of this kernel
+    STCD_CHECK(!refused, std::string(conv_kernel_str(kern)) + " does not take " + (refused ? refused : ""));
     if (sums) {
         STCD_CHECK(f->sum_c0 >= 0 && f->sum_c >= 1 && f->sum_c0 + f->sum_c <= g->co, "the summed channel slice lies outside the output channels");
         STCD_CHECK(f->sum_scale1 > 0.f && f->sum_scale2 > 0.f, "the sum scales must be positive");
-        STCD_CHECK(!k_small || (f->sum_c0 == 0 && f->sum_c == g->co && f->sum_scale1 == BN_FS1 && f->sum_scale2 == BN_FS2),
-                   "k_conv_small sums all its channels at the BatchNorm scales (2^26, 2^18)");
     }
-    ConvEpi epi;
     if (epi_on) {
         STCD_CHECK(!f->gate || (f->ldg >= g->co && f->ldg % 8 == 0), "gate: the pixel stride must be a multiple of 8 and >= co");
         STCD_CHECK(!f->res || (f->ldr >= g->co && f->ldr % 8 == 0), "res: the pixel stride must be a multiple of 8 and >= co");
@@ -3864,58 +3817,48 @@ int stcd_op_conv_fused(const stcd_conv_geom* g, stcd_conv_fused* f, const void* 
         epi.relu = f->relu ? 1 : 0;
         epi.gate = f->gate; epi.ldg = f->ldg; epi.res = f->res; epi.ldr = f->ldr; epi.alpha = f->alpha; epi.beta = f->beta;
     }
-    BwdSum bs;
     if (bwd) {
         STCD_CHECK(f->bw_y && f->bw_stat, "BatchNorm-backward sums need the layer's conv output and its statistics");
         STCD_CHECK(f->bw_ldy >= g->co && f->bw_ldy % 4 == 0, "bw_y: the pixel stride must be a multiple of 4 and >= co");
         bs.Y = f->bw_y; bs.ldy = f->bw_ldy; bs.stat = f->bw_stat; bs.mask = f->bw_mask; bs.acc = (long long*)f->bw_acc; bs.groups = groups;
     }
-    const ConvMfmaPlan p = conv_mfma_plan(*g);
+    ConvOp op;      // the named kernel's own plan for the requested groups
+    op.g = *g;
+    op.plan = conv_mfma_plan(*g);
+    const ConvMfmaPlan& p = op.plan;
     STCD_CHECK(p.ok, "geometry not supported by the MFMA kernels");
     STCD_CHECK(scratch && scratch_bytes >= p.wf_elems * 2, "scratch too small for the fragment-order filter");
-    hipStream_t s = (hipStream_t)hip_stream;
-    long long* const acc = (long long*)f->sum_acc;
-    const int sC = sums ? f->sum_c : g->co, sc0 = sums ? f->sum_c0 : 0;
-    const float s1 = sums ? f->sum_scale1 : BN_FS1, s2 = sums ? f->sum_scale2 : BN_FS2;
     const int64_t tiles16 = (int64_t)g->n * ((g->hm + 15) / 16) * ((g->wm + 15) / 16);
-    ConvResPlan rp; ConvTilePlan tp; ConvGemmPlan gp; ConvHaloPlan hp; ConvDmaPlan dp;
-    if (k_small) {
+    if (kern == ConvKernel::SMALL) {
         STCD_CHECK(conv_small_ok(*g, p) && conv_small_call_ok(*g, groups, nullptr), "geometry not supported by k_conv_small (one n-tile, <= 5 k-steps)");
         STCD_CHECK(!bwd || conv_small_bwdsum_ok(*g), "k_conv_small forms BatchNorm-backward sums for 16 channels out, whole 8 x 16 tiles, 3 or 5 k-steps");
         f->blocks = conv_small_blocks(*g, groups);
         f->blocks_per_group = f->blocks / groups;
         f->tiles_per_group = (int)((int64_t)g->n * ((g->hm + 7) / 8) * ((g->wm + 15) / 16) / groups);
-    } else if (k_res) {
-        rp = conv_res_plan(*g, p, groups);
-        STCD_CHECK(rp.ok, "geometry not supported by k_conv_res (3x3 stride 1, Ci % 32 == 0)");
-        STCD_CHECK(!bwd || conv_res_bwdsum_ok(*g, rp), "this k_conv_res plan forms no BatchNorm-backward sums (slices of one or two n-tiles, double halo)");
-        f->blocks = rp.blocks; f->blocks_per_group = rp.P; f->tiles_per_group = (int)(tiles16 / groups);
-    } else if (k_tile) {
-        tp = conv_tile_plan(*g, p, groups);
-        STCD_CHECK(tp.ok, "geometry not supported by k_conv_tile (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
-        f->blocks = tp.blocks; f->blocks_per_group = tp.P; f->tiles_per_group = (int)(tiles16 / groups);
-    } else if (k_gemm) {
-        gp = conv_gemm_plan(*g, p, groups);
-        STCD_CHECK(gp.ok, "geometry not supported by k_conv_gemm (Ci % 64 == 0, Co % 64 == 0)");
-        f->blocks = gp.blocks; f->blocks_per_group = gp.tiles_m; f->tiles_per_group = gp.tiles_m; f->tile_m = 32 * gp.W;
-    } else if (k_halo) {
-        hp = conv_halo_plan(*g, p);
-        STCD_CHECK(hp.ok, "geometry not supported by k_conv_halo (3x3 stride 1, Ci % 128 == 0, Co % 128 == 0)");
-        f->blocks = hp.blocks; f->blocks_per_group = hp.P; f->tiles_per_group = (int)tiles16;
+    } else if (kern == ConvKernel::RES) {
+        op.res = conv_res_plan(*g, p, groups);
+        STCD_CHECK(op.res.ok, "geometry not supported by k_conv_res (3x3 stride 1, Ci % 32 == 0)");
+        STCD_CHECK(!bwd || conv_res_bwdsum_ok(*g, op.res), "this k_conv_res plan forms no BatchNorm-backward sums (slices of one or two n-tiles, double halo)");
+        f->blocks = op.res.blocks; f->blocks_per_group = op.res.P; f->tiles_per_group = (int)(tiles16 / groups);
+    } else if (kern == ConvKernel::TILE) {
+        op.tile = conv_tile_plan(*g, p, groups);
+        STCD_CHECK(op.tile.ok, "geometry not supported by k_conv_tile (3x3 stride 1 over the full map, Ci % 64 == 0, Co % 16 == 0)");
+        f->blocks = op.tile.blocks; f->blocks_per_group = op.tile.P; f->tiles_per_group = (int)(tiles16 / groups);
+    } else if (kern == ConvKernel::GEMM) {
+        op.gemm = conv_gemm_plan(*g, p, groups);
+        STCD_CHECK(op.gemm.ok, "geometry not supported by k_conv_gemm (Ci % 64 == 0, Co % 64 == 0)");
+        f->blocks = op.gemm.blocks; f->blocks_per_group = op.gemm.tiles_m; f->tiles_per_group = op.gemm.tiles_m; f->tile_m = 32 * op.gemm.W;
+    } else if (kern == ConvKernel::HALO) {
+        op.halo = conv_halo_plan(*g, p);
+        STCD_CHECK(op.halo.ok, "geometry not supported by k_conv_halo (3x3 stride 1, Ci % 128 == 0, Co % 128 == 0)");
+        f->blocks = op.halo.blocks; f->blocks_per_group = op.halo.P; f->tiles_per_group = (int)tiles16;
     } else {
-        dp = conv_dma_plan(*g, p);
-        STCD_CHECK(dp.ok, "geometry not supported by k_conv_dma (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
-        f->blocks = dp.blocks; f->blocks_per_group = std::min(dp.blocks, dp.tiles_m); f->tiles_per_group = dp.tiles_m;
+        op.dma = conv_dma_plan(*g, p);
+        STCD_CHECK(op.dma.ok, "geometry not supported by k_conv_dma (Ci % 64 == 0, Co % 256 == 0, (Ci / 64) * taps even and >= 4)");
+        f->blocks = op.dma.blocks; f->blocks_per_group = std::min(op.dma.blocks, op.dma.tiles_m); f->tiles_per_group = op.dma.tiles_m;
     }
-    launch_pack_frag(*g, p, w, g->ci, g->co, scratch, s);
-    int rc = 1;
-    if (k_small) rc = launch_conv_small(*g, in, scratch, bias, out, false, groups, acc, sC, s, nullptr, bwd ? &bs : nullptr);
-    else if (k_res) rc = launch_conv_res(*g, p, rp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2, nullptr, bwd ? &bs : nullptr);
-    else if (k_tile) rc = launch_conv_tile(*g, p, tp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2);
-    else if (k_gemm) rc = launch_conv_gemm(*g, p, gp, in, scratch, bias, out, groups, acc, sC, s, sc0, s1, s2, epi_on ? &epi : nullptr);
-    else if (k_halo) rc = launch_conv_halo(*g, p, hp, in, scratch, bias, out, s, epi_on ? &epi : nullptr);
-    else rc = launch_conv_dma(*g, p, dp, in, scratch, bias, out, s, epi_on ? &epi : nullptr);
-    STCD_CHECK(rc == 0, "the named kernel's launcher rejected the combination");
+    launch_pack_frag(*g, p, w, g->ci, g->co, scratch, a.s);
+    STCD_CHECK(launch_conv(kern, op, a) == 0, "the named kernel's launcher rejected the combination");
     STCD_HIP(hipGetLastError());
     return 0;
 }

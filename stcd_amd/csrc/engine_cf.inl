@@ -471,15 +471,15 @@ static int configure_cf(stcd_engine& e, int B, int H, int W) {
 }
 
 // ------------------------------------------------------------------------------------------------------------ execution
-static void cf_gemm_fwd(const Ctx& c, const CfGemm& G, const StatReq* sr = nullptr, int* fused = nullptr) {
+static void cf_gemm_fwd(const Ctx& c, const CfGemm& G) {
     const ConvW& cv = c.e.convs[G.conv];
-    exec_conv(c, G.fwd, c.at(G.x.off), cv.b_off >= 0 ? c.params + cv.b_off : nullptr, c.at(G.y.off), false, sr, fused);
+    exec_conv(c, G.fwd, conv_args(c.at(G.x.off), c.at(G.y.off), cv.b_off >= 0 ? c.params + cv.b_off : nullptr));
 }
 // weight gradient (grouped launch at the end of the stage), bias gradient, data gradient
 // (the bias gradient -- the column sums of dy -- runs in the stage's grouped launch: cf_colsum_stage)
 static void cf_gemm_bwd(const Ctx& c, const CfGemm& G) {
     exec_wgrad(c, G.wg, c.at(G.x.off), c.at(G.dy.off));
-    if (G.has_dgr) exec_conv(c, G.dgr, c.at(G.dy.off), nullptr, c.at(G.dx.off), false);
+    if (G.has_dgr) exec_conv(c, G.dgr, conv_args(c.at(G.dy.off), c.at(G.dx.off)));
 }
 static void cf_colsum_stage(const Ctx& c, int stage) {
     const CfPlan& P = *c.e.cf;
@@ -592,8 +592,7 @@ static void cf_bn_forward(const Ctx& c, const CfBN& bn, const TRef& z, const TRe
         launch_bn_stats_precise(e.dt, c.at(z.off), z.ld, ppg, bn.C, c.params + p.g_off, c.params + p.b_off, bn_running + p.run_off,
                                 bn_running + p.run_off + bn.C, c.at<float>(bn.stat), c.at<float>(e.cf->scratch), 0.1f, 1e-5f, c.s);
     } else {             // evaluation: the running statistics, read by the activation kernel itself
-        a.gamma = c.params + p.g_off; a.beta = c.params + p.b_off;
-        a.running_mean = bn_running + p.run_off; a.running_var = bn_running + p.run_off + bn.C;
+        bn_fields(a, c, p, bn.C, bn_running, nullptr);
     }
     ProfScope ps(c, PC_BN_ACT, 0.0, 2.0 * ppg * bn.C * (double)dsize(e.dt));
     launch_bn_act(e.dt, a, c.s);
@@ -610,22 +609,22 @@ static void cf_bn_backward(const Ctx& c, const CfBN& bn, const TRef& dout, const
 }
 
 static void cf_up_forward(const Ctx& c, const CfUp& U) {
-    for (int ph = 0; ph < 4; ++ph) exec_conv(c, U.fwd[ph], c.at(U.in.v.off), c.params + U.b_off, c.at(U.out.v.off), false);
+    for (int ph = 0; ph < 4; ++ph) exec_conv(c, U.fwd[ph], conv_args(c.at(U.in.v.off), c.at(U.out.v.off), c.params + U.b_off));
 }
 static void cf_up_backward(const Ctx& c, const CfUp& U) {
     stcd_engine& e = c.e;
     const int D = U.out.c;
     const int64_t rows_in = (int64_t)U.in.n * U.in.h * U.in.w;
     for (int ph = 0; ph < 4; ++ph) exec_wgrad(c, U.wg[ph], c.at(U.in.v.off), c.at(U.out.g.off));
-    exec_conv(c, U.dgr[0], c.at(U.out.g.off), nullptr, c.at(U.in.g.off), false);
-    exec_conv(c, U.dgr[1], c.at(U.out.g.off), nullptr, c.at(U.dtmp.off), false);
+    exec_conv(c, U.dgr[0], conv_args(c.at(U.out.g.off), c.at(U.in.g.off)));
+    exec_conv(c, U.dgr[1], conv_args(c.at(U.out.g.off), c.at(U.dtmp.off)));
     launch_axpby(e.dt, 1.f, c.at(U.in.g.off), U.in.g.ld, 1.f, c.at(U.dtmp.off), U.dtmp.ld, c.at(U.in.g.off), U.in.g.ld, rows_in, D, c.s);
 }
 // conv + fused epilogue where the kernel has one (k_conv_gemm), else conv then the same arithmetic element-wise
 static void cf_conv_epi(const Ctx& c, const ConvOp& op, const void* in, const float* bias, void* out, int ldo, const ConvEpi& ep, int64_t rows, int C) {
-    int fused = 0;
-    exec_conv(c, op, in, bias, out, false, nullptr, nullptr, &ep, &fused);
-    if (fused) return;
+    ConvArgs a = conv_args(in, out, bias);
+    a.epi = &ep;
+    if (exec_conv(c, op, a).epi) return;
     const int dt = c.e.dt;
     if (ep.relu) launch_relu(dt, out, ldo, out, ldo, rows, C, c.s);
     if (ep.gate) launch_relu_bwd(dt, out, ldo, ep.gate, ep.ldg, out, ldo, rows, C, c.s);
@@ -706,7 +705,7 @@ static int forward_cf(stcd_engine& e, const float* x1, const float* x2, const fl
         {
             const ConvW& c0 = e.convs[F.aux_conv0];
             const BnP& bp = e.bns[F.aux_bn];
-            exec_conv(c, F.aux_fwd, c.at(F.c.v.off), params + c0.b_off, c.at(F.aux_y), true);
+            exec_conv(c, F.aux_fwd, conv_args(c.at(F.c.v.off), c.at(F.aux_y), params + c0.b_off, true));
             launch_aux_head(c.at<float>(F.aux_y), logits + F.out_off, params + bp.g_off, params + bp.b_off, bn_running + bp.run_off,
                             bn_running + bp.run_off + bp.C, params + F.aux_w3, params + F.aux_b3, c.at<float>(F.aux_stat), B, e.label, F.h, F.w,
                             tr ? 1 : 0, s);
@@ -720,7 +719,7 @@ static int forward_cf(stcd_engine& e, const float* x1, const float* x2, const fl
     cf_res_forward(c, P.res2);
     cf_up_forward(c, P.up1);
     cf_res_forward(c, P.res1);
-    exec_conv(c, P.head_fwd, c.at(P.res1.out.v.off), params + e.convs[P.head_conv].b_off, logits + P.cp_off, true);
+    exec_conv(c, P.head_fwd, conv_args(c.at(P.res1.out.v.off), logits + P.cp_off, params + e.convs[P.head_conv].b_off, true));
     STCD_HIP(hipGetLastError());
     return 0;
 }
@@ -747,7 +746,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
         if (!mfma_on(e)) STCD_HIP(hipMemsetAsync(c.at(e.dwe_begin), 0, e.dwe_end - e.dwe_begin, s));
         launch_gout_pack(dt, grad_logits + P.cp_off, c.at(e.G.off), B, e.label, e.H, e.W, s, c.at<long long>(e.final_bias_acc));
         exec_wgrad(c, P.head_wg, c.at(P.res1.out.v.off), c.at(e.G.off));
-        exec_conv(c, P.head_dgr, c.at(e.G.off), nullptr, c.at(P.res1.out.g.off), false);
+        exec_conv(c, P.head_dgr, conv_args(c.at(e.G.off), c.at(P.res1.out.g.off)));
         cf_res_backward(c, P.res1);
         cf_up_backward(c, P.up1);
         cf_res_backward(c, P.res2);
@@ -770,7 +769,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
                                     grads + bp.b_off, B, e.label, F.h, F.w, s);
                 launch_gout_pack(dt, c.at<float>(F.aux_dy), c.at(F.aux_G), B, e.label, F.h, F.w, s, c.at<long long>(F.aux_bias_acc));
                 exec_wgrad(c, F.aux_wg, c.at(F.c.v.off), c.at(F.aux_G));
-                exec_conv(c, F.aux_dgr, c.at(F.aux_G), nullptr, c.at(F.aux_dtmp), false);
+                exec_conv(c, F.aux_dgr, conv_args(c.at(F.aux_G), c.at(F.aux_dtmp)));
                 launch_slice(dt, c.at(F.c.g.off), F.c.g.ld, c.at(F.aux_dtmp), D, rows, D, 1, s);
             }
             launch_dropout_ew(dt, c.at(F.c.g.off), F.c.g.ld, c.at(F.bb.g.off), D, rows, D, cf_site(e, F.site0 + 1, P.diff_drop, true), s);

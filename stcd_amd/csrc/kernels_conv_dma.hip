@@ -403,12 +403,12 @@ ConvDmaPlan conv_dma_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p) {
     return dp;
 }
 
-int launch_conv_dma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvDmaPlan& dp, const void* in, const void* wf,
-                    const float* bias, void* out, hipStream_t s, const ConvEpi* epi) {
+int launch_conv_dma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvDmaPlan& dp, const ConvArgs& c) {
     if (!dp.ok) return 1;
+    const ConvEpi* const epi = c.epi;
     ConvDmaArgs a;
     a.g = g;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf; a.bias = bias; a.out = (bf16*)out;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = (bf16*)c.out;
     a.NTtot = p.NTtot; a.nk = (g.ci / 64) * g.ntaps;
     a.lead = (unsigned)((3 * g.wi + 3) * g.ldi * 2);
     a.in_bytes = (unsigned)((int64_t)g.n * g.hi * g.wi * g.ldi * 2);
@@ -424,7 +424,7 @@ int launch_conv_dma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvDm
     a.alpha = epi ? epi->alpha : 1.f; a.beta = epi ? epi->beta : 1.f;
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_conv_dma, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    k_conv_dma<<<(unsigned)dp.blocks, 512, (size_t)dp.lds_bytes, s>>>(a);
+    k_conv_dma<<<(unsigned)dp.blocks, 512, (size_t)dp.lds_bytes, c.s>>>(a);
     return 0;
 }
 

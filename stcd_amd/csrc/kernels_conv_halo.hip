@@ -333,12 +333,12 @@ ConvHaloPlan conv_halo_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p) {
     return hp;
 }
 
-int launch_conv_halo(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvHaloPlan& hp, const void* in, const void* wf,
-                     const float* bias, void* out, hipStream_t s, const ConvEpi* epi) {
+int launch_conv_halo(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvHaloPlan& hp, const ConvArgs& c) {
     if (!hp.ok) return 1;
+    const ConvEpi* const epi = c.epi;
     ConvHaloArgs a;
     a.g = g;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf; a.bias = bias; a.out = (bf16*)out;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = (bf16*)c.out;
     a.NTtot = p.NTtot; a.nchunks = g.ci / 64;
     a.tiles_x = (g.wm + 15) / 16; a.tiles_y = (g.hm + 15) / 16; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     a.P = hp.P; a.nslices = hp.nslices;
@@ -350,7 +350,7 @@ int launch_conv_halo(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvH
     a.alpha = epi ? epi->alpha : 1.f; a.beta = epi ? epi->beta : 1.f;
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_conv_halo, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    k_conv_halo<<<(unsigned)hp.blocks, 256, (size_t)hp.lds_bytes, s>>>(a);
+    k_conv_halo<<<(unsigned)hp.blocks, 256, (size_t)hp.lds_bytes, c.s>>>(a);
     return 0;
 }
 

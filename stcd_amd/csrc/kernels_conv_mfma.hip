@@ -445,10 +445,10 @@ static size_t conv_mfma_args(const stcd_conv_geom& g, const ConvMfmaPlan& p, con
     return conv_mfma_lds(g, p);
 }
 
-int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const void* in, const void* wf, const float* bias,
-                     void* out, bool out_nchw, hipStream_t s) {
+int launch_conv_mfma(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvArgs& c) {
     ConvMfmaArgs a;
-    const size_t lds = conv_mfma_args(g, p, in, wf, bias, out, out_nchw, a);
+    const hipStream_t s = c.s;
+    const size_t lds = conv_mfma_args(g, p, c.in, c.wf, c.bias, c.out, c.nchw, a);
     if (lds > 160 * 1024) return 1;      // (conv_mfma_plan)
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * g.n), (unsigned)(p.NTtot / p.NT));
 #define LAUNCH_NT(N_)                                                                                             \
@@ -1443,12 +1443,16 @@ bool conv_small_call_ok(const stcd_conv_geom& g, int groups, const XfSrc* xf) {
     if (groups < 1 || g.n % groups != 0) return false;
     return !(xf && xf->on) || (xf->C == g.ci && xf->groups == groups);
 }
-int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_modeB, const float* bias, void* out,
-                      bool out_nchw, int groups, long long* stat_acc, int cpad, hipStream_t s, const XfSrc* xf, const BwdSum* bs) {
+int launch_conv_small(const stcd_conv_geom& g, const ConvArgs& c) {
+    const bool out_nchw = c.nchw;
+    const int groups = c.groups;
+    const XfSrc* const xf = c.xf;
+    const BwdSum* const bs = c.bs;
+    const hipStream_t s = c.s;
     ConvSmallArgs a;
     a.bw_Y = nullptr; a.bw_ldy = 0; a.bw_stat = nullptr; a.bw_mask = nullptr; a.s1_scale = BN_FS1; a.s2_scale = BN_FS2;
     a.g = g;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf_modeB; a.bias = bias; a.out = out; a.out_nchw = out_nchw ? 1 : 0;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = c.out; a.out_nchw = out_nchw ? 1 : 0;
     a.Ci = g.ci;
     a.KS = (g.ntaps * g.ci + 31) / 32;
     const int nt = (g.co + 15) / 16;
@@ -1462,8 +1466,8 @@ int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_mo
     a.ntiles = g.n * a.tiles_x * a.tiles_y;
     a.groups = groups;
     a.halo_bytes = (a.HH * a.HWp * g.ci * 2 + 255) & ~255;
-    a.stat_acc = stat_acc;
-    a.cpad = cpad;
+    a.stat_acc = c.sums.acc;      // (all channels at the BatchNorm scales: conv_caps)
+    a.cpad = c.sums.C;
     fill_taps(g, a.tap);
     if (!conv_small_call_ok(g, groups, xf)) return 1;
     const int blocks = conv_small_blocks(g, groups);
@@ -1474,7 +1478,7 @@ int launch_conv_small(const stcd_conv_geom& g, const void* in, const void* wf_mo
         lds = 2 * (size_t)a.halo_bytes + (size_t)xf->groups * 2 * xf->C * 4;
     }
     if (bs) {      // fused BatchNorm-backward sums: the tiles are partitioned by the DESTINATION layer's groups
-        if (!conv_small_bwdsum_ok(g) || out_nchw || use_xf || nt != 1 || stat_acc || bs->groups != groups || !bs->acc) return 1;
+        if (!conv_small_bwdsum_ok(g) || nt != 1 || bs->groups != groups || !bs->acc) return 1;
         a.bw_Y = (const bf16*)bs->Y; a.bw_ldy = bs->ldy; a.bw_stat = bs->stat; a.bw_mask = bs->mask;
         a.stat_acc = bs->acc; a.cpad = g.co; a.s1_scale = BN_BS; a.s2_scale = BN_BS;
         if (a.KS == 3) k_conv_small<1, 3, false, 2, true><<<blocks, 256, lds, s>>>(a);
@@ -1973,24 +1977,27 @@ bool conv_res_xf_ok(const stcd_conv_geom& g, const ConvResPlan& rp, int groups, 
     return rp.ok && !rp.single_halo && xf.C == g.ci && xf.groups == groups &&
            (size_t)rp.lds_bytes + (size_t)xf.groups * 2 * xf.C * 4 <= 160 * 1024;
 }
-int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvResPlan& rp, const void* in, const void* wf,
-                    const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0, float s1_scale,
-                    float s2_scale, const XfSrc* xf, const BwdSum* bs) {
+int launch_conv_res(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvResPlan& rp, const ConvArgs& c) {
     if (!rp.ok) return 1;
+    const int groups = c.groups;
+    const XfSrc* const xf = c.xf;
+    const BwdSum* const bs = c.bs;
+    const hipStream_t s = c.s;
+    StatReq sums = c.sums;
     ConvResArgs a;
     a.bw_Y = nullptr; a.bw_ldy = 0; a.bw_stat = nullptr; a.bw_mask = nullptr;
     if (bs) {
-        if (!conv_res_bwdsum_ok(g, rp) || stat_acc || (xf && xf->on) || bs->groups != groups || !bs->acc) return 1;
+        if (!conv_res_bwdsum_ok(g, rp) || bs->groups != groups || !bs->acc) return 1;
         a.bw_Y = (const bf16*)bs->Y; a.bw_ldy = bs->ldy; a.bw_stat = bs->stat; a.bw_mask = bs->mask;
-        stat_acc = bs->acc; cpad = g.co; stat_c0 = 0; s1_scale = BN_BS; s2_scale = BN_BS;
+        sums = StatReq{bs->acc, groups, 0, g.co, BN_BS, BN_BS};
     }
     a.g = g;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf; a.bias = bias; a.out = (bf16*)out;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = (bf16*)c.out;
     a.NTtot = p.NTtot; a.KSp = p.CiB / 32; a.nchunks = g.ci / 32;
     a.nslices = rp.nslices; a.P = rp.P; a.groups = groups;
     a.tiles_x = (g.wm + 15) / 16; a.tiles_y = (g.hm + 15) / 16; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     a.filt_bytes = rp.filt_bytes;
-    a.stat_acc = stat_acc; a.cpad = cpad; a.stat_c0 = stat_c0; a.s1_scale = s1_scale; a.s2_scale = s2_scale;
+    a.stat_acc = sums.acc; a.cpad = sums.C; a.stat_c0 = sums.c0; a.s1_scale = sums.s1; a.s2_scale = sums.s2;
     a.in_bytes = (unsigned)((int64_t)g.n * g.hi * g.wi * g.ldi * 2);
     for (int t = 0; t < 9; ++t) a.tix[g.dy[t] + 1][g.dx[t] + 1] = (int8_t)t;
     const bool use_xf = xf && xf->on;
@@ -2348,18 +2355,19 @@ ConvGemmPlan conv_gemm_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int 
     return gp;
 }
 
-int launch_conv_gemm(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvGemmPlan& gp, const void* in, const void* wf,
-                   const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0,
-                   float s1_scale, float s2_scale, const ConvEpi* epi) {
+int launch_conv_gemm(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvGemmPlan& gp, const ConvArgs& c) {
     if (!gp.ok) return 1;
+    const int groups = c.groups;
+    const hipStream_t s = c.s;
+    const ConvEpi* const epi = c.epi;
     ConvGemmArgs a;
     a.g = g;
     a.relu = epi ? epi->relu : 0;
     a.gate = epi ? (const bf16*)epi->gate : nullptr; a.ldg = epi ? epi->ldg : 0;
     a.res = epi ? (const bf16*)epi->res : nullptr; a.ldr = epi ? epi->ldr : 0;
     a.alpha = epi ? epi->alpha : 1.f; a.beta = epi ? epi->beta : 1.f;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf; a.bias = bias; a.out = (bf16*)out;
-    a.stat_acc = stat_acc; a.groups = groups; a.cpad = cpad; a.stat_c0 = stat_c0; a.s1_scale = s1_scale; a.s2_scale = s2_scale;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = (bf16*)c.out;
+    a.stat_acc = c.sums.acc; a.groups = groups; a.cpad = c.sums.C; a.stat_c0 = c.sums.c0; a.s1_scale = c.sums.s1; a.s2_scale = c.sums.s2;
     a.NTtot = p.NTtot; a.nsteps = (g.ci / 64) * g.ntaps;
     a.lead = (unsigned)((3 * g.wi + 3) * g.ldi * 2);
     a.pix_chunks = gp.pix_chunks;

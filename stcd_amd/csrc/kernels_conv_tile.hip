@@ -334,18 +334,18 @@ ConvTilePlan conv_tile_plan(const stcd_conv_geom& g, const ConvMfmaPlan& p, int 
     return tp;
 }
 
-int launch_conv_tile(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvTilePlan& tp, const void* in, const void* wf,
-                     const float* bias, void* out, int groups, long long* stat_acc, int cpad, hipStream_t s, int stat_c0, float s1_scale,
-                     float s2_scale) {
+int launch_conv_tile(const stcd_conv_geom& g, const ConvMfmaPlan& p, const ConvTilePlan& tp, const ConvArgs& c) {
+    const int groups = c.groups;
+    const hipStream_t s = c.s;
     if (!tp.ok || groups < 1 || tp.blocks != tp.P * tp.nslices * groups) return 1;
     ConvTileArgs a;
     a.g = g;
-    a.in = (const bf16*)in; a.wf = (const bf16*)wf; a.bias = bias; a.out = (bf16*)out;
+    a.in = (const bf16*)c.in; a.wf = (const bf16*)c.wf; a.bias = c.bias; a.out = (bf16*)c.out;
     a.NTtot = p.NTtot; a.nparts = tp.nparts; a.nbuf = tp.nbuf;
     a.nslices = tp.nslices; a.P = tp.P; a.groups = groups;
     a.tiles_x = (g.wm + 15) / 16; a.tiles_y = (g.hm + 15) / 16; a.ntiles = g.n * a.tiles_x * a.tiles_y;
     a.filt_bytes = tp.filt_bytes;
-    a.stat_acc = stat_acc; a.cpad = cpad; a.stat_c0 = stat_c0; a.s1_scale = s1_scale; a.s2_scale = s2_scale;
+    a.stat_acc = c.sums.acc; a.cpad = c.sums.C; a.stat_c0 = c.sums.c0; a.s1_scale = c.sums.s1; a.s2_scale = c.sums.s2;
     a.in_bytes = (unsigned)((int64_t)g.n * g.hi * g.wi * g.ldi * 2);
     a.wf_bytes = (unsigned)(p.wf_elems * 2);
     a.out_bytes = (unsigned)((int64_t)g.n * g.ho * g.wo * g.ldo * 2);

@@ -255,24 +255,32 @@ def test_bwdsum_exact(c):
 def _reject_cases():
     small, res, tile = S.Case(S.SMALL, 2, 16, 16, 16, 16, 2), S.Case(S.RES, 2, 16, 16, 32, 32, 2), S.Case(S.TILE, 2, 16, 16, 64, 64, 2)
     halo, dma = S.Case(S.HALO, 1, 16, 16, 128, 128), S.Case(S.DMA, 1, 16, 16, 128, 256)
+    gemm = S.Case(S.GEMM, 2, 16, 16, 64, 64, 2, taps=S.TAP1)
+    # (two groups need two images: the one-image halo / dma shapes would be refused for n % groups, not for the kernel)
+    halo2, dma2 = S.Case(S.HALO, 2, 16, 16, 128, 128, 2), S.Case(S.DMA, 2, 16, 16, 128, 256, 2)
     return [("sums-on-halo", halo, "sums"), ("sums-on-dma", dma, "sums"),
             ("bwdsum-on-ragged-small", S.Case(S.SMALL, 2, 20, 18, 16, 16, 2), "bwd"),
             ("n-not-divisible-by-groups", S.Case(S.RES, 3, 16, 16, 32, 32, 2), "plain"),
-            ("epilogue-on-small", small, "epi"), ("epilogue-on-res", res, "epi"), ("epilogue-on-tile", tile, "epi")]
+            ("epilogue-on-small", small, "epi"), ("epilogue-on-res", res, "epi"), ("epilogue-on-tile", tile, "epi"),
+            # the rest of what the capability table (conv_caps, common.h) refuses
+            ("bwdsum-on-tile", tile, "bwd"), ("bwdsum-on-gemm", gemm, "bwd"), ("bwdsum-on-halo", halo, "bwd"), ("bwdsum-on-dma", dma, "bwd"),
+            ("two-groups-on-halo", halo2, "plain"), ("two-groups-on-dma", dma2, "plain"),
+            ("bwdsum-with-sums-on-small", small, "bwd+sums"), ("bwdsum-with-sums-on-res", res, "bwd+sums"),
+            ("slice-sums-on-small", S.Case(S.SMALL, 2, 16, 16, 16, 16, 2, c0=8, C=8), "sums")]
 
 
 @pytest.mark.parametrize("name,c,what", _reject_cases(), ids=lambda v: v if isinstance(v, str) else "")
 def test_unsupported_combinations_are_refused(name, c, what):
     x, w, b, _ = shared(c)
-    acc = Acc(8, c.groups, c.co)
+    acc, bacc = Acc(8, c.groups, c.nsum), Acc(8, c.groups, c.co)
     kw = {}
-    if what == "sums":
-        kw["acc"] = acc
-    elif what == "epi":
+    if "sums" in what:
+        kw.update(acc=acc, c0=c.c0)
+    if what == "epi":
         kw["relu"] = 1
-    elif what == "bwd":
+    if "bwd" in what:
         Y, stat, mask = (t.to(DEV) if t is not None else None for t in S.bwd_operands(c))
-        kw["bwd"] = dict(Y=Y, stat=stat, mask=mask, acc=acc)
+        kw["bwd"] = dict(Y=Y, stat=stat, mask=mask, acc=bacc)
     out, f, rc, msg = launch(c, x, w, b, expect_fail=True, **kw)
     assert rc != 0 and "stcd_op_conv_fused" in msg and len(msg) > 30, (rc, msg)
-    assert bool((out == PREFILL).all()) and acc.untouched(), "a refused request launched something"
+    assert bool((out == PREFILL).all()) and acc.untouched() and bacc.untouched(), "a refused request launched something"
