@@ -497,9 +497,6 @@ struct WgradJob {
 // one-tap weight gradients with Ci, Co >= 64 (1x1 convs, the phases of 2x2 stride-2 transposed convs): dW = X^T . dY as a GEMM
 // over positions, 128x128 / 64x64 channel tiles, positions split over gx blocks that each write one fp32 slab
 WgradMfmaPlan wgrad_gemm_plan(const stcd_conv_geom& g, int kpad, int wld);
-WgradJob wgrad_gemm_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
-                             int kpad, int wld);
-int launch_wgrad_gemm_group(int W, const WgradJob* jobs_dev, int njobs, int total_blocks, const char* base, hipStream_t s);
 // weight gradient of wide stride-1 tap-list layers (Ci % 256 == 0, Co % 256 == 0, maps >= 64 wide) on the LDS-DMA pipeline
 // (kernels_wgrad_dma.hip): block = (position split, tap, 256 x 256 channel tile); S splits -> S slabs [tap][ci][co]
 WgradMfmaPlan wgrad_dma_plan(const stcd_conv_geom& g, int kpad, int wld);
@@ -507,12 +504,24 @@ void wgrad_dma_set_split(WgradMfmaPlan& p, const stcd_conv_geom& g, int S, int k
 WgradJob wgrad_dma_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
                             int kpad, int wld);
 int launch_wgrad_dma_group(const WgradJob* jobs_dev, int njobs, int total_blocks, const char* base, hipStream_t s);
-WgradJob wgrad_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
-                        int kpad, int wld);
-void wgrad_job_set_xf(WgradJob& a, int64_t stat_off, int64_t mask_off, int C, int groups, int npg);
-int wgrad_variant_slots(int WCI, int NTW, bool t9, int lds_bytes);   // resident blocks of that kernel variant on the chip
-int launch_wgrad_group(int WCI, int NTW, bool t9, const WgradJob* jobs_dev, int njobs, int total_blocks, int lds_bytes,
-                       const char* base, hipStream_t s, bool xf = false);
+// Which kernel a weight-gradient launch runs on: derived by wgrad_kernel_of alone, read by the four functions after it (all next to
+// the tile and GEMM kernels, kernels_conv_mfma.hip).  Launches of one backward stage with equal kernels share one grouped grid.
+struct WgradKernel {
+    enum Kind { TILE, GEMM, DMA } kind = TILE;
+    int WCI = 0, NTW = 0; bool t9 = false, xf = false;      // TILE: k_wgrad_group<WCI, NTW, t9, xf>; ungrouped k_wgrad_mfma<WCI, NTW, t9>
+    int W = 0;                                              // GEMM: k_wgrad_gemm<W>.  DMA: k_wgrad_dma, no parameters
+    bool operator==(const WgradKernel& o) const { return kind == o.kind && WCI == o.WCI && NTW == o.NTW && t9 == o.t9 && xf == o.xf && W == o.W; }
+};
+// X of a job is the producer's raw conv output (virtual activation): its published table, masks and BatchNorm groups (WgradJob::xf_*)
+struct WgradXf { int64_t stat_off = -1, mask_off = -1; int C = 0, groups = 1, npg = 1; };
+WgradKernel wgrad_kernel_of(const WgradMfmaPlan& p, const stcd_conv_geom& g, bool xf);      // xf: asked for; only TILE keeps it
+bool wgrad_kernel_takes_xf(const WgradKernel& k);                        // false: launch_wgrad_jobs refuses it
+void wgrad_kernel_name(const WgradKernel& k, bool grouped, char out[64]);      // as the profile reports it
+int wgrad_variant_slots(const WgradKernel& k, int lds_bytes);            // resident blocks of a TILE kernel on the chip
+WgradJob wgrad_job(const WgradKernel& k, const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off,
+                   int64_t slab_off, int kpad, int wld, const WgradXf* xf = nullptr);      // xf: read when k.xf
+int launch_wgrad_jobs(const WgradKernel& k, const WgradJob* jobs_dev, int njobs, int total_blocks, int lds_bytes, const char* base,
+                      hipStream_t s);
 struct PackSpec;
 // Batched slab reduction: ONE launch per backward stage sums every weight-gradient launch's K-split slabs straight
 // into the reference-layout gradient tensors (device job table built at configure time).

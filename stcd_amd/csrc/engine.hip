@@ -71,23 +71,26 @@ struct WgradOp {
     int64_t slab = -1;                   // this launch's own K-split slabs (reduced in one batched launch per stage)
     int stage = 0;
     int64_t in_off = -1, dout_off = -1;  // workspace offsets of X and dY (grouped launch at the end of the stage)
-    bool grouped = false;
-    int group = -1;                      // index of its WgradGroup inside e.wgroups[stage]
-    // X is a virtual activation (the producer's raw conv output, transformed while staged: XfSrc / wgrad_job_set_xf); xf_C == 0: plain
-    int64_t xf_stat_off = -1, xf_mask_off = -1; int xf_C = 0, xf_groups = 1, xf_npg = 1;
+    int group = -1;                      // index of its WgradGroup inside e.wgroups[stage] (form_wgroups); -1: a launch of its own
+    WgradXf xf;                          // X is a virtual activation (the producer's raw conv output, transformed while staged: XfSrc); xf.C == 0: plain
     bool own_taps = false;               // filter taps (ky, kx) of this launch given here instead of conv.fwd.ky/kx[tap0 + t]
     int8_t oky[9] = {0}, okx[9] = {0};   // (the 7x7 stem: 49 taps spread over 7 launches)
 };
-struct WgradGroup {                      // all launches of one kernel variant in one backward stage
-    int WCI = 1, NTW = 1; bool t9 = false;
-    bool xf = false;                     // its jobs stage X through the virtual-activation transform (k_wgrad_group<.., XF = true>)
-    int gemm = 0;                        // > 0: k_wgrad_gemm<gemm> group (one-tap launches; WCI / NTW / t9 unused)
-    int dma = 0;                         // 1: k_wgrad_dma group (256 x 256 channel tiles, LDS-DMA staging; splits chosen for the group)
+struct WgradGroup {                      // all launches of one kernel in one backward stage
+    WgradKernel kernel;
     std::vector<WgradJob> jobs;
     int total_blocks = 0, lds_bytes = 0;
     int64_t table_off = -1;
     double flops = 0.0, bytes = 0.0;
-    int seen = 0; bool launched = false;  // run time: members whose operands exist so far in this backward; the grid went out
+};
+// What a backward call changes on the weight-gradient path; the plan above is read-only after configure.  WgradScope resets it.
+struct WgradRun {
+    struct Group { int seen = 0; bool launched = false; };      // members whose operands exist so far; the group's grid went out
+    std::vector<Group> groups[2];        // per stage, as e.wgroups (sized by build_wgrad_jobs: a step allocates nothing)
+    bool early = false;                  // exec_wgrad sends a group out with its last member
+    hipStream_t side = nullptr;          // ... on this stream, when there is one
+    bool rj_early_done = false, final_on_main = false;      // stage 1's split reduce table (rj_split)
+    bool failed = false;                 // a launch of this path was refused or a HIP call failed (set_error has the text): stage_tail returns 1
 };
 
 struct Cbrd {                         // conv -> BN -> ReLU -> Dropout2d [-> pool]
@@ -288,7 +291,7 @@ struct stcd_engine_impl {
     const WgradOp* wg_last_op = nullptr;
     int rj_split = 0, wg_final_group = -1;
     int64_t rj_total_early = 0, rj_total_final = 0;
-    bool rj_early_done = false, wg_final_on_main = false;      // run time, per backward
+    WgradRun wrun;
     int last_tail = 0;      // what the last stage-1 tail found: bit 0 the early part was reduced behind its groups, bit 1 the final group ran on the caller's stream
     // batched filter repacking: [0] = forward-only job list (eval), [1] = forward + data-gradient filters (training)
     std::vector<PackJob> jobs[2];
@@ -309,8 +312,7 @@ struct stcd_engine_impl {
     // chain's blocks find free slots (wgrad_side_stream)
     int wg_side_on = 1;
     static constexpr int WG_SIDE_DIV = 4;                // share of the planner's block budget for stage 0's grouped grids: 1 / div
-    static constexpr int WGROUP_ROUNDS = 1, WGROUP_MIN_TILES = 8;      // build_pack_jobs: resident rounds of a group's blocks, fewest tiles per block
-    bool wg_early = false; hipStream_t wg_cur_side = nullptr;      // set by backward_fcsiam for the duration of a call (exec_wgrad)
+    static constexpr int WGROUP_ROUNDS = 1, WGROUP_MIN_TILES = 8;      // split_tile_group: resident rounds of a group's blocks, fewest tiles per block
     hipStream_t wg_side = nullptr; hipEvent_t wg_fork = nullptr, wg_join = nullptr; int wg_side_dev = -1;
 };
 
@@ -518,7 +520,8 @@ static void build_fcsiam_tables(stcd_engine& e) {
 
 // ------------------------------------------------------------------------------------------ workspace plan
 struct Planner;
-static void build_pack_jobs(stcd_engine& e, Planner& ws);
+static void build_wgrad_jobs(stcd_engine& e, Planner& ws);
+static void build_filter_pack_jobs(stcd_engine& e, Planner& ws);
 // The workspace planner every configure_* builds its plan with: a bump allocator over the caller's workspace (256-byte slices, in
 // the order of the calls -- each family keeps its own sequence), the named tensors of the test introspection, the bias jobs and
 // the tail all four families share.
@@ -553,7 +556,8 @@ struct Planner {
     // the tail of every plan: the bias-job table, then the slab / reduce / weight-gradient / repack job tables
     void tables() {
         e.bias_jobs_off = take((int64_t)e.bias_jobs.size() * sizeof(BiasJob) + 16);
-        build_pack_jobs(e, *this);
+        build_wgrad_jobs(e, *this);
+        build_filter_pack_jobs(e, *this);
         e.jobs_uploaded_ws = nullptr;
     }
 };
@@ -700,7 +704,7 @@ static void plan_conv(const stcd_engine& e, ConvOp& op, int groups, bool with_ti
     pick_gemm_or_res(e, op, op.g, groups);
     if (with_tile) pick_tile(e, op, op.g, groups);
 }
-// the launches of the reference kernel: no bf16 MFMA plan, or no fragment image.  build_pack_jobs packs the fp32 filter image for
+// the launches of the reference kernel: no bf16 MFMA plan, or no fragment image.  build_filter_pack_jobs packs the fp32 filter image for
 // exactly these, and conv_kernel sends exactly these there.
 static bool conv_on_ref(bool mfma, const ConvOp& op) { return !(mfma && op.plan.ok && op.wf >= 0); }
 // ---- the binder: every conv-shaped launch and every weight gradient of every family is bound here, at configure time.  Both start
@@ -756,178 +760,188 @@ static void take_ref_images(stcd_engine& e, Planner& ws, bool with_dwe = true) {
     e.dwe_end = ws.cur;
 }
 
-// the grouped launch a weight gradient belongs to: same kernel variant (one LDS-DMA group per stage, whatever the tap count)
-static bool same_group(const WgradGroup& G, const WgradOp& op) {
-    const bool t9 = !op.plan.dma && op.g.ntaps == 9;
-    return G.gemm == op.plan.gemm && G.dma == op.plan.dma && G.WCI == op.plan.WCI && G.NTW == op.plan.NTW && G.t9 == t9 && G.xf == (op.xf_C > 0);
-}
 
 // STCD_CF_SIDE=0: ChangeFormer's single-call backward keeps its grouped weight gradients on the caller's stream
 static bool cf_side_on() { static const bool on = env_flag("STCD_CF_SIDE", true); return on; }
 
-static void build_pack_jobs(stcd_engine& e, Planner& ws) {
-    // ---- per-launch slab regions + the batched reduce job tables (MFMA path only)
-    for (int st = 0; st < 2; ++st) { e.rjobs[st].clear(); e.rjobs_total[st] = 0; }
-    for (int st = 0; st < 2; ++st) e.wgroups[st].clear();
-    e.rj_split = 0; e.wg_final_group = -1; e.rj_early_done = false; e.wg_final_on_main = false;
+// ---- the weight-gradient plan of a configure (build_wgrad_jobs): groups, their K splits, slabs and job tables, reduce tables
+// floats of ONE K-split slab of a launch, [tap][kpad][wld]
+static int64_t wgrad_slab_floats(const stcd_engine& e, const WgradOp& op) { return (int64_t)op.g.ntaps * e.convs[op.conv].fwd.kpad * e.convs[op.conv].fwd.wld; }
+// the 8 x 16-position tiles the tile kernel walks
+static int64_t wgrad_ntiles(const stcd_conv_geom& g) { return (int64_t)g.n * ((g.wm + 15) / 16) * ((g.hm + 7) / 8); }
+// the filter taps (ky, kx) a launch forms: its own table, or its part of the conv's
+static void wgrad_taps(const stcd_engine& e, const WgradOp& op, int8_t* ky, int8_t* kx) {
+    const PackSpec& f = e.convs[op.conv].fwd;
+    for (int t = 0; t < op.g.ntaps; ++t) {
+        ky[t] = op.own_taps ? op.oky[t] : f.ky[op.tap0 + t];
+        kx[t] = op.own_taps ? op.okx[t] : f.kx[op.tap0 + t];
+    }
+}
+static WgradJob wgrad_job_of(const stcd_engine& e, const WgradKernel& k, const WgradOp& op, int64_t in_off, int64_t dout_off, int64_t slab_off) {
+    const PackSpec& f = e.convs[op.conv].fwd;
+    return wgrad_job(k, op.g, op.plan, in_off, dout_off, slab_off, f.kpad, f.wld, &op.xf);
+}
+
+// step 1: one group per (stage, kernel); every launch with a plan joins the group of its kernel
+static void form_wgroups(stcd_engine& e) {
+    for (WgradOp* op : e.wgrad_ops) {
+        if (!op->plan.ok) continue;
+        const WgradKernel k = wgrad_kernel_of(op->plan, op->g, op->xf.C > 0);
+        std::vector<WgradGroup>& gs = e.wgroups[op->stage];
+        size_t gi = 0;
+        while (gi < gs.size() && !(gs[gi].kernel == k)) ++gi;
+        if (gi == gs.size()) { gs.emplace_back(); gs.back().kernel = k; }
+        op->group = (int)gi;
+    }
+}
+
+// step 2: the K split (gx) of every member, chosen for the GROUP; one function per kind
+// one block per CU and ONE round: the smallest split length (in 64-position K-tiles) whose blocks -- (split, tap, channel tile) over all
+// layers of the group -- fit the 256 CUs; every block then walks about the same K
+static void split_dma_group(const stcd_engine& e, const std::vector<WgradOp*>& ops) {
+    auto positions = [](const WgradOp* op) { return (int64_t)op->g.n * op->g.hi * op->g.wi; };
+    auto blocks_at = [&](int64_t kt) {
+        int64_t b = 0;
+        for (const WgradOp* op : ops) b += ((positions(op) + kt * 64 - 1) / (kt * 64)) * op->plan.gy * op->plan.gz;
+        return b;
+    };
+    int64_t lo = 1, hi = 1;
+    // (fewer than one block per CU leaves whole CUs to the kernels of the backward chain the group runs beside -- its
+    //  blocks fill the register file of the CUs they sit on)
+    // 192 when the group runs on the side stream (single-call backwards): measured 26.9 -> 26.3 ms; 256 gains nothing there
+    const int dma_blocks = e.wg_side_on && cf_side_on() ? 192 : 256;
+    while (blocks_at(hi) > dma_blocks) hi *= 2;
+    while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (blocks_at(mid) <= dma_blocks) hi = mid; else lo = mid + 1; }
+    for (WgradOp* op : ops) {
+        const PackSpec& f = e.convs[op->conv].fwd;
+        int64_t S = (positions(op) + lo * 64 - 1) / (lo * 64);
+        S = std::min<int64_t>(S, std::max<int64_t>(1, ((int64_t)64 << 20) / (wgrad_slab_floats(e, *op) * 4)));
+        wgrad_dma_set_split(op->plan, op->g, (int)S, f.kpad, f.wld);
+    }
+}
+// about WGROUP_ROUNDS resident rounds of blocks over all the group's layers, each block owning at least WGROUP_MIN_TILES tiles, so
+// deep layers get few slabs and the prologue / slab epilogue is amortised
+static void split_tile_group(const stcd_engine& e, int stage, const WgradGroup& G, const std::vector<WgradOp*>& ops) {
+    int64_t W = 0;
+    for (const WgradOp* op : ops) W += wgrad_ntiles(op->g) * op->plan.gy * op->plan.gz;
+    int slots = wgrad_variant_slots(G.kernel, G.lds_bytes);
+    // stage 0 of the FC-Siam family runs beside stage 1's chain on a side stream: its grids leave room for the chain's blocks
+    // (stage 1's groups keep the full budget: half cost 2 %, a quarter 7 %)
+    if (stage == 0 && e.wg_side_on && fc_family(e)) slots = std::max(64, slots / stcd_engine_impl::WG_SIDE_DIV);
+    const int64_t rounds = stcd_engine_impl::WGROUP_ROUNDS;
+    const int64_t tpb = std::max<int64_t>(stcd_engine_impl::WGROUP_MIN_TILES, (W + rounds * slots - 1) / (rounds * slots));
+    for (WgradOp* op : ops) {
+        const int64_t slab = wgrad_slab_floats(e, *op);
+        int64_t gx = std::max<int64_t>(1, (wgrad_ntiles(op->g) + tpb - 1) / tpb);
+        gx = std::min<int64_t>(gx, std::max<int64_t>(1, ((int64_t)32 << 20) / (slab * 4)));
+        op->plan.gx = (int)gx;
+        op->plan.slab_floats = gx * slab;
+    }
+}
+static void choose_wgroup_splits(stcd_engine& e) {
+    for (int st = 0; st < 2; ++st)
+        for (size_t gi = 0; gi < e.wgroups[st].size(); ++gi) {
+            WgradGroup& G = e.wgroups[st][gi];
+            std::vector<WgradOp*> ops;      // its members, in wgrad_ops order
+            for (WgradOp* op : e.wgrad_ops)
+                if (op->stage == st && op->group == (int)gi) ops.push_back(op);
+            for (const WgradOp* op : ops)      // LDS need of the group = max over its jobs
+                G.lds_bytes = std::max(G.lds_bytes, wgrad_job_of(e, G.kernel, *op, 0, 0, 0).lds_bytes);
+            if (G.kernel.kind == WgradKernel::DMA) split_dma_group(e, ops);
+            else if (G.kernel.kind == WgradKernel::TILE) split_tile_group(e, st, G, ops);      // (GEMM: gx is fixed by wgrad_gemm_plan)
+        }
+}
+
+// step 3: every launch's slabs, in wgrad_ops order, and the job of every grouped launch in its group's table
+static void take_wgrad_slabs(stcd_engine& e, Planner& ws) {
+    for (WgradOp* op : e.wgrad_ops) {
+        if (!op->plan.ok) continue;
+        op->slab = ws.take(op->plan.slab_floats * 4);
+        if (op->group < 0) continue;
+        WgradGroup& G = e.wgroups[op->stage][op->group];
+        WgradJob j = wgrad_job_of(e, G.kernel, *op, op->in_off, op->dout_off, op->slab);
+        j.start = G.total_blocks;
+        G.total_blocks += j.gx * j.gy * j.gz;
+        G.jobs.push_back(j);
+        double fl, by;
+        conv_work(e, op->g, op->kreal, op->nreal, &fl, &by);
+        G.flops += fl; G.bytes += by;
+    }
+}
+
+// step 4: the slab sum of one launch (its `start` is the table's to set), and the table of each stage
+static ReduceJob reduce_job_of(const stcd_engine& e, const WgradOp& op) {
+    const ConvW& cv = e.convs[op.conv];
+    ReduceJob j{};
+    j.slab_off = op.slab; j.out_off = cv.w_off;
+    j.slab_stride = wgrad_slab_floats(e, op);
+    j.gx = op.plan.gx; j.ntaps = op.g.ntaps; j.K = cv.cin; j.N = cv.cout; j.kpad = cv.fwd.kpad; j.wld = cv.fwd.wld;
+    j.ks = cv.fwd.ks; j.kn_major = cv.fwd.kn_major;
+    wgrad_taps(e, op, j.ky, j.kx);
+    j.tiled = (int64_t)j.ntaps * j.K * j.N >= 512 * 1024;     // measured: the tiled form pays from ~0.5 M weights per launch
+    if (!j.tiled) {   // index space: blocks of (256 / parts) outputs x parts threads; <= 32 slabs per part where 64 parts allow
+        const int64_t outs = (int64_t)j.ntaps * j.K * j.N;
+        int parts = 1;
+        while (parts < 64 && parts * 32 < j.gx) parts *= 2;
+        j.parts = (int8_t)parts;
+        const int64_t OUTS = 256 / parts;
+        j.count = ((outs + OUTS - 1) / OUTS) * 256;
+    } else {   // index space: one block (256 threads) per tile of 32 co x TK ci x taps, all slabs (>= 0.5 M weights: the 32 / 64 MB
+        const int TK = j.ntaps == 1 ? 32 : 16;                 // slab caps leave <= 32 of them): see k_reduce_jobs
+        const int64_t ntiles = (int64_t)((j.N + 31) / 32) * ((j.K + TK - 1) / TK);
+        j.parts = 1;
+        j.count = ntiles * 256;
+    }
+    return j;
+}
+static int64_t append_reduce_job(std::vector<ReduceJob>& table, int64_t total, ReduceJob j) {
+    j.start = total;
+    table.push_back(j);
+    return total + ((j.count + 255) & ~(int64_t)255);     // block-aligned: one job per block
+}
+static void build_reduce_tables(stcd_engine& e) {
+    for (const WgradOp* op : e.wgrad_ops)
+        if (op->plan.ok) e.rjobs_total[op->stage] = append_reduce_job(e.rjobs[op->stage], e.rjobs_total[op->stage], reduce_job_of(e, *op));
+}
+
+// step 5: stage 1's table by group: the final group's jobs last, each part counting from 0 (the order of summation of every output is
+// its job's own; the split only partitions jobs across launches).  stcd_set_debug bit 1: one table, one launch on the tail.
+static void split_reduce_final(stcd_engine& e) {
+    const WgradOp* last = e.wg_last_op;
+    if (!last || !last->plan.ok || last->group < 0 || last->stage != 1 || (e.debug_flags & 2)) return;
+    std::vector<ReduceJob> part[2];
+    int64_t tot[2] = {0, 0};
+    for (const WgradOp* op : e.wgrad_ops) {      // (the order build_reduce_tables appended them in)
+        if (!op->plan.ok || op->stage != 1) continue;
+        if (op->group < 0) return;               // a launch of its own: no split
+        const int k = op->group == last->group ? 1 : 0;
+        tot[k] = append_reduce_job(part[k], tot[k], e.rjobs[1][part[0].size() + part[1].size()]);
+    }
+    if (part[0].empty() || part[1].empty()) return;
+    e.rjobs[1] = part[0];
+    e.rjobs[1].insert(e.rjobs[1].end(), part[1].begin(), part[1].end());
+    e.rj_split = (int)part[0].size(); e.wg_final_group = last->group;
+    e.rj_total_early = tot[0]; e.rj_total_final = tot[1];
+}
+
+static void build_wgrad_jobs(stcd_engine& e, Planner& ws) {
+    for (int st = 0; st < 2; ++st) { e.rjobs[st].clear(); e.rjobs_total[st] = 0; e.wgroups[st].clear(); }
+    e.rj_split = 0; e.wg_final_group = -1; e.rj_total_early = e.rj_total_final = 0;
     if (e.dt == BF16 && e.use_mfma) {
-        // ---- grouped weight-gradient launches: one grid per (stage, kernel variant).  The K split (gx) of every layer is
-        //      chosen for the GROUP: about two resident rounds of blocks over all its layers, each block owning at least
-        //      8 tiles, so deep layers get few slabs and the prologue / slab epilogue is amortised.
-        if (e.use_wgroup) {
-            for (WgradOp* op : e.wgrad_ops) {
-                if (!op->plan.ok) continue;
-                const bool t9 = !op->plan.dma && op->g.ntaps == 9;      // (one LDS-DMA group per stage, whatever the tap count)
-                std::vector<WgradGroup>& gs = e.wgroups[op->stage];
-                size_t gi = 0;
-                while (gi < gs.size() && !same_group(gs[gi], *op)) ++gi;
-                if (gi == gs.size()) { WgradGroup g; g.WCI = op->plan.WCI; g.NTW = op->plan.NTW; g.t9 = t9; g.gemm = op->plan.gemm; g.dma = op->plan.dma; g.xf = op->xf_C > 0; gs.push_back(g); }
-                op->grouped = true;
-            }
-            for (int st = 0; st < 2; ++st)
-                for (WgradGroup& G : e.wgroups[st]) {
-                    if (G.gemm) { G.lds_bytes = 2 * 2 * G.gemm * (64 * 64 + 8 * 32); continue; }     // gx fixed by wgrad_gemm_plan
-                    if (G.dma) {
-                        // one block per CU and ONE round: the smallest split length (in 64-position K-tiles) whose blocks -- (split, tap,
-                        // channel tile) over all layers of the group -- fit the 256 CUs; every block then walks about the same K
-                        G.lds_bytes = 128 * 1024;
-                        std::vector<WgradOp*> dops;
-                        for (WgradOp* op : e.wgrad_ops)
-                            if (op->grouped && op->stage == st && op->plan.dma) dops.push_back(op);
-                        auto blocks_at = [&](int64_t kt) {
-                            int64_t b = 0;
-                            for (WgradOp* op : dops) {
-                                const int64_t M = (int64_t)op->g.n * op->g.hi * op->g.wi;
-                                b += ((M + kt * 64 - 1) / (kt * 64)) * op->plan.gy * op->plan.gz;
-                            }
-                            return b;
-                        };
-                        int64_t lo = 1, hi = 1;
-                        // (fewer than one block per CU leaves whole CUs to the kernels of the backward chain the group runs beside -- its
-                        //  blocks fill the register file of the CUs they sit on)
-                        // 192 when the group runs on the side stream (single-call backwards): measured 26.9 -> 26.3 ms; 256 gains nothing there
-                        const int dma_blocks = e.wg_side_on && cf_side_on() ? 192 : 256;
-                        while (blocks_at(hi) > dma_blocks) hi *= 2;
-                        while (lo < hi) { const int64_t mid = (lo + hi) / 2; if (blocks_at(mid) <= dma_blocks) hi = mid; else lo = mid + 1; }
-                        for (WgradOp* op : dops) {
-                            const ConvW& cv = e.convs[op->conv];
-                            const int64_t M = (int64_t)op->g.n * op->g.hi * op->g.wi;
-                            int64_t S = (M + lo * 64 - 1) / (lo * 64);
-                            const int64_t slab_bytes = (int64_t)op->g.ntaps * cv.fwd.kpad * cv.fwd.wld * 4;
-                            S = std::min<int64_t>(S, std::max<int64_t>(1, ((int64_t)64 << 20) / slab_bytes));
-                            wgrad_dma_set_split(op->plan, op->g, (int)S, cv.fwd.kpad, cv.fwd.wld);
-                        }
-                        continue;
-                    }
-                    std::vector<WgradOp*> ops;
-                    int64_t W = 0;
-                    for (WgradOp* op : e.wgrad_ops)
-                        if (op->grouped && op->stage == st && same_group(G, *op)) {
-                            ops.push_back(op);
-                            const int64_t ntiles = (int64_t)op->g.n * ((op->g.wm + 15) / 16) * ((op->g.hm + 7) / 8);
-                            W += ntiles * op->plan.gy * op->plan.gz;
-                        }
-                    for (WgradOp* op : ops) {   // LDS need of the group = max over its jobs
-                        const ConvW& cv = e.convs[op->conv];
-                        WgradJob j = wgrad_make_job(op->g, op->plan, 0, 0, 0, cv.fwd.kpad, cv.fwd.wld);
-                        if (op->xf_C > 0) wgrad_job_set_xf(j, op->xf_stat_off, op->xf_mask_off, op->xf_C, op->xf_groups, op->xf_npg);
-                        G.lds_bytes = std::max(G.lds_bytes, j.lds_bytes);
-                    }
-                    int slots = wgrad_variant_slots(G.WCI, G.NTW, G.t9, G.lds_bytes);
-                    // stage 0 of the FC-Siam family runs beside stage 1's chain on a side stream: its grids leave room for the chain's blocks
-                    // (stage 1's groups keep the full budget: half cost 2 %, a quarter 7 %)
-                    if (st == 0 && e.wg_side_on && fc_family(e)) slots = std::max(64, slots / stcd_engine_impl::WG_SIDE_DIV);
-                    const int64_t rounds = stcd_engine_impl::WGROUP_ROUNDS;
-                    const int64_t tpb = std::max<int64_t>(stcd_engine_impl::WGROUP_MIN_TILES, (W + rounds * slots - 1) / (rounds * slots));
-                    for (WgradOp* op : ops) {
-                        const ConvW& cv = e.convs[op->conv];
-                        const int64_t ntiles = (int64_t)op->g.n * ((op->g.wm + 15) / 16) * ((op->g.hm + 7) / 8);
-                        const int64_t slab_bytes = (int64_t)op->g.ntaps * cv.fwd.kpad * cv.fwd.wld * 4;
-                        int64_t gx = std::max<int64_t>(1, (ntiles + tpb - 1) / tpb);
-                        gx = std::min<int64_t>(gx, std::max<int64_t>(1, ((int64_t)32 << 20) / slab_bytes));
-                        op->plan.gx = (int)gx;
-                        op->plan.slab_floats = gx * op->g.ntaps * cv.fwd.kpad * cv.fwd.wld;
-                    }
-                }
-        }
-        int64_t cur[2] = {0, 0};
-        std::vector<int> rj_group1;      // stage 1: the group of every reduce job's launch (-1: a launch of its own)
-        for (WgradOp* op : e.wgrad_ops) {
-            if (!op->plan.ok) continue;
-            const ConvW& cv = e.convs[op->conv];
-            op->slab = ws.take(op->plan.slab_floats * 4);
-            if (op->grouped) {
-                for (WgradGroup& G : e.wgroups[op->stage])
-                    if (same_group(G, *op)) {
-                        op->group = (int)(&G - e.wgroups[op->stage].data());
-                        WgradJob j = op->plan.dma ? wgrad_dma_make_job(op->g, op->plan, op->in_off, op->dout_off, op->slab, cv.fwd.kpad, cv.fwd.wld)
-                                   : op->plan.gemm ? wgrad_gemm_make_job(op->g, op->plan, op->in_off, op->dout_off, op->slab, cv.fwd.kpad, cv.fwd.wld)
-                                                   : wgrad_make_job(op->g, op->plan, op->in_off, op->dout_off, op->slab, cv.fwd.kpad, cv.fwd.wld);
-                        if (op->xf_C > 0 && !op->plan.dma && !op->plan.gemm) wgrad_job_set_xf(j, op->xf_stat_off, op->xf_mask_off, op->xf_C, op->xf_groups, op->xf_npg);
-                        j.start = G.total_blocks;
-                        G.total_blocks += j.gx * j.gy * j.gz;
-                        G.jobs.push_back(j);
-                        double fl, by;
-                        conv_work(e, op->g, op->kreal, op->nreal, &fl, &by);
-                        G.flops += fl; G.bytes += by;
-                    }
-            }
-            ReduceJob j{};
-            j.slab_off = op->slab; j.out_off = cv.w_off;
-            j.slab_stride = (int64_t)op->g.ntaps * cv.fwd.kpad * cv.fwd.wld;
-            j.gx = op->plan.gx; j.ntaps = op->g.ntaps; j.K = cv.cin; j.N = cv.cout; j.kpad = cv.fwd.kpad; j.wld = cv.fwd.wld;
-            j.ks = cv.fwd.ks; j.kn_major = cv.fwd.kn_major;
-            for (int t = 0; t < op->g.ntaps; ++t) {
-                j.ky[t] = op->own_taps ? op->oky[t] : cv.fwd.ky[op->tap0 + t];
-                j.kx[t] = op->own_taps ? op->okx[t] : cv.fwd.kx[op->tap0 + t];
-            }
-            j.tiled = (int64_t)j.ntaps * j.K * j.N >= 512 * 1024;     // measured: the tiled form pays from ~0.5 M weights per launch
-            if (!j.tiled) {   // index space: blocks of (256 / parts) outputs x parts threads; <= 32 slabs per part where 64 parts allow
-                const int64_t outs = (int64_t)j.ntaps * j.K * j.N;
-                int parts = 1;
-                while (parts < 64 && parts * 32 < j.gx) parts *= 2;
-                j.parts = (int8_t)parts;
-                const int64_t OUTS = 256 / parts;
-                j.count = ((outs + OUTS - 1) / OUTS) * 256;
-            } else {   // index space: one block (256 threads) per tile of 32 co x TK ci x taps, all slabs (>= 0.5 M weights: the 32 / 64 MB
-                const int TK = j.ntaps == 1 ? 32 : 16;                 // slab caps leave <= 32 of them): see k_reduce_jobs
-                const int64_t ntiles = (int64_t)((j.N + 31) / 32) * ((j.K + TK - 1) / TK);
-                j.parts = 1;
-                j.count = ntiles * 256;
-            }
-            j.start = cur[op->stage];
-            cur[op->stage] += (j.count + 255) & ~(int64_t)255;     // block-aligned: one job per block
-            e.rjobs[op->stage].push_back(j);
-            if (op->stage == 1) rj_group1.push_back(op->grouped ? op->group : -1);
-        }
-        // stage 1's table by group: the final group's jobs last, each part counting from 0 (the order of summation of every output is
-        // its job's own; the split only partitions jobs across launches).  stcd_set_debug bit 1: one table, one launch on the tail.
-        e.rj_split = 0; e.wg_final_group = -1; e.rj_total_early = e.rj_total_final = 0;
-        if (e.wg_last_op && e.wg_last_op->plan.ok && e.wg_last_op->grouped && e.wg_last_op->stage == 1 && !(e.debug_flags & 2)) {
-            const int gf = e.wg_last_op->group;
-            std::vector<ReduceJob> part[2];
-            bool all_grouped = true;
-            for (size_t i = 0; i < e.rjobs[1].size(); ++i) {
-                all_grouped = all_grouped && rj_group1[i] >= 0;
-                part[rj_group1[i] == gf ? 1 : 0].push_back(e.rjobs[1][i]);
-            }
-            if (all_grouped && !part[0].empty() && !part[1].empty()) {
-                int64_t tot[2] = {0, 0};
-                for (int k = 0; k < 2; ++k)
-                    for (ReduceJob& j : part[k]) { j.start = tot[k]; tot[k] += (j.count + 255) & ~(int64_t)255; }
-                e.rjobs[1] = part[0];
-                e.rjobs[1].insert(e.rjobs[1].end(), part[1].begin(), part[1].end());
-                e.rj_split = (int)part[0].size(); e.wg_final_group = gf;
-                e.rj_total_early = tot[0]; e.rj_total_final = tot[1];
-            }
-        }
+        if (e.use_wgroup) { form_wgroups(e); choose_wgroup_splits(e); }
+        take_wgrad_slabs(e, ws);
+        build_reduce_tables(e);
+        split_reduce_final(e);
         for (int st = 0; st < 2; ++st) {
-            e.rjobs_total[st] = cur[st];
             e.rjobs_off[st] = ws.take((int64_t)e.rjobs[st].size() * sizeof(ReduceJob) + 16);
             for (WgradGroup& G : e.wgroups[st]) G.table_off = ws.take((int64_t)G.jobs.size() * sizeof(WgradJob) + 16);
         }
     }
-    // ---- one repack launch per forward: job tables (uploaded to the workspace on first use)
+    for (int st = 0; st < 2; ++st) e.wrun.groups[st].assign(e.wgroups[st].size(), WgradRun::Group());
+}
+
+// one repack launch per forward: the filter job tables (uploaded to the workspace on first use)
+static void build_filter_pack_jobs(stcd_engine& e, Planner& ws) {
     for (int with_dgrad = 0; with_dgrad < 2; ++with_dgrad) {
         std::vector<PackJob>& jobs = e.jobs[with_dgrad];
         jobs.clear();
@@ -1218,15 +1232,13 @@ static int configure_fcsiam(stcd_engine& e, int B, int H, int W) {
             if (op.small && e.use_small) return true;
             return op.res.ok && !nchw && !op.res.single_halo;
         };
-        auto wg_ok = [&](const WgradOp& op) { return op.plan.ok && !op.plan.gemm && !op.plan.dma && op.plan.WCI < 4 && op.plan.NTW < 4; };
+        auto wg_ok = [&](const WgradOp& op) { return op.plan.ok && wgrad_kernel_takes_xf(wgrad_kernel_of(op.plan, op.g, true)); };
         auto link = [&](Cbrd& P, ConvOp& cf, WgradOp& cw, bool nchw) {
             if (P.pool || P.fuse_dst.off >= 0) return false;
             if (!fwd_ok(cf, nchw) || !wg_ok(cw)) return false;
             P.virt = true; ++e.fc_virt_layers;
             cw.in_off = P.Y.off;
-            cw.xf_stat_off = P.stat;
-            cw.xf_mask_off = (P.drop >= 0) ? e.masks + e.drops[P.drop].off * 4 : -1;
-            cw.xf_C = e.convs[P.conv].cout; cw.xf_groups = P.groups; cw.xf_npg = P.npg;
+            cw.xf = WgradXf{P.stat, (P.drop >= 0) ? e.masks + e.drops[P.drop].off * 4 : -1, e.convs[P.conv].cout, P.groups, P.npg};
             return true;
         };
         for (size_t i = 0; i + 1 < e.enc.size(); ++i) {
@@ -1494,43 +1506,6 @@ static bool exec_conv_x4(const Ctx& c, const ConvOp ops[4], const void* in, cons
     return true;
 }
 
-// weight gradient of one launch, delivered straight into the reference-layout gradient tensor
-static void wgroup_member_ready(const Ctx& c, const WgradOp& op);
-static void exec_wgrad(const Ctx& c, const WgradOp& op, const void* in, const void* dout) {
-    const ConvW& cv = c.e.convs[op.conv];
-    PackSpec sub = cv.fwd;                 // this launch's taps of the filter
-    sub.ntaps = op.g.ntaps;
-    for (int t = 0; t < op.g.ntaps; ++t) {
-        sub.ky[t] = op.own_taps ? op.oky[t] : cv.fwd.ky[op.tap0 + t];
-        sub.kx[t] = op.own_taps ? op.okx[t] : cv.fwd.kx[op.tap0 + t];
-    }
-    double fl, by;
-    conv_work(c.e, op.g, op.kreal, op.nreal, &fl, &by);
-    if (mfma_on(c.e) && op.plan.ok && op.grouped) {          // runs in the stage's grouped launch (reduce_stage, or early: wgroup_member_ready)
-        if (c.e.wg_early) wgroup_member_ready(c, op);
-        return;
-    }
-    if (mfma_on(c.e) && op.plan.ok) {
-        int rc;
-        {
-            char kname[64];
-            snprintf(kname, sizeof(kname), "k_wgrad_mfma<%d, %d>", op.plan.WCI, op.plan.NTW);
-            ProfScope prof(c, PC_WGRAD, fl, by, kname);
-            rc = launch_wgrad_mfma(op.g, op.plan, in, dout, c.at<float>(op.slab), sub.kpad, sub.wld, c.s);
-        }
-        if (rc == 0) return;       // the slabs are summed by the stage's batched reduce launch (reduce_stage)
-    }
-    if (op.own_taps) { set_error("internal: no reference fallback for a launch with its own tap table"); return; }
-    double* dwe = c.at<double>(cv.dwe) + (int64_t)op.tap0 * sub.kpad * sub.wld;
-    if (mfma_on(c.e))   // the bulk memset of the reference path's accumulators is skipped in MFMA mode
-        (void)hipMemsetAsync(dwe, 0, (size_t)sub.ntaps * sub.kpad * sub.wld * 8, c.s);
-    {
-        ProfScope prof(c, PC_WGRAD, fl, by, "k_wgrad_ref");
-        launch_wgrad_ref_f64(c.e.dt, op.g, in, dout, dwe, sub.kpad, sub.wld, c.s);
-    }
-    launch_unpack_dw(sub, dwe, c.grads + cv.w_off, c.s);
-}
-
 // what comes before the pack launch: uploads the job tables on first use of a workspace, then says whether the filter images must be
 // (re)packed -- and books them as packed, so the caller launches the pack (on its own or inside k_step_prologue) when *need is set
 static int pack_prepare(const Ctx& c, bool with_dgrad, bool* need) {
@@ -1572,80 +1547,103 @@ static int pack_all_weights(const Ctx& c, bool with_dgrad) {
     return 0;
 }
 
-static void launch_wgroup(const Ctx& c, WgradGroup& G) {
-    {
-        char kname[64];
-        if (G.dma) snprintf(kname, sizeof(kname), "k_wgrad_dma");
-        else if (G.gemm) snprintf(kname, sizeof(kname), "k_wgrad_gemm<%d>", G.gemm);
-        else snprintf(kname, sizeof(kname), "k_wgrad_group<%d, %d, %s>", G.WCI, G.NTW, G.t9 ? "true" : "false");
-        ProfScope prof(c, PC_WGRAD, G.flops, G.bytes, kname);
-        G.launched = true;
-        if (G.dma) {
-            launch_wgrad_dma_group(c.at<WgradJob>(G.table_off), (int)G.jobs.size(), G.total_blocks, c.ws, c.s);
-            return;
-        }
-        if (G.gemm) {
-            launch_wgrad_gemm_group(G.gemm, c.at<WgradJob>(G.table_off), (int)G.jobs.size(), G.total_blocks, c.ws, c.s);
-            return;
-        }
-        if (launch_wgrad_group(G.WCI, G.NTW, G.t9, c.at<WgradJob>(G.table_off), (int)G.jobs.size(), G.total_blocks, G.lds_bytes,
-                               c.ws, c.s, G.xf) != 0)
-            set_error("grouped weight-gradient launch exceeds the LDS budget");
-    }
+// ---- weight gradients at run time.  What a call changes is in e.wrun (WgradScope); the plan is only read.  A refusal or a failed HIP
+//      call keeps the first such text of the call and sets wrun.failed, which stage_tail turns into the backward's return value.
+static void wgrad_fail(const Ctx& c, const std::string& msg) {
+    if (!c.e.wrun.failed) set_error(msg);
+    c.e.wrun.failed = true;
 }
 
-// FC-Siam backward with early launches (e.wg_early): a member's operands (X stored by the forward, dY final) exist when the chain
+static void launch_wgroup(const Ctx& c, int stage, int group) {
+    const WgradGroup& G = c.e.wgroups[stage][group];
+    char kname[64];
+    wgrad_kernel_name(G.kernel, true, kname);
+    ProfScope prof(c, PC_WGRAD, G.flops, G.bytes, kname);
+    c.e.wrun.groups[stage][group].launched = true;
+    if (launch_wgrad_jobs(G.kernel, c.at<WgradJob>(G.table_off), (int)G.jobs.size(), G.total_blocks, G.lds_bytes, c.ws, c.s) != 0)
+        wgrad_fail(c, "grouped weight-gradient launch exceeds the LDS budget");
+}
+
+// A backward with early launches (wrun.early): a member's operands (X stored by the forward, dY final) exist when the chain
 // calls exec_wgrad for it; the group's grid goes out with its LAST member -- on the side stream, behind an event of the chain's
 // stream, when there is one -- instead of at the end of the stage
 // stage 1 with a split reduce table: once every group but the final one has gone out, their slabs are summed right behind them (on the
 // stream they went out on), under the chain's last kernels instead of on the tail
 static void reduce_early_if_due(const Ctx& c) {
     stcd_engine& e = c.e;
-    if (e.rj_split <= 0 || e.rj_early_done) return;
+    if (e.rj_split <= 0 || e.wrun.rj_early_done) return;
     if (e.prof.on) return;      // instrumented steps run serially on one stream: both parts go out on the tail, timed as one record
     for (size_t g = 0; g < e.wgroups[1].size(); ++g)
-        if ((int)g != e.wg_final_group && !e.wgroups[1][g].launched) return;
+        if ((int)g != e.wg_final_group && !e.wrun.groups[1][g].launched) return;
     launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]), e.rj_split, e.rj_total_early, c.ws, c.grads, c.s);
-    e.rj_early_done = true;
+    e.wrun.rj_early_done = true;
 }
 static void wgroup_member_ready(const Ctx& c, const WgradOp& op) {
     stcd_engine& e = c.e;
-    if (op.group < 0 || op.group >= (int)e.wgroups[op.stage].size()) return;
-    WgradGroup& G = e.wgroups[op.stage][op.group];
-    if (++G.seen < (int)G.jobs.size() || G.launched) return;
+    WgradRun& run = e.wrun;
+    WgradRun::Group& rg = run.groups[op.stage][op.group];
+    if (++rg.seen < (int)e.wgroups[op.stage][op.group].jobs.size() || rg.launched) return;
     // stage 1's final group (conv11, conv12) becomes ready when the chain has nothing left to run beside it: it goes out on the
     // caller's stream, and its slab reduce and the optimizer behind it need no cross-stream hand-off (stage_tail; measured in
     // DESIGN.md section 4, "Step seams")
     const bool final_group = op.stage == 1 && e.rj_split > 0 && op.group == e.wg_final_group;
-    if (e.wg_cur_side && !final_group) {
-        if (hipEventRecord(e.wg_fork, c.s) != hipSuccess || hipStreamWaitEvent(e.wg_cur_side, e.wg_fork, 0) != hipSuccess) { set_error("side-stream fork failed"); return; }
-        Ctx cs{e, c.ws, c.params, c.grads, e.wg_cur_side};
-        launch_wgroup(cs, G);
+    if (run.side && !final_group) {
+        if (hipEventRecord(e.wg_fork, c.s) != hipSuccess || hipStreamWaitEvent(run.side, e.wg_fork, 0) != hipSuccess) { wgrad_fail(c, "side-stream fork failed"); return; }
+        Ctx cs{e, c.ws, c.params, c.grads, run.side};
+        launch_wgroup(cs, op.stage, op.group);
         if (op.stage == 1) reduce_early_if_due(cs);
     } else {
-        launch_wgroup(c, G);
-        if (final_group && e.wg_cur_side) e.wg_final_on_main = true;
+        launch_wgroup(c, op.stage, op.group);
+        if (final_group && run.side) run.final_on_main = true;
         else if (op.stage == 1) reduce_early_if_due(c);
     }
 }
 
-// the stage's groups that have not gone out yet, then the batched slab reduction; resets the groups' run-time state
+// weight gradient of one launch, delivered straight into the reference-layout gradient tensor
+static void exec_wgrad(const Ctx& c, const WgradOp& op, const void* in, const void* dout) {
+    const ConvW& cv = c.e.convs[op.conv];
+    if (mfma_on(c.e) && op.plan.ok && op.group >= 0) {          // runs in the stage's grouped launch (reduce_stage, or early: wgroup_member_ready)
+        if (c.e.wrun.early) wgroup_member_ready(c, op);
+        return;
+    }
+    double fl, by;
+    conv_work(c.e, op.g, op.kreal, op.nreal, &fl, &by);
+    if (mfma_on(c.e) && op.plan.ok) {
+        char kname[64];
+        wgrad_kernel_name(wgrad_kernel_of(op.plan, op.g, false), false, kname);
+        ProfScope prof(c, PC_WGRAD, fl, by, kname);
+        if (launch_wgrad_mfma(op.g, op.plan, in, dout, c.at<float>(op.slab), cv.fwd.kpad, cv.fwd.wld, c.s) == 0)
+            return;                // the slabs are summed by the stage's batched reduce launch (reduce_stage)
+    }
+    if (op.own_taps) { wgrad_fail(c, "internal: no reference fallback for a launch with its own tap table"); return; }
+    PackSpec sub = cv.fwd;                 // this launch's taps of the filter
+    sub.ntaps = op.g.ntaps;
+    wgrad_taps(c.e, op, sub.ky, sub.kx);
+    double* dwe = c.at<double>(cv.dwe) + (int64_t)op.tap0 * sub.kpad * sub.wld;
+    if (mfma_on(c.e)) {   // the bulk memset of the reference path's accumulators is skipped in MFMA mode
+        const hipError_t err = hipMemsetAsync(dwe, 0, (size_t)sub.ntaps * sub.kpad * sub.wld * 8, c.s);
+        if (err != hipSuccess) { wgrad_fail(c, std::string("exec_wgrad: hipMemsetAsync: ") + hipGetErrorString(err)); return; }
+    }
+    {
+        ProfScope prof(c, PC_WGRAD, fl, by, "k_wgrad_ref");
+        launch_wgrad_ref_f64(c.e.dt, op.g, in, dout, dwe, sub.kpad, sub.wld, c.s);
+    }
+    launch_unpack_dw(sub, dwe, c.grads + cv.w_off, c.s);
+}
+
+// the stage's groups that have not gone out yet, then the batched slab reduction
 static void reduce_stage(const Ctx& c, int stage) {
     stcd_engine& e = c.e;
-    for (WgradGroup& G : e.wgroups[stage]) {
-        if (!G.launched) launch_wgroup(c, G);
-        G.launched = false; G.seen = 0;
-    }
+    for (size_t g = 0; g < e.wgroups[stage].size(); ++g)
+        if (!e.wrun.groups[stage][g].launched) launch_wgroup(c, stage, (int)g);
     if (e.rjobs[stage].empty()) return;
+    ProfScope prof(c, PC_PACK, 0.0, 0.0, "k_reduce_jobs");
     if (stage == 1 && e.rj_split > 0) {      // split table: whatever of the early part is still open, then the final group's jobs
-        ProfScope prof(c, PC_PACK, 0.0, 0.0, "k_reduce_jobs");
-        if (!e.rj_early_done) launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]), e.rj_split, e.rj_total_early, c.ws, c.grads, c.s);
-        e.last_tail = (e.rj_early_done ? 1 : 0) | (e.wg_final_on_main ? 2 : 0);      // (stcd_seam_plan)
-        e.rj_early_done = false; e.wg_final_on_main = false;
+        if (!e.wrun.rj_early_done) launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]), e.rj_split, e.rj_total_early, c.ws, c.grads, c.s);
+        e.last_tail = (e.wrun.rj_early_done ? 1 : 0) | (e.wrun.final_on_main ? 2 : 0);      // (stcd_seam_plan)
         launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[1]) + e.rj_split, (int)e.rjobs[1].size() - e.rj_split, e.rj_total_final, c.ws, c.grads, c.s);
         return;
     }
-    ProfScope prof(c, PC_PACK, 0.0, 0.0, "k_reduce_jobs");
     launch_reduce_jobs(c.at<ReduceJob>(e.rjobs_off[stage]), (int)e.rjobs[stage].size(), e.rjobs_total[stage], c.ws, c.grads, c.s);
 }
 
@@ -1943,18 +1941,19 @@ static void finish_biases(const Ctx& c) {
 // sums, bias finish).  With a side stream all of it runs there, behind an event of the caller's stream, and wg_join is recorded; the
 // caller's stream waits on it only where wait_join says so (the last stage of a call: an earlier stage's tail runs beside the next
 // stage's chain, and the side stream's order carries it to the last join).
+// Returns 1 when a HIP call here fails or the call's weight-gradient path has failed (wrun.failed).
 template <typename Extra>
 static int stage_tail(const Ctx& c, int stage, hipStream_t side, bool wait_join, Extra extra) {
     stcd_engine& e = c.e;
-    if (!side) { reduce_stage(c, stage); extra(c); return 0; }
-    if (stage == 1 && e.wg_final_on_main && e.rj_early_done) {
+    if (!side) { reduce_stage(c, stage); extra(c); return e.wrun.failed; }
+    if (stage == 1 && e.wrun.final_on_main && e.wrun.rj_early_done) {
         // the stage's final group went out on the caller's stream, and everything the side stream holds went out long ago (the earlier
         // stage's tail, the early groups, their reduce): join it first, then the final group's reduce follows that group on this stream
         STCD_HIP(hipEventRecord(e.wg_join, side));
         STCD_HIP(hipStreamWaitEvent(c.s, e.wg_join, 0));
         reduce_stage(c, stage);
         extra(c);
-        return 0;
+        return e.wrun.failed;
     }
     STCD_HIP(hipEventRecord(e.wg_fork, c.s));
     STCD_HIP(hipStreamWaitEvent(side, e.wg_fork, 0));
@@ -1963,13 +1962,27 @@ static int stage_tail(const Ctx& c, int stage, hipStream_t side, bool wait_join,
     extra(cs);
     STCD_HIP(hipEventRecord(e.wg_join, side));
     if (wait_join) STCD_HIP(hipStreamWaitEvent(c.s, e.wg_join, 0));
-    return 0;
+    return e.wrun.failed;
 }
 
-struct EarlyScope {      // exec_wgrad sends a group out with its last member for the duration of a backward call
+// Every backward entry opens with this: e.wrun is reset for the stages the call runs (stage < 0: both) and set up for the call, and
+// is clean again when the call ends, however it ends.  early: exec_wgrad sends a group out with its last member, on `side` if set.
+// last_tail (stcd_seam_plan) is the stage-1 tail's to write and outlives the call.
+struct WgradScope {
     stcd_engine& e;
-    EarlyScope(stcd_engine& e_, bool on, hipStream_t sd) : e(e_) { e.wg_early = on; e.wg_cur_side = sd; }
-    ~EarlyScope() { e.wg_early = false; e.wg_cur_side = nullptr; }
+    WgradScope(stcd_engine& e_, int stage, bool early, hipStream_t side) : e(e_) {
+        reset(stage);
+        e.wrun.early = early; e.wrun.side = side;
+        if (stage != 0) e.last_tail = 0;
+    }
+    ~WgradScope() { reset(-1); }
+    void reset(int stage) {
+        WgradRun& r = e.wrun;
+        for (int st = 0; st < 2; ++st)
+            if (stage < 0 || stage == st) std::fill(r.groups[st].begin(), r.groups[st].end(), WgradRun::Group());
+        r.early = false; r.side = nullptr;
+        r.rj_early_done = r.final_on_main = r.failed = false;
+    }
 };
 
 static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float* params, float* grads, void* workspace,
@@ -1978,11 +1991,7 @@ static int backward_fcsiam(stcd_engine& e, const float* grad_logits, const float
     // both stages in one call (no gradient all-reduce between them): stage 0's weight gradients only read stored tensors and write
     // their own slabs / gradient entries, so they can run beside stage 1's chain
     hipStream_t side = stage < 0 ? wgrad_side_stream(e, s) : nullptr;
-    EarlyScope early_scope(e, mfma_on(e) && e.use_wgroup, side);
-    for (int st = 0; st < 2; ++st)
-        if (stage < 0 || stage == st)
-            for (WgradGroup& G : e.wgroups[st]) { G.seen = 0; G.launched = false; }      // (a failed call may have left them set)
-    if (stage != 0) { e.rj_early_done = false; e.wg_final_on_main = false; e.last_tail = 0; }
+    WgradScope wgrad_scope(e, stage, mfma_on(e) && e.use_wgroup, side);
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt);
     if (stage <= 0) {
@@ -2506,8 +2515,7 @@ static int backward_snunet(stcd_engine& e, const float* grad_logits, const float
     // groups whose members all sit deep in the backward order -- the GEMM groups, the 32 x 32 tile group -- run beside the rest of
     // the chain: 13.22 -> 12.80 ms; cutting the groups into buckets of the backward order, or smaller grids, added nothing)
     hipStream_t side = stage < 0 ? wgrad_side_stream(e, s) : nullptr;
-    EarlyScope early_scope(e, mfma_on(e) && e.use_wgroup, side);
-    for (WgradGroup& G : e.wgroups[0]) { G.seen = 0; G.launched = false; }
+    WgradScope wgrad_scope(e, stage, mfma_on(e) && e.use_wgroup, side);
     const int dt = e.dt, B = e.B;
     const int64_t T = (int64_t)dsize(dt);
     const int c4 = SN_F[0] * 4;
@@ -3143,6 +3151,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
                           hipStream_t s) {
     if (stage == 1) return 0;
     Ctx c{e, (char*)workspace, params, grads, s};
+    WgradScope wgrad_scope(e, stage, false, nullptr);      // (the groups go out on the tail)
     const int B = e.B, dt = e.dt;
     const int64_t T = (int64_t)dsize(dt), HW = (int64_t)e.H * e.W;
     STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
@@ -3216,8 +3225,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
             launch_maxpool3_bwd(dt, c.at<unsigned char>(e.g_pool_idx), c.at(st.ddst.off), st.ddst.ld, c.at(st.dsrc.off), st.dsrc.ld, st.N, st.h, st.w, st.C, s);
         }
     }
-    reduce_stage(c, 0);
-    launch_bias_finish(c.at<BiasJob>(e.bias_jobs_off), (int)e.bias_jobs.size(), c.ws, c.grads, s);
+    if (stage_tail(c, 0, nullptr, false, finish_biases)) return 1;
     STCD_HIP(hipGetLastError());
     return 0;
 }
@@ -3226,7 +3234,7 @@ static int backward_segcd(stcd_engine& e, const float* grad_logits, const float*
 
 // The shape-bound state every configure_* rebuilds from empty, reset in ONE place (stcd_configure) -- a vector left out here lets a
 // table grow with every re-configure (tests/test_lifecycle_cpu.py).  Per-layer fields of the table-time vectors (sn_blocks, g_layers,
-// xc) are reset by their family's own loops; build_pack_jobs clears the job tables it owns.
+// xc) are reset by their family's own loops; build_wgrad_jobs and build_filter_pack_jobs clear the job tables they own.
 static void reset_plan(stcd_engine& e) {
     e.enc.clear(); e.dec.clear(); e.ups.clear();
     e.drops.clear(); e.drop_floats = 0;
@@ -3876,31 +3884,22 @@ int stcd_op_wgrad(int dtype, int impl, const stcd_conv_geom* g, const void* in, 
         STCD_HIP(hipGetLastError());
         return 0;
     }
-    if (impl == 7) {      // the LDS-DMA kernel: 256 x 256 channel tile per (position split, tap) block (ChangeFormer's 256 -> 256 3x3 layers)
+    // 7: the LDS-DMA kernel, 256 x 256 channel tile per (position split, tap) block (ChangeFormer's 256 -> 256 3x3 layers)
+    // 3: one-tap launches on the position-GEMM kernel (the engine's choice for Ci, Co >= 64)
+    // either as a grouped launch of one job: `scratch` holds the slabs, then the job table
+    if (impl == 3 || impl == 7) {
         STCD_CHECK(dtype == STCD_DTYPE_BF16, "the MFMA implementation is bf16 only");
-        WgradMfmaPlan p = wgrad_dma_plan(*g, g->ci, g->co);
-        STCD_CHECK(p.ok, "geometry not supported by the LDS-DMA weight-gradient kernel (stride 1, full map >= 64 wide, Ci % 256 == 0, Co % 256 == 0)");
-        wgrad_dma_set_split(p, *g, op_dma_splits(*g, p), g->ci, g->co);
+        WgradMfmaPlan p = impl == 7 ? wgrad_dma_plan(*g, g->ci, g->co) : wgrad_gemm_plan(*g, g->ci, g->co);
+        STCD_CHECK(p.ok, impl == 7 ? "geometry not supported by the LDS-DMA weight-gradient kernel (stride 1, full map >= 64 wide, Ci % 256 == 0, Co % 256 == 0)"
+                                   : "geometry not supported by the GEMM weight-gradient kernel (one tap, Ci >= 64, Co >= 64)");
+        if (impl == 7) wgrad_dma_set_split(p, *g, op_dma_splits(*g, p), g->ci, g->co);
         const int64_t table = (p.slab_floats * 4 + 255) & ~(int64_t)255;
         STCD_CHECK(scratch && scratch_bytes >= table + (int64_t)sizeof(WgradJob), "scratch too small for the partial slabs + job table");
-        WgradJob j = wgrad_dma_make_job(*g, p, (int64_t)(intptr_t)in, (int64_t)(intptr_t)dout, (int64_t)(intptr_t)scratch, g->ci, g->co);
+        const WgradKernel k = wgrad_kernel_of(p, *g, false);
+        const WgradJob j = wgrad_job(k, *g, p, (int64_t)(intptr_t)in, (int64_t)(intptr_t)dout, (int64_t)(intptr_t)scratch, g->ci, g->co);
         STCD_HIP(hipMemcpyAsync((char*)scratch + table, &j, sizeof(j), hipMemcpyHostToDevice, (hipStream_t)hip_stream));
         STCD_HIP(hipStreamSynchronize((hipStream_t)hip_stream));       // `j` is a stack object
-        launch_wgrad_dma_group((const WgradJob*)((char*)scratch + table), 1, p.gx * p.gy * p.gz, nullptr, (hipStream_t)hip_stream);
-        launch_reduce_dw((const float*)scratch, p.gx, *g, g->ci, g->co, g->ci, g->co, nullptr, dw, (hipStream_t)hip_stream);
-        STCD_HIP(hipGetLastError());
-        return 0;
-    }
-    if (impl == 3) {      // one-tap launches on the position-GEMM kernel (the engine's choice for Ci, Co >= 64)
-        STCD_CHECK(dtype == STCD_DTYPE_BF16, "the MFMA implementation is bf16 only");
-        WgradMfmaPlan p = wgrad_gemm_plan(*g, g->ci, g->co);
-        STCD_CHECK(p.ok, "geometry not supported by the GEMM weight-gradient kernel (one tap, Ci >= 64, Co >= 64)");
-        const int64_t table = (p.slab_floats * 4 + 255) & ~(int64_t)255;
-        STCD_CHECK(scratch && scratch_bytes >= table + (int64_t)sizeof(WgradJob), "scratch too small for the partial slabs + job table");
-        WgradJob j = wgrad_gemm_make_job(*g, p, (int64_t)(intptr_t)in, (int64_t)(intptr_t)dout, (int64_t)(intptr_t)scratch, g->ci, g->co);
-        STCD_HIP(hipMemcpyAsync((char*)scratch + table, &j, sizeof(j), hipMemcpyHostToDevice, (hipStream_t)hip_stream));
-        STCD_HIP(hipStreamSynchronize((hipStream_t)hip_stream));       // `j` is a stack object
-        launch_wgrad_gemm_group(p.gemm, (const WgradJob*)((char*)scratch + table), 1, p.gx * p.gy * p.gz, nullptr, (hipStream_t)hip_stream);
+        STCD_CHECK(launch_wgrad_jobs(k, (const WgradJob*)((char*)scratch + table), 1, p.gx * p.gy * p.gz, j.lds_bytes, nullptr, (hipStream_t)hip_stream) == 0, "LDS budget exceeded");
         launch_reduce_dw((const float*)scratch, p.gx, *g, g->ci, g->co, g->ci, g->co, nullptr, dw, (hipStream_t)hip_stream);
         STCD_HIP(hipGetLastError());
         return 0;

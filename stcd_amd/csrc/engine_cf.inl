@@ -10,7 +10,7 @@
 // Every matrix product is a 1x1-geometry launch of the tap-list GEMM kernels: Linear layers directly, the strided patch-embedding
 // and spatial-reduction convolutions over an im2col matrix in the reference's own K order (k_im2col), so filters and their
 // gradients keep the reference layouts.  Every tensor has its own value and gradient buffer (no reuse): the weight gradients
-// of a backward stage then run as the grouped launches of build_pack_jobs / reduce_stage.
+// of a backward stage then run as the grouped launches of build_wgrad_jobs / reduce_stage.
 // Dropout / DropPath masks are never stored: each site hashes (site seed, element index) in the forward and again in the backward.
 
 struct CfT { TRef v, g; int n = 0, h = 0, w = 0, c = 0; };          // value + gradient, [n, h, w, c] NHWC (ld = c unless a slice)
@@ -737,10 +737,7 @@ static int backward_cf(stcd_engine& e, const float* grad_logits, const float* pa
     // both stages in one call: the grouped weight gradients go out with their last member on the engine's side stream (the head's
     // LDS-DMA group right after the second up-sampling layer's backward) and run beside the rest of the chain
     hipStream_t side = (stage < 0 && cf_side_on()) ? wgrad_side_stream(e, s) : nullptr;
-    EarlyScope early_scope(e, side != nullptr, side);
-    for (int st = 0; st < 2; ++st)
-        if (stage < 0 || stage == st)
-            for (WgradGroup& G : e.wgroups[st]) { G.seen = 0; G.launched = false; }
+    WgradScope wgrad_scope(e, stage, side != nullptr, side);
     if (stage <= 0) {
         STCD_HIP(hipMemsetAsync(grads, 0, e.param_floats * 4, s));
         if (!mfma_on(e)) STCD_HIP(hipMemsetAsync(c.at(e.dwe_begin), 0, e.dwe_end - e.dwe_begin, s));

@@ -967,8 +967,8 @@ WgradMfmaPlan wgrad_mfma_plan(const stcd_conv_geom& g, int kpad, int wld, bool a
     return p;
 }
 
-WgradJob wgrad_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
-                        int kpad, int wld) {
+static WgradJob wgrad_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
+                               int kpad, int wld) {
     WgradJob a;
     memset(&a, 0, sizeof(a));
     a.g = g;
@@ -994,14 +994,8 @@ WgradJob wgrad_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t
     a.wi_valid = p.wi_valid > 0 ? p.wi_valid : g.wi; a.pad_ = 0;
     const int WK = 4 / p.WCI;
     a.lds_bytes = (int)std::max<size_t>(2 * (size_t)(a.x_bytes + a.y_bytes), (size_t)(WK - 1) * p.WCI * 9 * p.NTW * 4 * 64 * 4);
-    a.xf_stat_off = -1; a.xf_mask_off = -1; a.xf_C = 0; a.xf_groups = 1; a.xf_npg = 1; a.pad2_ = 0;     // plain X (wgrad_job_set_xf)
+    a.xf_stat_off = -1; a.xf_mask_off = -1; a.xf_C = 0; a.xf_groups = 1; a.xf_npg = 1; a.pad2_ = 0;     // plain X (wgrad_job)
     return a;
-}
-
-// X of this job is the producer's raw conv output (virtual activation): its published table, masks and BatchNorm groups
-void wgrad_job_set_xf(WgradJob& a, int64_t stat_off, int64_t mask_off, int C, int groups, int npg) {
-    a.xf_stat_off = stat_off; a.xf_mask_off = mask_off; a.xf_C = C; a.xf_groups = groups; a.xf_npg = npg;
-    a.lds_bytes = std::max(a.lds_bytes, 2 * (a.x_bytes + a.y_bytes) + groups * 2 * C * 4);
 }
 
 #define WG_DISPATCH(W_, N_, T_, WHAT)                                       \
@@ -1014,33 +1008,34 @@ void wgrad_job_set_xf(WgradJob& a, int64_t stat_off, int64_t mask_off, int C, in
         else { if (T_) { WHAT(2, 2, true); } else { WHAT(2, 2, false); } }                          \
     } while (0)
 
-int wgrad_variant_slots(int WCI, int NTW, bool t9, int lds_bytes) {
+int wgrad_variant_slots(const WgradKernel& k, int lds_bytes) {
     int dev = 0, cus = 256, per_cu = 2;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return 512; }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
 #define WG_OCC(W_, N_, T_) \
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_wgrad_group<W_, N_, T_>, 256, (size_t)lds_bytes) != hipSuccess) per_cu = 2
-    WG_DISPATCH(WCI, NTW, t9, WG_OCC);
+    WG_DISPATCH(k.WCI, k.NTW, k.t9, WG_OCC);
 #undef WG_OCC
     (void)hipGetLastError();
     return std::max(1, per_cu) * cus;
 }
 
-int launch_wgrad_group(int WCI, int NTW, bool t9, const WgradJob* jobs_dev, int njobs, int total_blocks, int lds_bytes,
-                       const char* base, hipStream_t s, bool xf) {
+// the 64-channel tiles of kernel K_ (two 34-KB X buffers, + two 17-KB dY buffers at 64 x 64) need more than the default 64 KB of LDS
+#define WG_LDS_ATTR(K_)                                                                                                                  \
+    do {                                                                                                                                 \
+        static bool attr_set = false;                                                                                                    \
+        if (!attr_set)                                                                                                                   \
+            for (const void* f : {(const void*)K_<4, 2, true>, (const void*)K_<4, 2, false>, (const void*)K_<4, 4, true>, (const void*)K_<4, 4, false>}) \
+                (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                                    \
+        attr_set = true;                                                                                                                 \
+    } while (0)
+
+static int launch_wgrad_group(int WCI, int NTW, bool t9, const WgradJob* jobs_dev, int njobs, int total_blocks, int lds_bytes,
+                              const char* base, hipStream_t s, bool xf) {
     if (njobs <= 0 || total_blocks <= 0) return 0;
     if (lds_bytes > 128 * 1024) return 1;
-    if (lds_bytes > 64 * 1024) {      // the 64-channel tiles: two 34-KB X buffers (+ two 17-KB dY buffers at 64 x 64)
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)k_wgrad_group<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_group<4, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_group<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_group<4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-    }
+    if (lds_bytes > 64 * 1024) WG_LDS_ATTR(k_wgrad_group);
     if (xf) {      // virtual-activation jobs (opt-in plan): the tile shapes FC-Siam's layers use
 #define WG_GROUP_XF(W_, N_, T_) k_wgrad_group<W_, N_, T_, true><<<(unsigned)total_blocks, 256, (size_t)lds_bytes, s>>>(jobs_dev, njobs, base)
         if (WCI == 4 || NTW == 4) return 1;
@@ -1059,20 +1054,11 @@ int launch_wgrad_mfma(const stcd_conv_geom& g, const WgradMfmaPlan& p, const voi
     if (!p.ok) return 1;
     const WgradJob a = wgrad_make_job(g, p, (int64_t)(intptr_t)in, (int64_t)(intptr_t)dout, (int64_t)(intptr_t)slab, kpad, wld);
     if (a.lds_bytes > 128 * 1024) return 1;
-    if (a.lds_bytes > 64 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)k_wgrad_mfma<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_mfma<4, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_mfma<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)k_wgrad_mfma<4, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-    }
+    if (a.lds_bytes > 64 * 1024) WG_LDS_ATTR(k_wgrad_mfma);
     dim3 grid((unsigned)p.gx, (unsigned)p.gy, (unsigned)p.gz);
-    const bool t9 = g.ntaps == 9;
+    const WgradKernel k = wgrad_kernel_of(p, g, false);
 #define WG_ONE(W_, N_, T_) k_wgrad_mfma<W_, N_, T_><<<grid, 256, (size_t)a.lds_bytes, s>>>(a)
-    WG_DISPATCH(p.WCI, p.NTW, t9, WG_ONE);
+    WG_DISPATCH(k.WCI, k.NTW, k.t9, WG_ONE);
 #undef WG_ONE
     return 0;
 }
@@ -2580,8 +2566,8 @@ WgradMfmaPlan wgrad_gemm_plan(const stcd_conv_geom& g, int kpad, int wld) {
     return p;
 }
 
-WgradJob wgrad_gemm_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
-                             int kpad, int wld) {
+static WgradJob wgrad_gemm_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off, int64_t slab_off,
+                                    int kpad, int wld) {
     WgradJob a;
     memset(&a, 0, sizeof(a));
     a.g = g;
@@ -2597,7 +2583,7 @@ WgradJob wgrad_gemm_make_job(const stcd_conv_geom& g, const WgradMfmaPlan& p, in
     return a;
 }
 
-int launch_wgrad_gemm_group(int W, const WgradJob* jobs_dev, int njobs, int total_blocks, const char* base, hipStream_t s) {
+static int launch_wgrad_gemm_group(int W, const WgradJob* jobs_dev, int njobs, int total_blocks, const char* base, hipStream_t s) {
     if (njobs <= 0 || total_blocks <= 0) return 0;
     const int T = 32 * W;
     const size_t lds = (size_t)2 * 2 * (T / 32) * (64 * 64 + 8 * 32);
@@ -2609,6 +2595,39 @@ int launch_wgrad_gemm_group(int W, const WgradJob* jobs_dev, int njobs, int tota
         k_wgrad_gemm<2><<<(unsigned)total_blocks, 256, lds, s>>>(jobs_dev, njobs, base);
     }
     return 0;
+}
+
+// ---- which weight-gradient kernel: derived here, and named, given its job and launched below; nothing else reads the plan for it
+WgradKernel wgrad_kernel_of(const WgradMfmaPlan& p, const stcd_conv_geom& g, bool xf) {
+    WgradKernel k;
+    if (p.dma) k.kind = WgradKernel::DMA;                    // (one LDS-DMA kernel, whatever the tap count)
+    else if (p.gemm) { k.kind = WgradKernel::GEMM; k.W = p.gemm; }
+    else { k.WCI = p.WCI; k.NTW = p.NTW; k.t9 = g.ntaps == 9; k.xf = xf; }
+    return k;
+}
+bool wgrad_kernel_takes_xf(const WgradKernel& k) { return k.kind == WgradKernel::TILE && k.WCI < 4 && k.NTW < 4; }
+void wgrad_kernel_name(const WgradKernel& k, bool grouped, char out[64]) {
+    if (k.kind == WgradKernel::DMA) snprintf(out, 64, "k_wgrad_dma");
+    else if (k.kind == WgradKernel::GEMM) snprintf(out, 64, "k_wgrad_gemm<%d>", k.W);
+    else if (grouped) snprintf(out, 64, "k_wgrad_group<%d, %d, %s>", k.WCI, k.NTW, k.t9 ? "true" : "false");
+    else snprintf(out, 64, "k_wgrad_mfma<%d, %d>", k.WCI, k.NTW);
+}
+WgradJob wgrad_job(const WgradKernel& k, const stcd_conv_geom& g, const WgradMfmaPlan& p, int64_t in_off, int64_t dout_off,
+                   int64_t slab_off, int kpad, int wld, const WgradXf* xf) {
+    if (k.kind == WgradKernel::DMA) return wgrad_dma_make_job(g, p, in_off, dout_off, slab_off, kpad, wld);
+    if (k.kind == WgradKernel::GEMM) return wgrad_gemm_make_job(g, p, in_off, dout_off, slab_off, kpad, wld);
+    WgradJob a = wgrad_make_job(g, p, in_off, dout_off, slab_off, kpad, wld);
+    if (k.xf && xf) {      // X is the producer's raw conv output (virtual activation): its published table, masks and BatchNorm groups
+        a.xf_stat_off = xf->stat_off; a.xf_mask_off = xf->mask_off; a.xf_C = xf->C; a.xf_groups = xf->groups; a.xf_npg = xf->npg;
+        a.lds_bytes = std::max(a.lds_bytes, 2 * (a.x_bytes + a.y_bytes) + xf->groups * 2 * xf->C * 4);
+    }
+    return a;
+}
+int launch_wgrad_jobs(const WgradKernel& k, const WgradJob* jobs_dev, int njobs, int total_blocks, int lds_bytes, const char* base,
+                      hipStream_t s) {
+    if (k.kind == WgradKernel::DMA) return launch_wgrad_dma_group(jobs_dev, njobs, total_blocks, base, s);
+    if (k.kind == WgradKernel::GEMM) return launch_wgrad_gemm_group(k.W, jobs_dev, njobs, total_blocks, base, s);
+    return launch_wgrad_group(k.WCI, k.NTW, k.t9, jobs_dev, njobs, total_blocks, lds_bytes, base, s, k.xf);
 }
 
 }  // namespace stcd
