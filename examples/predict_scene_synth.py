@@ -35,6 +35,8 @@ parser.add_argument("--vector", type=str, default="", metavar="OUT.geojson",
                     help="also write the predicted change objects as GeoJSON polygons (pixel coordinates)")
 parser.add_argument("--min_area", type=int, default=4, help="with --vector: objects below this many pixels are dropped")
 parser.add_argument("--max_hole", type=int, default=4, help="with --vector: holes of at most this many pixels are filled")
+parser.add_argument("--simplify", type=float, default=None, metavar="TOL",
+                    help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5")
 
 
 def main(argv=None):
@@ -68,6 +70,10 @@ def main(argv=None):
         clean = objects.filter_objects(res.mask.contiguous(), args.min_area, args.max_hole)
         comp = objects.label_components(clean)
         rings = objects.object_rings(comp)
+        traced = int(rings.vertices.shape[0])
+        if args.simplify is not None:
+            rings = objects.simplify_rings(rings, tolerance=args.simplify)
+            print(f"simplified at {args.simplify} px (Douglas-Peucker on the device): {traced} vertices before, {int(rings.vertices.shape[0])} after")
         doc = objects.rings_to_geojson(rings, path=args.vector, properties=objects.object_table(comp))
         print(f"{len(doc['features'])} polygons ({rings.count} rings, {int(rings.vertices.shape[0])} vertices) written to {args.vector}")
     return res

@@ -571,6 +571,46 @@ int stcd_rings_count(const int32_t* labels, int height, int width, int connectiv
 int stcd_rings_write(const int32_t* labels, int height, int width, int connectivity, int64_t max_corners, int64_t n_rings, int64_t n_vertices,
                      int32_t* vertices, int64_t* offsets, int32_t* object, int64_t* area2, void* scratch, int64_t scratch_bytes, void* hip_stream);
 
+/* ---- ring simplification: Douglas-Peucker over rings in the layout above (vertices int32 [V,2] = (y, x), offsets int64 [R+1]),
+ *      on the device, with exact integer arithmetic.  tests/simplify_spec.py states every output.  The tolerance travels as
+ *      q = floor(4 * tolerance^2), 0 <= q < 2^31 (tolerances 1.0, 1.5, 2.0: q = 4, 9, 16); coordinates must lie in [0, 16384], so
+ *      that every key below is at most 2^58.  For one ring P[0..n-1], P[n] = P[0]:
+ *        1. key(p, a, b) = d^2 * L', d the distance of p from the SEGMENT (a, b), L = |b - a|^2, L' = L or 1 when L == 0: with
+ *           e = p - a, d = b - a, t = e.d:  t <= 0: |p - a|^2 * L;  t >= L: |p - b|^2 * L;  else cross(e, d)^2;  L == 0: |p - a|^2.
+ *        2. anchors: vertex 0 and the vertex a1 of largest |P - P[0]|^2 (lowest index on ties); chains [0, a1] and [a1, n].
+ *        3. on a chain [i, j] with j - i >= 2 the interior vertex k of largest key against (P[i], P[j]), lowest index on ties, is
+ *           kept if 4 * key > q * L', and [i, k] and [k, j] are treated the same way; otherwise every interior vertex is dropped.
+ *        4. if nothing but the anchors was kept, the vertex of largest key against (P[0], P[a1]) among all others (lowest index on
+ *           ties) is kept too, whatever its key: at least a triangle.
+ *        5. area2 (the formula of stcd_rings_write) of the kept vertices is 0, or differs in sign from that of the input ring as
+ *           recomputed from its vertices: the ring is copied whole.  So a hole stays a hole and an outer ring an outer ring.  Rings
+ *           of fewer than 4 vertices are copied whole.
+ *      The result keeps the ring count and order, every ring a subsequence of its input in travel order with the first vertex still
+ *      first; q == 0 drops only vertices that lie on the segment between their kept neighbours (none on a traced ring).  Topology
+ *      is NOT protected: a simplified hole may touch or cross its exterior and two objects' polygons may overlap by up to the
+ *      tolerance.
+ *      Every ring iterates the levels of step 3 inside one kernel (a wavefront per ring up to 64 vertices, a block per longer
+ *      ring, its state in LDS up to 2048 vertices and in the scratch buffer above): no launch and no host read per level, no
+ *      thread walks a chain.  Two phases with one host read between them, as for the rings; the scratch buffer carries the state.
+ *      Neither entry allocates, copies to the host or synchronises.
+ *      Status word: 0, or bits 1: a coordinate outside [0, 16384], 2: a ring reached the round cap of n (a bug, never a property
+ *      of the input), 4: offsets that do not start at 0, do not ascend or do not end at n_vertices (nothing of such a ring is read),
+ *      8 (write entry, in the scratch header only, scratch byte 24): n_out is not what the count phase left. ---- */
+/* Bytes of the scratch buffer of the two entries below (8-byte aligned): 48 + 29 per vertex + 12 per ring + 8 per 4096 vertices; 0
+ * for arguments they refuse (negative, or 2^31 and above). */
+int64_t stcd_rings_simplify_scratch_bytes(int64_t n_rings, int64_t n_vertices);
+/* counts: int64 [2] on the device = (V', status): the vertices that remain.  Refused before any launch: null pointers, negative
+ * counts or counts of 2^31 and above, q outside [0, 2^31), misaligned pointers (8 bytes), a scratch buffer that is too small. */
+int stcd_rings_simplify_count(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t q,
+                              int64_t* counts, void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* After stcd_rings_simplify_count on the same rings and scratch, with the V' it left as n_out: out_vertices int32 [n_out,2],
+ * out_offsets int64 [R+1], out_area2 int64 [R], recomputed from the vertices that remain.  Refused before any launch: what the
+ * count entry refuses, n_out < 0 and n_out > n_vertices.  An n_out that passes those checks but is not the count phase's own (or a
+ * count phase that left a status, or other ring sizes) is found on the device: nothing is written and bit 8 is set. */
+int stcd_rings_simplify_write(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t q, int64_t n_out,
+                              int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, void* scratch, int64_t scratch_bytes,
+                              void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

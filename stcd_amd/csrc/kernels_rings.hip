@@ -32,10 +32,11 @@
 #include <climits>
 
 #include "common.h"
+#include "ring_scan.h"                         // rg_wave_scan, rg_block_scan
 
 namespace stcd {
 
-#define RG_CHUNK 4096                          // vertices (corners in the write phase) per block of the scans: 256 threads x 16
+#define RG_CHUNK 4096                         // vertices (corners in the write phase) per block of the scans: 256 threads x 16
 #define RG_MAX_GRID 2048                       // blocks of the grid-stride passes over the corners (Guideline 11)
 
 enum { RG_ST_WALK = 1, RG_ST_LINK = 2, RG_ST_CAPACITY = 4, RG_ST_MISMATCH = 8 };
@@ -87,15 +88,6 @@ __device__ __forceinline__ void rg_advance(RgCursor& c, int Wp) {
     if (c.x >= Wp) { c.x -= Wp; ++c.y; }
 }
 
-__device__ __forceinline__ long long rg_wave_scan(long long v, int lane) {      // inclusive
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------------ count phase: numbering
 __global__ void __launch_bounds__(256)
 k_ring_count(const int* __restrict__ lab, int H, int W, int64_t NV, long long* __restrict__ sums) {
@@ -113,26 +105,6 @@ k_ring_count(const int* __restrict__ lab, int H, int W, int64_t NV, long long* _
     if (lane == 0) wsum[wave] = n;
     __syncthreads();
     if (threadIdx.x == 0) sums[blockIdx.x] = (long long)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-}
-
-// one block: a[stride * i] becomes the sum of the entries before i; returns the total (to every thread)
-__device__ __forceinline__ long long rg_block_scan(long long* __restrict__ a, int64_t n, int stride, long long* ws) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    long long carry = 0;
-    for (int64_t base = 0; base < n; base += 256) {                    // uniform
-        const int64_t i = base + threadIdx.x;
-        const long long v = i < n ? a[stride * i] : 0;
-        const long long inc = rg_wave_scan(v, lane);
-        if (lane == 63) ws[wave] = inc;
-        __syncthreads();
-        long long before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { if (w < wave) before += ws[w]; total += ws[w]; }
-        if (i < n) a[stride * i] = carry + before + inc - v;
-        carry += total;
-        __syncthreads();                                               // ws is written again
-    }
-    return carry;
 }
 
 __global__ void __launch_bounds__(256)

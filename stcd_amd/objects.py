@@ -8,12 +8,15 @@ stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_
 
 ``object_rings`` goes on from numbered objects to vector data: the boundary rings of every object with their holes, on the device
 (stcd_amd/csrc/kernels_rings.hip behind ``stcd_rings_count`` and ``stcd_rings_write``; tests/rings_spec.py is the specification),
-and ``rings_to_geojson`` writes them as polygons on the host.
+``simplify_rings`` thins them with Douglas-Peucker, still on the device (stcd_amd/csrc/kernels_simplify.hip behind
+``stcd_rings_simplify_count`` and ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification), and
+``rings_to_geojson`` writes either as polygons on the host.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -24,8 +27,10 @@ from ._lib import StcdError
 from .selftrain import _check_mask
 
 TILE = 64               # the tile pass labels TILE x TILE pixels per block (OBJ_TILE of kernels_objects.hip): where the seams lie
+SIMPLIFY_WAVE_MAX = 64     # the longest ring one wavefront simplifies (SM_WAVE_MAX of kernels_simplify.hip); a block takes longer ones
+SIMPLIFY_LDS_MAX = 2048     # the longest ring whose state the block keeps in LDS (SM_LDS_MAX); above it the state is in global memory
 
-_SCRATCH = {}           # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
+_SCRATCH = {}          # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
 
 
 class Components(NamedTuple):
@@ -232,6 +237,69 @@ def object_rings(components: Components, connectivity: int = 8, max_corners: Opt
     return Rings(vertices, offsets, obj, area2, R)
 
 
+def simplify_q(tolerance) -> int:
+    """The integer the kernels compare with: ``floor(4 * tolerance**2)``, clamped to ``2**31 - 1`` (1.0, 1.5, 2.0 give 4, 9, 16)."""
+    t = float(tolerance)
+    if not t >= 0.0:
+        raise StcdError(f"tolerance must be >= 0, got {tolerance!r}")
+    v = 4.0 * t * t
+    return 2 ** 31 - 1 if v >= 2 ** 31 - 1 else int(math.floor(v))
+
+
+def _check_rings(rings):
+    vertices, offsets, obj, area2, R = rings.vertices, rings.offsets, rings.object, rings.area2, int(rings.count)
+    for t, dtype, name in ((vertices, torch.int32, "vertices"), (offsets, torch.int64, "offsets"), (obj, torch.int32, "object"), (area2, torch.int64, "area2")):
+        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != vertices.device:
+            raise StcdError(f"rings.{name} must be a contiguous {str(dtype).split('.')[-1]} tensor on the GPU, all four on one device")
+    if vertices.dim() != 2 or vertices.shape[1] != 2 or R < 0 or tuple(offsets.shape) != (R + 1,) or tuple(obj.shape) != (R,) or tuple(area2.shape) != (R,):
+        raise StcdError("rings: vertices must be [V,2], offsets [count+1], object and area2 [count]")
+    if vertices.shape[0] >= 2 ** 31 or R >= 2 ** 31:
+        raise StcdError("rings: 2^31 vertices or rings and more are not supported")
+    return vertices, offsets, obj, R, int(vertices.shape[0])
+
+
+def simplify_rings(rings: Rings, tolerance: float = 1.5) -> Rings:
+    """Douglas-Peucker over every ring of ``rings`` (``object_rings``' result, or any ``Rings`` with int32 ``(y, x)`` vertices in
+    ``[0, 16384]``), on the device: a new ``Rings`` with the same ``count``, ``object`` and ring order, every ring a subsequence of
+    its input in travel order with the first vertex still first, ``area2`` recomputed from the vertices that remain.  The rule set
+    is integer arithmetic on ``simplify_q(tolerance)`` (include/stcd_hip.h, ``stcd_rings_simplify_count`` /
+    ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification and the device equals it to the bit): two anchors per
+    ring, the largest distance from the segment first with the lowest index on ties, a triangle at the least, and a ring whose
+    simplified area is 0 or has changed its sign is returned whole, so that a hole stays a hole and an outer ring an outer ring.
+    ``tolerance`` is in pixels; 0 returns the rings of ``object_rings`` bit for bit.
+
+    Douglas-Peucker does not protect topology: a simplified hole may touch or cross its exterior, and the polygons of two objects
+    may overlap by up to the tolerance.  Orthogonalising building outlines is out of scope.
+
+    One host read, of the new vertex count and a status word (16 bytes), between the two phases."""
+    q = simplify_q(tolerance)
+    vertices, offsets, obj, R, V = _check_rings(rings)
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        if R == 0:
+            return Rings(torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                         torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), 0)
+        nbytes = int(_lib.lib().stcd_rings_simplify_scratch_bytes(R, V))
+        key = (str(dev), "simplify", nbytes)
+        scratch = _SCRATCH.get(key)
+        if scratch is None:
+            scratch = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_rings_simplify_count(_ptr(vertices), _ptr(offsets), R, V, q, _ptr(counts), _ptr(scratch), scratch.numel(),
+                                                        _stream(dev)))
+        n_out, status = (int(v) for v in counts.cpu().numpy())
+        if status:
+            raise StcdError(f"simplify_rings: the count phase reports status {status} (bit 1: a coordinate outside [0, 16384], bit 4: offsets that "
+                            "do not ascend from 0 to the vertex count; bit 2: a ring reached its round cap, which is a bug in the kernels, "
+                            "not a property of the rings)")
+        out_vertices = torch.empty((n_out, 2), dtype=torch.int32, device=dev)
+        out_offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        out_area2 = torch.empty(R, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_rings_simplify_write(_ptr(vertices), _ptr(offsets), R, V, q, n_out, _ptr(out_vertices), _ptr(out_offsets),
+                                                        _ptr(out_area2), _ptr(scratch), scratch.numel(), _stream(dev)))
+    return Rings(out_vertices, out_offsets, obj.clone(), out_area2, R)
+
+
 def _host_array(x, dtype):
     if torch.is_tensor(x):
         x = x.detach().cpu().numpy()
@@ -250,7 +318,8 @@ def rings_to_geojson(rings, path=None, transform=None, properties: Optional[Obje
     exterior is counter-clockwise with and without a transform.  ``properties``, an ``ObjectTable`` of the same
     components, adds ``area``, ``bbox`` and, where present, ``overlap`` to each feature's ``label``.  An object with more than one
     outer ring raises ``StcdError``: that happens only when the labels were made with connectivity 8 and the rings with 4.
-    The rings are exact pixel outlines; simplification (Douglas-Peucker) is out of scope."""
+    The rings are written as they come: exact pixel outlines from ``object_rings``, thinned ones from ``simplify_rings``
+    (Douglas-Peucker on the device), whose result this takes unchanged."""
     vertices = _host_array(rings.vertices, np.int64).reshape(-1, 2)
     offsets = _host_array(rings.offsets, np.int64).reshape(-1)
     obj = _host_array(rings.object, np.int64).reshape(-1)
