@@ -36,7 +36,10 @@ parser.add_argument("--vector", type=str, default="", metavar="OUT.geojson",
 parser.add_argument("--min_area", type=int, default=4, help="with --vector: objects below this many pixels are dropped")
 parser.add_argument("--max_hole", type=int, default=4, help="with --vector: holes of at most this many pixels are filled")
 parser.add_argument("--simplify", type=float, default=None, metavar="TOL",
-                    help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5")
+                    help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5; "
+                         "the polygons are then rasterized again (objects.rasterize_rings) and scored against the mask they came from")
+parser.add_argument("--vector_label", type=str, default="", metavar="IN.geojson",
+                    help="read the label from GeoJSON polygons in pixel coordinates (objects.geojson_to_rings + rasterize_rings) instead of the synthetic one")
 
 
 def main(argv=None):
@@ -51,6 +54,13 @@ def main(argv=None):
     if args.load_path:
         model.load_state_dict(torch.load(args.load_path, map_location="cpu"))
     model.to(dev)
+
+    if args.vector_label:
+        # vector ground truth: the polygons (pixel coordinates) rasterized on the device replace the synthetic label
+        from stcd_amd import objects
+        truth = objects.geojson_to_rings(args.vector_label, device=dev)
+        label = objects.rasterize_rings(truth, (args.size, args.size), mask_value=1).mask
+        print(f"label from {args.vector_label}: {truth.count} rings, {int(truth.vertices.shape[0])} vertices, {int(label.sum())} labelled pixels")
 
     plan = plan_tiles(args.size, args.size, args.tile, args.stride)
     t0 = time.perf_counter()
@@ -74,6 +84,11 @@ def main(argv=None):
         if args.simplify is not None:
             rings = objects.simplify_rings(rings, tolerance=args.simplify)
             print(f"simplified at {args.simplify} px (Douglas-Peucker on the device): {traced} vertices before, {int(rings.vertices.shape[0])} after")
+            # what the tolerance cost in pixels: the polygons rasterized again, with the mask they came from as overlay
+            from stcd_amd.metrics import scores_from_cm
+            cm = objects.rasterize_rings(rings, clean.shape, overlay=(clean != 0).to(torch.uint8)).cm.cpu().numpy()      # 0 / 1: an overlay byte of 255 is ignored
+            fid = scores_from_cm(cm)
+            print(f"polygons against their mask: {int(cm[0, 1] + cm[1, 0])} pixels differ, IoU {fid['iou'][1]:.4f}, F1 {fid['f1'][1]:.4f}")
         doc = objects.rings_to_geojson(rings, path=args.vector, properties=objects.object_table(comp))
         print(f"{len(doc['features'])} polygons ({rings.count} rings, {int(rings.vertices.shape[0])} vertices) written to {args.vector}")
     return res

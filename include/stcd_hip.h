@@ -611,6 +611,46 @@ int stcd_rings_simplify_write(const int32_t* vertices, const int64_t* offsets, i
                               int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, void* scratch, int64_t scratch_bytes,
                               void* hip_stream);
 
+/* ---- ring rasterization: rings in the layout above (vertices int32 [V,2] = (y, x) lattice corners in [0, 16384], offsets int64
+ *      [R+1], ring r closed implicitly: edges from vertex k to vertex k + 1 mod n) back to a uint8 mask of height x width pixels at
+ *      the origin, 1 <= height, width <= 16384, on the device, with exact integer arithmetic.  tests/raster_spec.py states every
+ *      output.  Pixel (i, j) is the unit square between (i, j) and (i + 1, j + 1), sampled at its centre (i + 1/2, j + 1/2).
+ *        1. an edge with y0 == y1 contributes nothing.  Another edge is taken with y0 < y1, dy = y1 - y0, and sign s = +1 if it ran
+ *           north as stored (y1 < y0 before the swap), else -1.  It touches row i iff y0 <= i < y1 and 0 <= i < height: a row's
+ *           centre line never passes through a lattice vertex, so there are no vertex cases.
+ *        2. in row i it toggles column j* = floor((num + dy - 1) / (2 dy)), num = 2 x0 dy + (x1 - x0) (2 i + 1 - 2 y0) (twice dy
+ *           times the x of the crossing, 0 <= num <= 2^29): the first j with j + 1/2 >= crossing, so a centre ON an edge counts as
+ *           right of it; j* is clamped to [0, width], and column `width` is outside the frame.  delta[i][j*] += s.
+ *        3. the winding number w[i][j] is the sum of delta[i][0..j]: for the rings of stcd_rings_write (outer ring area2 > 0, hole
+ *           < 0) it is 1 inside an object and 0 elsewhere.
+ *        4. rule 0 (positive): a pixel is set iff w > 0, the union of overlapping polygons with holes subtracted; rule 1 (evenodd):
+ *           iff w is odd, for foreign rings whose orientation means nothing.
+ *      So parts of a ring beyond the frame are clipped exactly, a ring of fewer than 3 vertices or one that runs out and back along
+ *      a line cancels itself, and two polygons that share an edge partition the pixels along it.
+ *      One clear (hipMemsetAsync of the scratch buffer, on every call) and two kernels on the caller's stream; the entry neither
+ *      allocates nor reads anything back.  k_raster_edges: a thread per edge finds its ring by binary search in offsets, clips the
+ *      row span to [0, height) before any loop and adds s with a 32-bit integer atomic that returns nothing; a lane walks its own
+ *      edge up to 32 rows, longer edges are collected per wavefront and its 64 lanes stride over the rows of each; no thread walks a
+ *      ring.  k_raster_scan: a wavefront per row sums delta in chunks of 1024 columns with a carried sum, applies the rule, writes
+ *      the mask (16-byte stores when width % 16 == 0 and mask / overlay are 16-byte aligned, bytes otherwise) and counts cm.
+ *      Integer atomics are order-free: every output is a pure function of the input.
+ *      Status word, the FIRST 4 bytes of the scratch buffer: 0, or bits 1: a coordinate outside [0, 16384] (the edge is skipped),
+ *      4: offsets that do not start at 0, do not ascend or do not end at n_vertices (nothing of such a ring is read).  Where it is
+ *      set the mask contents are unspecified. ---- */
+/* Bytes of the scratch buffer of the entry below (8-byte aligned): 16 (the header) + 4 * height * (width + 1) (the delta plane,
+ * int32 [height][width + 1]), rounded up to a multiple of 8; 0 for a height or width outside [1, 16384]. */
+int64_t stcd_rings_raster_scratch_bytes(int height, int width);
+/* mask: uint8 [height,width] on the device, mask_value (1..255) where set, else 0.  overlay / cm: both or neither; overlay uint8
+ * [height,width] (>= 1 is set, 255 is ignored), cm int64 [4] on the device, cm[2 * overlay_set + raster_set] += count over the
+ * pixels that are not ignored: counts are ADDED to what cm holds, reduced per wave and block before one 64-bit integer atomic per
+ * block and counter.  Refused before any HIP call: null pointers (overlay and cm aside, and vertices when n_vertices == 0), overlay without cm or cm without overlay,
+ * negative counts or counts of 2^31 and above, height / width outside [1, 16384], a rule other than 0 / 1, mask_value outside
+ * [1, 255], vertices / offsets / cm / scratch not 8-byte aligned, a scratch buffer that is too small.  n_rings == 0 or
+ * n_vertices == 0 writes an all-zero mask (and still counts cm).  mask and cm must not overlap scratch. */
+int stcd_rings_raster(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int height, int width,
+                      int rule, int mask_value, const uint8_t* overlay, int64_t* cm, uint8_t* mask, void* scratch, int64_t scratch_bytes,
+                      void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

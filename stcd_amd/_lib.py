@@ -174,6 +174,8 @@ _PROTOS = {
     "stcd_rings_simplify_scratch_bytes": (_i64, [_i64, _i64]),
     "stcd_rings_simplify_count": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "stcd_rings_simplify_write": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_rings_raster_scratch_bytes": (_i64, [_i, _i]),
+    "stcd_rings_raster": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv_fused": (_i, [C.POINTER(ConvGeom), C.POINTER(ConvFused), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),

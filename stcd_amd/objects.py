@@ -10,7 +10,9 @@ stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_
 (stcd_amd/csrc/kernels_rings.hip behind ``stcd_rings_count`` and ``stcd_rings_write``; tests/rings_spec.py is the specification),
 ``simplify_rings`` thins them with Douglas-Peucker, still on the device (stcd_amd/csrc/kernels_simplify.hip behind
 ``stcd_rings_simplify_count`` and ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification), and
-``rings_to_geojson`` writes either as polygons on the host.
+``rings_to_geojson`` writes either as polygons on the host.  ``rasterize_rings`` goes the other way, from rings to a mask on the
+device (stcd_amd/csrc/kernels_raster.hip behind ``stcd_rings_raster``; tests/raster_spec.py is the specification), with the
+confusion counts against an overlay in the same pass, and ``geojson_to_rings`` reads polygons back on the host.
 """
 from __future__ import annotations
 
@@ -29,8 +31,10 @@ from .selftrain import _check_mask
 TILE = 64               # the tile pass labels TILE x TILE pixels per block (OBJ_TILE of kernels_objects.hip): where the seams lie
 SIMPLIFY_WAVE_MAX = 64     # the longest ring one wavefront simplifies (SM_WAVE_MAX of kernels_simplify.hip); a block takes longer ones
 SIMPLIFY_LDS_MAX = 2048     # the longest ring whose state the block keeps in LDS (SM_LDS_MAX); above it the state is in global memory
+RASTER_SPAN_MAX = 32     # the longest clipped row span of an edge one lane rasterizes alone (RS_SPAN_MAX of kernels_raster.hip); a wavefront strides over longer ones
+RASTER_ROW_CHUNK = 1024     # columns of a row a wavefront scans per step with a carried sum (RS_ROW_CHUNK)
 
-_SCRATCH = {}          # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
+_SCRATCH = {}         # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
 
 
 class Components(NamedTuple):
@@ -50,6 +54,11 @@ class Rings(NamedTuple):
     object: torch.Tensor                # int32 [count] on the device: the label of the ring's object
     area2: torch.Tensor                 # int64 [count] on the device: twice the signed area, > 0 outer ring, < 0 hole
     count: int
+
+
+class Raster(NamedTuple):
+    mask: torch.Tensor                  # uint8 [H,W] on the device
+    cm: Optional[torch.Tensor]          # int64 [2,2] on the device, cm[label, pred], None without an overlay
 
 
 class ObjectScores(NamedTuple):
@@ -372,6 +381,162 @@ def rings_to_geojson(rings, path=None, transform=None, properties: Optional[Obje
         with open(path, "w") as fh:
             json.dump(collection, fh)
     return collection
+
+
+_RASTER_RULES = {"positive": 0, "evenodd": 1}
+
+
+def rasterize_rings(rings: Rings, shape, rule: str = "positive", mask_value: int = 255, overlay: Optional[torch.Tensor] = None,
+                    check: bool = True) -> Raster:
+    """The rings of ``rings`` (``object_rings``' or ``simplify_rings``' result, or any ``Rings`` on the GPU with int32 ``(y, x)``
+    vertices in ``[0, 16384]``, ``geojson_to_rings``' among them) back to pixels: a new uint8 mask of ``shape = (H, W)``,
+    ``1 <= H, W <= 16384``, holding ``mask_value`` where set, on the device.  Pixel ``(i, j)`` is sampled at its centre; the rule is
+    exact integer arithmetic (include/stcd_hip.h, ``stcd_rings_raster``; tests/raster_spec.py is the specification and the device
+    equals it to the bit): every edge adds its sign to a delta plane at the first column whose centre is not left of it, a row's
+    running sum is the winding number ``w``, and a pixel is set where ``w > 0`` (``rule="positive"``: the union of overlapping
+    polygons, holes subtract) or where ``w`` is odd (``rule="evenodd"``: for foreign rings whose orientation means nothing).  Parts
+    of a ring beyond the frame are clipped exactly; ``rasterize_rings(object_rings(c), c.labels.shape).mask`` is ``(c.labels > 0) * 255``.
+    ``rings.object`` and ``rings.area2`` are not read.
+
+    With an ``overlay`` (uint8 ``[H,W]`` on the same device, >= 1 is set, 255 is ignored) the same pass counts ``cm`` int64
+    ``[2,2]``, ``cm[overlay, raster]``, freshly zeroed per call: ``metrics.scores_from_cm(r.cm.cpu().numpy())`` scores the polygons
+    against the overlay, and ``cm[0, 1] + cm[1, 0]`` is the number of pixels that differ.  A mask that marks its objects with 255
+    is all "ignored" as an overlay: pass ``(mask != 0).to(torch.uint8)``.
+
+    ``check=True`` reads the 4-byte status word afterwards and raises ``StcdError`` naming the bit (1: a coordinate outside
+    ``[0, 16384]``, 4: offsets that do not ascend from 0 to the vertex count); ``check=False`` synchronises nothing."""
+    vertices, offsets, obj, R, V = _check_rings(rings)
+    try:
+        H, W = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise StcdError(f"shape must be (height, width), got {shape!r}") from None
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise StcdError(f"shape must lie in [1, 16384] x [1, 16384], got {(H, W)}")
+    if rule not in _RASTER_RULES:
+        raise StcdError(f"rule must be 'positive' or 'evenodd', got {rule!r}")
+    if not 1 <= int(mask_value) <= 255:
+        raise StcdError(f"mask_value must be in [1, 255], got {mask_value}")
+    dev = vertices.device
+    if overlay is not None:
+        _check_mask(overlay, "overlay", (H, W), dev)
+    with torch.cuda.device(dev):
+        mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        cm = None if overlay is None else torch.zeros((2, 2), dtype=torch.int64, device=dev)
+        nbytes = int(_lib.lib().stcd_rings_raster_scratch_bytes(H, W))
+        key = (str(dev), "raster", nbytes)
+        scratch = _SCRATCH.get(key)
+        if scratch is None:
+            scratch = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().stcd_rings_raster(_ptr(vertices), _ptr(offsets), R, V, H, W, _RASTER_RULES[rule], int(mask_value), _ptr(overlay),
+                                                _ptr(cm), _ptr(mask), _ptr(scratch), scratch.numel(), _stream(dev)))
+        if check:
+            status = int(scratch[:4].cpu().numpy().view(np.int32)[0])
+            if status:
+                raise StcdError(f"rasterize_rings: status {status} (bit 1: a coordinate outside [0, 16384], bit 4: offsets that do not ascend "
+                                "from 0 to the vertex count); the mask is not valid")
+    return Raster(mask, cm)
+
+
+def _geojson_polygons(doc):
+    """``[(properties or None, [polygon, ...])]``, one entry per feature, a polygon being its list of rings."""
+    kind = doc.get("type") if isinstance(doc, dict) else None
+    if kind == "FeatureCollection":
+        features = doc.get("features")
+        if not isinstance(features, list):
+            raise StcdError("geojson_to_rings: a FeatureCollection needs a list of features")
+    elif kind == "Feature":
+        features = [doc]
+    elif kind in ("Polygon", "MultiPolygon"):
+        features = [{"type": "Feature", "properties": None, "geometry": doc}]
+    else:
+        raise StcdError(f"geojson_to_rings: expected a FeatureCollection, Feature, Polygon or MultiPolygon, got type {kind!r}")
+    out = []
+    for k, feat in enumerate(features):
+        geom = feat.get("geometry") if isinstance(feat, dict) and feat.get("type") == "Feature" else None
+        kind = geom.get("type") if isinstance(geom, dict) else None
+        if kind == "Polygon":
+            polys = [geom.get("coordinates")]
+        elif kind == "MultiPolygon":
+            polys = geom.get("coordinates")
+        else:
+            raise StcdError(f"geojson_to_rings: feature {k} holds {kind!r}: only Polygon and MultiPolygon are read (lines and points are out of scope)")
+        if not isinstance(polys, list) or not all(isinstance(p, list) for p in polys):
+            raise StcdError(f"geojson_to_rings: feature {k} has no coordinate lists")
+        out.append((feat.get("properties"), polys))
+    return out
+
+
+def geojson_to_rings(doc_or_path, transform=None, device=None) -> Rings:
+    """The host-side inverse of ``rings_to_geojson``: a GeoJSON ``FeatureCollection``, ``Feature``, ``Polygon`` or ``MultiPolygon``
+    (a dict, or the path of a file) as a ``Rings``, ready for ``rasterize_rings``.  ``device=None`` returns CPU tensors (which
+    ``rings_to_geojson`` accepts), otherwise the tensors are put on ``device``.
+
+    Each ring loses its repeated closing vertex; every coordinate ``[x', y']`` goes back through the inverse of ``transform``
+    (the six numbers ``(a, b, c, d, e, f)`` of ``rings_to_geojson``: ``x' = a x + b y + c``, ``y' = d x + e y + f``; singular is an
+    error) and is rounded to the pixel lattice as ``floor(v + 1/2)``.  ROUNDING MOVES A FOREIGN VERTEX BY UP TO HALF A PIXEL in x
+    and in y; sub-pixel vertices are out of scope, as are lines and points.  The first ring of a polygon becomes an outer ring and
+    the others holes: ``area2`` is recomputed with the project's formula (the sum of ``x_t y_h - x_h y_t``, > 0 for an outer
+    ring) and a ring whose sign disagrees with its role is reversed with its first vertex kept first, which is exactly what
+    undoes ``rings_to_geojson``'s reversal under a north-up transform.  Rings whose rounded ``area2`` is 0 are dropped; a
+    coordinate that lands outside ``[0, 16384]`` (or is not finite) raises ``StcdError``.  Rings come in document order: per
+    feature, per polygon, the outer ring and then its holes.  ``object`` is the feature's ``properties["label"]`` when every
+    feature has a positive integer one, else the feature's index plus 1; the polygons of a ``MultiPolygon`` share it."""
+    doc = doc_or_path
+    if not isinstance(doc, dict):
+        with open(doc_or_path) as fh:
+            doc = json.load(fh)
+    inv = None
+    if transform is not None:
+        try:
+            a, b, c, d, e, f = (float(v) for v in transform)
+        except (TypeError, ValueError):
+            raise StcdError(f"geojson_to_rings: transform must be six numbers (a, b, c, d, e, f), got {transform!r}") from None
+        det = a * e - b * d
+        if not (math.isfinite(det) and det != 0.0 and all(math.isfinite(v) for v in (c, f))):
+            raise StcdError(f"geojson_to_rings: the transform {tuple(transform)} is singular")
+        inv = (a, b, c, d, e, f, det)
+    features = _geojson_polygons(doc)
+    labels = []
+    for props, _ in features:
+        lab = props.get("label") if isinstance(props, dict) else None
+        labels.append(lab if isinstance(lab, int) and not isinstance(lab, bool) and 0 < lab < 2 ** 31 else None)
+    if any(lab is None for lab in labels):
+        labels = list(range(1, len(features) + 1))
+    verts, offs, objs, area2 = [], [0], [], []
+    for k, (_, polys) in enumerate(features):
+        for poly in polys:
+            for role, coords in enumerate(poly):
+                try:
+                    pts = [(float(p[0]), float(p[1])) for p in coords]
+                except (TypeError, ValueError, IndexError):
+                    raise StcdError(f"geojson_to_rings: feature {k} has a ring that is not a list of [x, y] positions") from None
+                if len(pts) > 1 and pts[-1] == pts[0]:
+                    pts.pop()
+                ring = []
+                for x, y in pts:
+                    if inv is not None:
+                        a, b, c, d, e, f, det = inv
+                        x, y = (e * (x - c) - b * (y - f)) / det, (a * (y - f) - d * (x - c)) / det
+                    if not (math.isfinite(x) and math.isfinite(y)):
+                        raise StcdError(f"geojson_to_rings: feature {k} has a coordinate that is not finite")
+                    yi, xi = math.floor(y + 0.5), math.floor(x + 0.5)
+                    if not (0 <= yi <= 16384 and 0 <= xi <= 16384):
+                        raise StcdError(f"geojson_to_rings: feature {k} has a vertex at (y, x) = ({yi}, {xi}), outside [0, 16384]")
+                    ring.append((yi, xi))
+                a2 = sum(xt * yh - xh * yt for (yt, xt), (yh, xh) in zip(ring, ring[1:] + ring[:1]))
+                if a2 == 0:
+                    continue
+                if (a2 > 0) != (role == 0):
+                    ring, a2 = ring[:1] + ring[:0:-1], -a2
+                verts.extend(ring)
+                offs.append(len(verts))
+                objs.append(labels[k])
+                area2.append(a2)
+    out = Rings(torch.from_numpy(np.asarray(verts, np.int32).reshape(-1, 2)), torch.from_numpy(np.asarray(offs, np.int64)),
+                torch.from_numpy(np.asarray(objs, np.int32)), torch.from_numpy(np.asarray(area2, np.int64)), len(objs))
+    if device is not None:
+        out = Rings(*(t.to(device) for t in out[:4]), out.count)
+    return out
 
 
 def score_tables(pred_overlap: np.ndarray, label_overlap: np.ndarray, min_overlap: float = 0.5):
