@@ -38,8 +38,19 @@ parser.add_argument("--max_hole", type=int, default=4, help="with --vector: hole
 parser.add_argument("--simplify", type=float, default=None, metavar="TOL",
                     help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5; "
                          "the polygons are then rasterized again (objects.rasterize_rings) and scored against the mask they came from")
+parser.add_argument("--boundary", type=float, default=None, metavar="T",
+                    help="also print boundary precision, recall and F1 at T pixels and the Hausdorff distance of the prediction against the "
+                         "label (distance.boundary_scores); with --vector ... --simplify the same scores of the simplified polygons' raster "
+                         "against the mask they came from")
 parser.add_argument("--vector_label", type=str, default="", metavar="IN.geojson",
                     help="read the label from GeoJSON polygons in pixel coordinates (objects.geojson_to_rings + rasterize_rings) instead of the synthetic one")
+
+
+def print_boundary(what, scores, tolerance):
+    h2 = scores.hausdorff2
+    hd = "undefined (one boundary is empty)" if h2 >= 2 ** 30 else f"{h2 ** 0.5:.2f} px"
+    print(f"{what}: boundary precision {scores.precision[0]:.4f}  recall {scores.recall[0]:.4f}  F1 {scores.f1[0]:.4f} at {tolerance} px "
+          f"({scores.n_pred} / {scores.n_label} boundary pixels); Hausdorff distance {hd}")
 
 
 def main(argv=None):
@@ -74,6 +85,9 @@ def main(argv=None):
     print(f"change pixels predicted {int(res.mask.sum())} / labelled {int((label >= 1).sum())}; mean change probability {float(res.prob.mean()):.4f}")
     print(f"confusion matrix [label, pred]: {res.cm.tolist()}")
     print(f"OA {s['oa']:.4f}  precision {s['precision'][1]:.4f}  recall {s['recall'][1]:.4f}  F1 {s['f1'][1]:.4f}  IoU {s['iou'][1]:.4f}")
+    if args.boundary is not None:
+        from stcd_amd import distance
+        print_boundary("prediction against the label", distance.boundary_scores(res.mask.contiguous(), label.contiguous(), (args.boundary,)), args.boundary)
     if args.vector:
         # the mask as vector data: small objects and small holes removed, the rest numbered, outlined and written as polygons
         from stcd_amd import objects
@@ -89,6 +103,10 @@ def main(argv=None):
             cm = objects.rasterize_rings(rings, clean.shape, overlay=(clean != 0).to(torch.uint8)).cm.cpu().numpy()      # 0 / 1: an overlay byte of 255 is ignored
             fid = scores_from_cm(cm)
             print(f"polygons against their mask: {int(cm[0, 1] + cm[1, 0])} pixels differ, IoU {fid['iou'][1]:.4f}, F1 {fid['f1'][1]:.4f}")
+            if args.boundary is not None:                       # the same cost in the tolerance's own unit: the distance between the outlines
+                from stcd_amd import distance
+                raster = objects.rasterize_rings(rings, clean.shape, mask_value=1).mask
+                print_boundary("polygons against their mask", distance.boundary_scores(raster, (clean != 0).to(torch.uint8), (args.boundary,)), args.boundary)
         doc = objects.rings_to_geojson(rings, path=args.vector, properties=objects.object_table(comp))
         print(f"{len(doc['features'])} polygons ({rings.count} rings, {int(rings.vertices.shape[0])} vertices) written to {args.vector}")
     return res

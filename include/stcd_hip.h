@@ -651,6 +651,61 @@ int stcd_rings_raster(const int32_t* vertices, const int64_t* offsets, int64_t n
                       int rule, int mask_value, const uint8_t* overlay, int64_t* cm, uint8_t* mask, void* scratch, int64_t scratch_bytes,
                       void* hip_stream);
 
+/* ---- distance transform: the exact squared Euclidean distance transform of a uint8 mask [height,width], 1 <= height, width <=
+ *      16384, on the device, and what is read off it: the int32 plane (scipy.ndimage.distance_transform_edt, squared and exact),
+ *      the disc buffers (scipy.ndimage.binary_dilation / binary_erosion with a disc of any radius; the square window of
+ *      stcd_mask_close stays what it is) and the boundary match of two masks (boundary precision / recall at a pixel tolerance and
+ *      the Hausdorff distance, today .cpu() plus scipy).  tests/edt_spec.py states every output; all quantities are integers.
+ *        - A pixel is set iff its byte is non-zero.  Pixel (i, j) is a lattice point; the squared distance of two pixels is
+ *          (i - i')^2 + (j - j')^2.
+ *        - d2[i][j] is the minimum squared distance from (i, j) to a SEED pixel inside the frame, 0 on a seed.  With no seed in the
+ *          frame every value is NO_SEED = 2^30; the largest real value is 2 * 16383^2 < 2^30.  Nothing outside the frame is a
+ *          seed.  Only the distance is returned, never the nearest pixel: ties between seeds do not matter.
+ *        - seeds: 0 (unset) the zero pixels, scipy's convention; 1 (set) the object pixels; 2 (boundary) the boundary pixels.
+ *        - boundary: an optional plane `ignore` marks VOID pixels, byte 255 (the label's "ignored" byte).  p is a boundary pixel
+ *          of mask M iff p is set in M, p is not void, and at least one 4-neighbour of p inside the frame is unset in M and not
+ *          void.  So the frame edge is no boundary, a void pixel is never a boundary pixel and never makes its neighbour one: a tile
+ *          cut from a scene and a label with an ignored margin grow no false outlines.
+ *        - buffer: q = floor(radius^2), computed once on the host.  Dilation by the disc sets p iff d2_set[p] <= q; erosion keeps p
+ *          iff d2_unset[p] > q, and does not eat in from the frame edge.  Closing is dilate then erode, opening erode then dilate:
+ *          close >= mask >= open as sets, radius 0 is the identity.
+ *        - boundary match of pred against label, the label's byte 255 void for both masks; up to 8 tolerances t as q_t =
+ *          floor(t^2).  Bp, Bl: the two boundary sets.  counts[s] = (n, max_d2, within[0..T-1]) for side 0 (Bp measured against
+ *          Bl) and side 1 (Bl against Bp): n the boundary pixels of that side, max_d2 the largest d2 among them to the other
+ *          side's boundary (0 if n == 0, NO_SEED if the other side is empty and n > 0), within[t] how many have d2 <= q_t.
+ *          precision_t = within0[t] / n0, recall_t = within1[t] / n1, hausdorff2 = max of the two max_d2, on the host.
+ *      Separable: a column pass leaves g, the distance along the column to its nearest seed, as uint16; the row pass takes
+ *      min_k (j - k)^2 + g[i][k]^2.  Four launches per transform on the caller's stream, whatever the data: k_edt_col_seeds (a thread
+ *      per chunk of 64 rows and 4 columns evaluates the seed predicate in its loader and tables the chunk's first and last seed
+ *      row), k_edt_col_carry (a thread per column carries them across the chunks), k_edt_col_dist (the loader again, g from the
+ *      chunk's 64 seed bits and the table), k_edt_row (a block per row; the cost is Monge, so the leftmost argmin is monotone: the
+ *      middle column first, then the middles of the halves within the argmins of their neighbours, log2 levels inside the kernel
+ *      with the row resident in LDS; O(W log W) per row, independent of the data).  The epilogue of the row pass is chosen by the
+ *      entry: the plane, the threshold, or the match counts.  No entry allocates, reads anything back or synchronises; there is no
+ *      atomic on the d2 path, and the match counts meet in integer atomics: every output is a pure function of the input. ---- */
+/* Bytes of the scratch buffer of the three entries below (16-byte aligned): 2 per pixel of the frame with its width rounded up to
+ * 4 (g), rounded up to 16, plus 4 per column of that width and chunk of 64 rows (the table); 0 for a height or width outside
+ * [1, 16384]. */
+int64_t stcd_edt_scratch_bytes(int height, int width);
+/* d2: int32 [height,width] on the device.  ignore: NULL, or with seeds == 2 a uint8 [height,width] plane whose byte 255 is void.
+ * Refused before any HIP call: null pointers, a shape outside [1, 16384], seeds outside 0..2, an ignore plane with seeds 0 or 1,
+ * d2 not 4-byte or scratch not 16-byte aligned, a scratch buffer that is too small.  16-byte stores when width % 4 == 0 and d2 is
+ * 16-byte aligned; mask rows are read as 32-bit words when width % 4 == 0 and the planes are 4-byte aligned, as bytes otherwise. */
+int stcd_edt(const uint8_t* mask, const uint8_t* ignore, int height, int width, int seeds, int32_t* d2, void* scratch, int64_t scratch_bytes,
+             void* hip_stream);
+/* One half of an opening or closing, no d2 plane written: out [height,width] = mask_value (1..255) where d2 <= q (keep_above == 0:
+ * with seeds == 1 the dilation) or where d2 > q (keep_above == 1: with seeds == 0 the erosion), else 0; q >= 0.  out must not
+ * overlap mask, and neither may overlap scratch.  Refusals as above. */
+int stcd_mask_buffer(const uint8_t* mask, int height, int width, int seeds, int q, int keep_above, int mask_value, uint8_t* out, void* scratch,
+                     int64_t scratch_bytes, void* hip_stream);
+/* counts: int64 [2][2 + n_q] on the device as defined above, cleared by the entry itself (one hipMemsetAsync).  q: n_q (0..8)
+ * integers >= 0 on the HOST, copied into the kernel arguments.  Two transforms, no d2 plane: each row pass measures the boundary
+ * pixels of the other mask in its epilogue, reduced per wave and block before one 64-bit integer atomic per block and counter.
+ * Refused before any HIP call: null pointers, a shape outside [1, 16384], n_q outside [0, 8], a negative q, counts not 8-byte or
+ * scratch not 16-byte aligned, a scratch buffer that is too small. */
+int stcd_boundary_match(const uint8_t* pred, const uint8_t* label, int height, int width, const int32_t* q, int n_q, int64_t* counts,
+                        void* scratch, int64_t scratch_bytes, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

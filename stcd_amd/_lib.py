@@ -176,6 +176,10 @@ _PROTOS = {
     "stcd_rings_simplify_write": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_rings_raster_scratch_bytes": (_i64, [_i, _i]),
     "stcd_rings_raster": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_edt_scratch_bytes": (_i64, [_i, _i]),
+    "stcd_edt": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "stcd_mask_buffer": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    "stcd_boundary_match": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv_fused": (_i, [C.POINTER(ConvGeom), C.POINTER(ConvFused), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),
