@@ -15,6 +15,7 @@ import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import numpy as np
 import torch
 
 from stcd_amd import synth
@@ -38,6 +39,9 @@ parser.add_argument("--max_hole", type=int, default=4, help="with --vector: hole
 parser.add_argument("--simplify", type=float, default=None, metavar="TOL",
                     help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5; "
                          "the polygons are then rasterized again (objects.rasterize_rings) and scored against the mask they came from")
+parser.add_argument("--boxes", type=str, default="", metavar="OUT.geojson",
+                    help="with --vector: also write every object's minimum-area rectangle (objects.convex_hulls + oriented_boxes on the traced "
+                         "outlines, not the simplified ones) with its angle, width, height, rectangularity and solidity")
 parser.add_argument("--boundary", type=float, default=None, metavar="T",
                     help="also print boundary precision, recall and F1 at T pixels and the Hausdorff distance of the prediction against the "
                          "label (distance.boundary_scores); with --vector ... --simplify the same scores of the simplified polygons' raster "
@@ -55,6 +59,8 @@ def print_boundary(what, scores, tolerance):
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    if args.boxes and not args.vector:
+        parser.error("--boxes needs --vector")
     assert torch.cuda.is_available(), "the engine needs a GPU (no CPU fallback)"
     dev = torch.device("cuda:0")
     a, b, label = synth.make_pairs_u8(1, args.size, args.size, args.seed)          # uint8 [1,H,W,3] x 2, uint8 [1,H,W] in {0,1}
@@ -95,6 +101,16 @@ def main(argv=None):
         comp = objects.label_components(clean)
         rings = objects.object_rings(comp)
         traced = int(rings.vertices.shape[0])
+        if args.boxes:
+            # footprint rectangles: the hull and the minimum-area rectangle of every traced ring, on the device
+            hulls = objects.convex_hulls(rings)
+            boxes = objects.oriented_boxes(hulls)
+            shape = objects.box_shape(boxes, rings, hulls)
+            doc = objects.boxes_to_geojson(boxes, rings, path=args.boxes, properties=shape)
+            outer = (rings.area2 > 0).cpu().numpy()
+            print(f"{len(doc['features'])} rectangles written to {args.boxes}: {int(hulls.vertices.shape[0])} hull vertices of {traced}; "
+                  f"median rectangularity {float(np.median(shape['rectangularity'][outer])) if outer.any() else float('nan'):.3f}, "
+                  f"median solidity {float(np.median(shape['solidity'][outer])) if outer.any() else float('nan'):.3f}")
         if args.simplify is not None:
             rings = objects.simplify_rings(rings, tolerance=args.simplify)
             print(f"simplified at {args.simplify} px (Douglas-Peucker on the device): {traced} vertices before, {int(rings.vertices.shape[0])} after")

@@ -611,6 +611,59 @@ int stcd_rings_simplify_write(const int32_t* vertices, const int64_t* offsets, i
                               int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, void* scratch, int64_t scratch_bytes,
                               void* hip_stream);
 
+/* ---- convex hulls and oriented boxes: rings in the layout above (vertices int32 [V,2] = (y, x) in [0, 16384], offsets int64 [R+1]),
+ *      on the device, with exact integer arithmetic.  tests/hull_spec.py states every output.
+ *      Hull of one ring P[0..n-1]:
+ *        1. a coordinate that occurs more than once counts at its lowest index only.
+ *        2. the hull ring is the subsequence of P, in input order, of the STRICT extreme points of the convex hull of the point set
+ *           (a point collinear with its hull neighbours is not one); it starts at the hull vertex of lowest input index.
+ *        3. area2 (the formula of stcd_rings_write) is recomputed from the kept vertices; ring count and order are unchanged.
+ *        4. 0, 1 or 2 distinct points, or points all on one line, give 0, 1 or 2 vertices and area2 0.
+ *      Found by QuickHull over index intervals: the anchors are the lexicographic minimum and maximum of (x, y), the two chains
+ *      between them are intervals in travel order, on a chain the vertex strictly outside the chord with the largest |cross|
+ *      (below 2^30; the first in travel order on ties) is kept and the chain splits there; "outside" is decided by the sign of the
+ *      ring's own area2 as recomputed from its vertices.  That equals rules 1 to 4 on every ring that does not cross itself (the
+ *      rings of stcd_rings_write, pinches included).  On a ring that crosses itself, or repeats a hull vertex, the entries end, stay
+ *      in bounds and return a subsequence that holds the two anchors; which other vertices it holds is unspecified.
+ *      Every ring iterates its levels inside one kernel (a wavefront per ring up to 64 vertices, a block per longer ring, its state
+ *      in LDS up to 2048 vertices and in the scratch buffer above): no launch and no host read per level.  Two phases with one host
+ *      read between them, as for the simplification; the scratch buffer carries the state.  Neither entry allocates, copies to the
+ *      host or synchronises.
+ *      Status word: 0, or bits 1: a coordinate outside [0, 16384], 2: a ring reached the round cap of n (a bug, never a property
+ *      of the input), 4: offsets that do not start at 0, do not ascend or do not end at n_vertices (nothing of such a ring is read),
+ *      8 (write entry, in the scratch header only, scratch byte 24): n_out is not what the count phase left.
+ *      Oriented box of one hull H[0..h-1] (stcd_rings_boxes):
+ *        5. h < 3: edge -1 and zeros.
+ *        6. for edge i from H[i] to H[(i + 1) % h]: e = (ey, ex), L = ey^2 + ex^2; for every j: d_j = (H[j] - H[i]) . e and
+ *           z_j = ex (y_j - y_i) - ey (x_j - x_i).  W = max d - min d; Z = max z if max z >= -min z, else min z (on a convex hull
+ *           all z_j have one sign).  The box on edge i has area W |Z| / L.  An edge with L == 0 (no hull has one) is passed over.
+ *        7. the chosen edge has the smallest area, compared exactly in 128 bits (W_i |Z_i| L_b < W_b |Z_b| L_i; the products stay
+ *           below 2^90), the lowest i on ties; no edge with L > 0: edge -1 and zeros.
+ *        8. the box: origin H[i], dir e, extent (min d, max d, Z).  With n = (ex, -ey) a point H[i] + a e + b n has d = a L and
+ *           z = b L: the corners are (a, b) = (dmin / L, 0), (dmax / L, 0), (dmax / L, Z / L), (dmin / L, Z / L).
+ *      One launch: a wavefront per hull of up to 64 vertices, the block for each longer one (in LDS up to 1024 vertices), a lane
+ *      per edge over all vertices, O(h^2) per hull by design: hulls of digital shapes are short. ---- */
+/* Bytes of the scratch buffer of the two hull entries (8-byte aligned): 48 + 25 per vertex + 12 per ring + 8 per 4096 vertices; 0
+ * for arguments they refuse (negative, or 2^31 and above). */
+int64_t stcd_rings_hull_scratch_bytes(int64_t n_rings, int64_t n_vertices);
+/* counts: int64 [2] on the device = (V', status): the hull vertices.  Refused before any launch: null pointers, negative counts or
+ * counts of 2^31 and above, misaligned pointers (8 bytes), a scratch buffer that is too small. */
+int stcd_rings_hull_count(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t* counts, void* scratch,
+                          int64_t scratch_bytes, void* hip_stream);
+/* After stcd_rings_hull_count on the same rings and scratch, with the V' it left as n_out: out_vertices int32 [n_out,2], out_offsets
+ * int64 [R+1], out_area2 int64 [R].  Refused before any launch: what the count entry refuses, n_out < 0 and n_out > n_vertices.  An
+ * n_out that passes those checks but is not the count phase's own (or a count phase that left a status, or other ring sizes) is
+ * found on the device: nothing is written and bit 8 is set. */
+int stcd_rings_hull_write(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t n_out,
+                          int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* out_edge int32 [R], out_origin int32 [R,2] = (y, x), out_dir int32 [R,2] = (ey, ex), out_extent int64 [R,3] = (dmin, dmax, Z), all
+ * on the device; status: one int32 on the device, cleared by the entry, then 0 or bits 1 and 4 as above (bit 1: the coordinate is
+ * clamped; bit 4: the ring gets edge -1); where it is set the boxes are not valid.  The rules ask for no convexity: any rings in the layout above are taken.  Refused before any launch:
+ * null pointers, negative counts or counts of 2^31 and above, misaligned pointers.  Needs no scratch buffer, allocates nothing and
+ * reads nothing back. */
+int stcd_rings_boxes(const int32_t* hull_vertices, const int64_t* hull_offsets, int64_t n_rings, int64_t n_vertices, int32_t* out_edge,
+                     int32_t* out_origin, int32_t* out_dir, int64_t* out_extent, int32_t* status, void* hip_stream);
+
 /* ---- ring rasterization: rings in the layout above (vertices int32 [V,2] = (y, x) lattice corners in [0, 16384], offsets int64
  *      [R+1], ring r closed implicitly: edges from vertex k to vertex k + 1 mod n) back to a uint8 mask of height x width pixels at
  *      the origin, 1 <= height, width <= 16384, on the device, with exact integer arithmetic.  tests/raster_spec.py states every

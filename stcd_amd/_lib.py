@@ -174,6 +174,10 @@ _PROTOS = {
     "stcd_rings_simplify_scratch_bytes": (_i64, [_i64, _i64]),
     "stcd_rings_simplify_count": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "stcd_rings_simplify_write": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_rings_hull_scratch_bytes": (_i64, [_i64, _i64]),
+    "stcd_rings_hull_count": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "stcd_rings_hull_write": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_rings_boxes": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "stcd_rings_raster_scratch_bytes": (_i64, [_i, _i]),
     "stcd_rings_raster": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_edt_scratch_bytes": (_i64, [_i, _i]),

@@ -10,7 +10,9 @@ stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_
 (stcd_amd/csrc/kernels_rings.hip behind ``stcd_rings_count`` and ``stcd_rings_write``; tests/rings_spec.py is the specification),
 ``simplify_rings`` thins them with Douglas-Peucker, still on the device (stcd_amd/csrc/kernels_simplify.hip behind
 ``stcd_rings_simplify_count`` and ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification), and
-``rings_to_geojson`` writes either as polygons on the host.  ``rasterize_rings`` goes the other way, from rings to a mask on the
+``rings_to_geojson`` writes either as polygons on the host.  ``convex_hulls`` and ``oriented_boxes`` give every ring its convex hull and
+its minimum-area rectangle, on the device (stcd_amd/csrc/kernels_hull.hip behind ``stcd_rings_hull_count``, ``stcd_rings_hull_write`` and
+``stcd_rings_boxes``; tests/hull_spec.py is the specification); ``box_shape`` and ``boxes_to_geojson`` read them on the host.  ``rasterize_rings`` goes the other way, from rings to a mask on the
 device (stcd_amd/csrc/kernels_raster.hip behind ``stcd_rings_raster``; tests/raster_spec.py is the specification), with the
 confusion counts against an overlay in the same pass, and ``geojson_to_rings`` reads polygons back on the host.
 """
@@ -31,6 +33,10 @@ from .selftrain import _check_mask
 TILE = 64               # the tile pass labels TILE x TILE pixels per block (OBJ_TILE of kernels_objects.hip): where the seams lie
 SIMPLIFY_WAVE_MAX = 64     # the longest ring one wavefront simplifies (SM_WAVE_MAX of kernels_simplify.hip); a block takes longer ones
 SIMPLIFY_LDS_MAX = 2048     # the longest ring whose state the block keeps in LDS (SM_LDS_MAX); above it the state is in global memory
+HULL_WAVE_MAX = 64     # the longest ring one wavefront hulls (HL_WAVE_MAX of kernels_hull.hip); a block takes longer ones
+HULL_LDS_MAX = 2048     # the longest ring whose hull state the block keeps in LDS (HL_LDS_MAX); above it the state is in global memory
+BOX_WAVE_MAX = 64     # the longest hull one wavefront boxes (BX_WAVE_MAX of kernels_hull.hip); the block takes longer ones
+BOX_LDS_MAX = 1024     # the longest hull the block holds in LDS (BX_LDS_MAX); above it the vertices are read from global memory
 RASTER_SPAN_MAX = 32     # the longest clipped row span of an edge one lane rasterizes alone (RS_SPAN_MAX of kernels_raster.hip); a wavefront strides over longer ones
 RASTER_ROW_CHUNK = 1024     # columns of a row a wavefront scans per step with a carried sum (RS_ROW_CHUNK)
 
@@ -53,6 +59,14 @@ class Rings(NamedTuple):
     offsets: torch.Tensor               # int64 [count+1] on the device: ring r is vertices[offsets[r]:offsets[r + 1]]
     object: torch.Tensor                # int32 [count] on the device: the label of the ring's object
     area2: torch.Tensor                 # int64 [count] on the device: twice the signed area, > 0 outer ring, < 0 hole
+    count: int
+
+
+class OrientedBoxes(NamedTuple):
+    edge: torch.Tensor                  # int32 [count] on the device: the hull edge the box stands on, -1 for a hull of fewer than 3 vertices
+    origin: torch.Tensor                # int32 [count,2] on the device: the edge's first vertex (y, x)
+    dir: torch.Tensor                   # int32 [count,2] on the device: the edge vector e = (ey, ex)
+    extent: torch.Tensor                # int64 [count,3] on the device: (dmin, dmax, Z), in units of |e| (tests/hull_spec.py, rule 8)
     count: int
 
 
@@ -309,6 +323,79 @@ def simplify_rings(rings: Rings, tolerance: float = 1.5) -> Rings:
     return Rings(out_vertices, out_offsets, obj.clone(), out_area2, R)
 
 
+def convex_hulls(rings: Rings) -> Rings:
+    """The convex hull of every ring of ``rings`` (``object_rings``' result, or any ``Rings`` with int32 ``(y, x)`` vertices in
+    ``[0, 16384]``), on the device: a new ``Rings`` with the same ``count``, ``object`` and ring order, every ring the subsequence
+    of its input, in input order, of the strict extreme points of the hull of its point set (a vertex collinear with its hull
+    neighbours is dropped, a repeated coordinate counts at its lowest index), ``area2`` recomputed from the vertices that remain
+    (include/stcd_hip.h, ``stcd_rings_hull_count`` / ``stcd_rings_hull_write``; tests/hull_spec.py is the specification and the
+    device equals it to the bit).  For a ring that does not cross itself, every ring of ``object_rings`` among them, the result is
+    a strictly convex polygon travelled in the input's direction: a hole's hull keeps ``area2 < 0``, and ``|area2|`` does not
+    shrink.  A ring of 0, 1 or 2 distinct points, or all on one line, gives 0, 1 or 2 vertices and ``area2`` 0.  ``rings_to_geojson``,
+    ``rasterize_rings`` and ``oriented_boxes`` take the result unchanged.
+
+    A ring that crosses itself (a foreign ring of ``geojson_to_rings``, possibly a ring of ``simplify_rings``) or repeats a hull
+    vertex still gives a subsequence that holds its leftmost and rightmost vertex, but which others it holds is unspecified and it
+    need not be a convex polygon in travel order: take the hull of the traced rings first, which costs nothing extra.
+
+    One host read, of the hull vertex count and a status word (16 bytes), between the two phases."""
+    vertices, offsets, obj, R, V = _check_rings(rings)
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        if R == 0:
+            return Rings(torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                         torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), 0)
+        nbytes = int(_lib.lib().stcd_rings_hull_scratch_bytes(R, V))
+        key = (str(dev), "hull", nbytes)
+        scratch = _SCRATCH.get(key)
+        if scratch is None:
+            scratch = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_rings_hull_count(_ptr(vertices), _ptr(offsets), R, V, _ptr(counts), _ptr(scratch), scratch.numel(), _stream(dev)))
+        n_out, status = (int(v) for v in counts.cpu().numpy())
+        if status:
+            raise StcdError(f"convex_hulls: the count phase reports status {status} (bit 1: a coordinate outside [0, 16384], bit 4: offsets that "
+                            "do not ascend from 0 to the vertex count; bit 2: a ring reached its round cap, which is a bug in the kernels, "
+                            "not a property of the rings)")
+        out_vertices = torch.empty((n_out, 2), dtype=torch.int32, device=dev)
+        out_offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        out_area2 = torch.empty(R, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_rings_hull_write(_ptr(vertices), _ptr(offsets), R, V, n_out, _ptr(out_vertices), _ptr(out_offsets),
+                                                    _ptr(out_area2), _ptr(scratch), scratch.numel(), _stream(dev)))
+    return Rings(out_vertices, out_offsets, obj.clone(), out_area2, R)
+
+
+def oriented_boxes(hulls: Rings, check: bool = True) -> OrientedBoxes:
+    """The minimum-area rectangle of every ring of ``hulls`` (``convex_hulls``' result), on the device, one launch: the rectangle
+    stands on a hull edge, and for every edge the exact integer extents of the hull along and across it are compared as fractions
+    in 128 bits, the lowest edge index winning ties (include/stcd_hip.h, ``stcd_rings_boxes``; tests/hull_spec.py is the
+    specification and the device equals it to the bit).  Per ring: ``edge``, ``origin`` (that edge's first vertex), ``dir`` (the edge
+    vector ``e``) and ``extent = (dmin, dmax, Z)``; ``box_shape`` turns them into corners, width, height and angle on the host.  A
+    hull of fewer than 3 vertices gets edge -1 and zeros.  The rules ask for no convexity, so any ``Rings`` is taken, but only a
+    convex ring's rectangle is its minimum-area one.
+
+    ``check=True`` reads the 4-byte status word afterwards and raises ``StcdError`` naming the bit (1: a coordinate outside
+    ``[0, 16384]``, 4: offsets that do not ascend from 0 to the vertex count); ``check=False`` synchronises nothing."""
+    vertices, offsets, obj, R, V = _check_rings(hulls)
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        edge = torch.empty(R, dtype=torch.int32, device=dev)
+        origin = torch.empty((R, 2), dtype=torch.int32, device=dev)
+        direction = torch.empty((R, 2), dtype=torch.int32, device=dev)
+        extent = torch.empty((R, 3), dtype=torch.int64, device=dev)
+        if R == 0:
+            return OrientedBoxes(edge, origin, direction, extent, 0)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().stcd_rings_boxes(_ptr(vertices), _ptr(offsets), R, V, _ptr(edge), _ptr(origin), _ptr(direction), _ptr(extent),
+                                               _ptr(status), _stream(dev)))
+        if check:
+            st = int(status.cpu().numpy()[0])
+            if st:
+                raise StcdError(f"oriented_boxes: status {st} (bit 1: a coordinate outside [0, 16384], bit 4: offsets that do not ascend "
+                                "from 0 to the vertex count); the boxes are not valid")
+    return OrientedBoxes(edge, origin, direction, extent, R)
+
+
 def _host_array(x, dtype):
     if torch.is_tensor(x):
         x = x.detach().cpu().numpy()
@@ -377,6 +464,98 @@ def rings_to_geojson(rings, path=None, transform=None, properties: Optional[Obje
                 props["overlap"] = [int(v) for v in table[2][label - 1]]
         features.append({"type": "Feature", "properties": props, "geometry": {"type": "Polygon", "coordinates": [outer] + holes}})
     collection = {"type": "FeatureCollection", "features": features}
+    if path is not None:
+        with open(path, "w") as fh:
+            json.dump(collection, fh)
+    return collection
+
+
+def box_shape(boxes, rings=None, hulls=None) -> dict:
+    """What ``oriented_boxes``' integer columns say, as float64 numpy arrays, on the host (``boxes``: an ``OrientedBoxes``, or the same
+    five fields as numpy arrays or CPU tensors).  With ``e = (ey, ex)`` the box's edge vector, ``L = |e|^2`` and ``(dmin, dmax, Z)``
+    its extent: ``corners`` ``[R,4,2]`` as ``(y, x)``, ``origin + (d / L) e + (z / L) (ex, -ey)`` for ``(d, z)`` = ``(dmin, 0)``,
+    ``(dmax, 0)``, ``(dmax, Z)``, ``(dmin, Z)``; ``width = (dmax - dmin) / sqrt(L)`` along the edge and ``height = |Z| / sqrt(L)``
+    across it; ``angle = atan2(ey, ex)`` folded into ``[0, pi)`` (the fold is made on the integers, so an edge along x gives 0.0);
+    ``area = (dmax - dmin) |Z| / L``.  With ``rings`` (the rings the hulls were made from, same count): ``rectangularity =
+    |area2| / (2 area)``; with ``rings`` and ``hulls``: ``solidity = |area2| / |hull area2|``.  A ring with edge -1 gets NaN in
+    every column."""
+    R = int(boxes.count)
+    edge = _host_array(boxes.edge, np.int64).reshape(-1)
+    origin = _host_array(boxes.origin, np.int64).reshape(-1, 2)
+    e = _host_array(boxes.dir, np.int64).reshape(-1, 2)
+    extent = _host_array(boxes.extent, np.int64).reshape(-1, 3)
+    if edge.shape[0] != R or origin.shape[0] != R or e.shape[0] != R or extent.shape[0] != R:
+        raise StcdError("box_shape: the fields of `boxes` do not fit together")
+    none = edge < 0
+    L = np.where(none, 1, e[:, 0] ** 2 + e[:, 1] ** 2).astype(np.float64)
+    dmin, dmax, Z = (extent[:, k].astype(np.float64) for k in range(3))
+    o, ef = origin.astype(np.float64), e.astype(np.float64)
+    nf = np.stack([ef[:, 1], -ef[:, 0]], axis=1)
+    corners = np.stack([o + (d / L)[:, None] * ef + (z / L)[:, None] * nf
+                        for d, z in ((dmin, np.zeros(R)), (dmax, np.zeros(R)), (dmax, Z), (dmin, Z))], axis=1)
+    flip = (e[:, 0] < 0) | ((e[:, 0] == 0) & (e[:, 1] < 0))
+    up = np.where(flip[:, None], -e, e).astype(np.float64)
+    out = {"corners": corners, "width": (dmax - dmin) / np.sqrt(L), "height": np.abs(Z) / np.sqrt(L), "angle": np.arctan2(up[:, 0], up[:, 1]),
+           "area": ((extent[:, 1] - extent[:, 0]) * np.abs(extent[:, 2])).astype(np.float64) / L}
+    if hulls is not None and rings is None:
+        raise StcdError("box_shape: solidity needs `rings` as well as `hulls`")
+    if rings is not None:
+        area2 = np.abs(_host_array(rings.area2, np.int64).reshape(-1)).astype(np.float64)
+        if area2.shape[0] != R:
+            raise StcdError("box_shape: `rings` and `boxes` differ in count")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["rectangularity"] = area2 / (2.0 * out["area"])
+            if hulls is not None:
+                hull2 = np.abs(_host_array(hulls.area2, np.int64).reshape(-1)).astype(np.float64)
+                if hull2.shape[0] != R:
+                    raise StcdError("box_shape: `hulls` and `boxes` differ in count")
+                out["solidity"] = area2 / hull2
+    for v in out.values():
+        v[none] = np.nan
+    return out
+
+
+def boxes_to_geojson(boxes, rings, path=None, transform=None, properties: Optional[dict] = None) -> dict:
+    """A GeoJSON ``FeatureCollection`` (a dict; written to ``path`` if given) with one rectangle ``Polygon`` per object: the box of
+    its outer ring (``rings.area2 > 0``; holes give no box).  ``boxes`` are ``oriented_boxes``' of the hulls of ``rings``, ring for
+    ring.  Host side.  ``transform``, the ``[x, y]`` order and the ring closure are ``rings_to_geojson``'s; the exterior is
+    counter-clockwise with and without a mirroring transform, decided by the signed area of the four transformed corners (a
+    clockwise rectangle is listed in reverse, its first corner staying first).  Each feature's properties hold ``label`` and
+    every per-ring column of ``properties``, a ``box_shape`` result for the same boxes (by default ``box_shape(boxes, rings)``:
+    ``angle``, ``width``, ``height``, ``area`` and ``rectangularity``; pass ``box_shape(boxes, rings, hulls)`` for ``solidity`` too).
+    An object with more than one outer ring, or an outer ring without a box (edge -1), raises ``StcdError``."""
+    R = int(boxes.count)
+    obj = _host_array(rings.object, np.int64).reshape(-1)
+    area2 = _host_array(rings.area2, np.int64).reshape(-1)
+    edge = _host_array(boxes.edge, np.int64).reshape(-1)
+    if int(rings.count) != R or obj.shape[0] != R or area2.shape[0] != R or edge.shape[0] != R:
+        raise StcdError("boxes_to_geojson: `boxes` and `rings` differ in count")
+    shape = box_shape(boxes, rings) if properties is None else properties
+    corners = np.asarray(shape["corners"], np.float64).reshape(-1, 4, 2)
+    if corners.shape[0] != R:
+        raise StcdError("boxes_to_geojson: `properties` is not the box_shape of these boxes")
+    if transform is not None:
+        a, b, c, d, e, f = (float(v) for v in transform)
+    features = {}
+    for r in range(R):
+        if area2[r] <= 0:
+            continue
+        label = int(obj[r])
+        if label in features:
+            raise StcdError(f"boxes_to_geojson: object {label} has more than one outer ring: the labels and the rings' connectivity disagree")
+        if edge[r] < 0:
+            raise StcdError(f"boxes_to_geojson: the outer ring of object {label} has no box")
+        coords = [[float(x), float(y)] if transform is None else [a * float(x) + b * float(y) + c, d * float(x) + e * float(y) + f]
+                  for y, x in corners[r].tolist()]
+        if sum(p[0] * q[1] - q[0] * p[1] for p, q in zip(coords, coords[1:] + coords[:1])) < 0:
+            coords = coords[:1] + coords[:0:-1]
+        coords.append(list(coords[0]))
+        props = {"label": label}
+        for name, column in shape.items():
+            if name != "corners":
+                props[name] = float(column[r])
+        features[label] = {"type": "Feature", "properties": props, "geometry": {"type": "Polygon", "coordinates": [coords]}}
+    collection = {"type": "FeatureCollection", "features": [features[label] for label in sorted(features)]}
     if path is not None:
         with open(path, "w") as fh:
             json.dump(collection, fh)
