@@ -39,6 +39,10 @@ parser.add_argument("--max_hole", type=int, default=4, help="with --vector: hole
 parser.add_argument("--simplify", type=float, default=None, metavar="TOL",
                     help="with --vector: simplify the outlines with this tolerance in pixels (objects.simplify_rings), e.g. 1.5; "
                          "the polygons are then rasterized again (objects.rasterize_rings) and scored against the mask they came from")
+parser.add_argument("--topology", action="store_true",
+                    help="with --vector ... --simplify: repair the simplified outlines' topology (objects.simplify_rings_safe): no two edges "
+                         "cross and no object ends up inside another's polygon; prints the rounds, the restored vertices and what plain "
+                         "Douglas-Peucker leaves")
 parser.add_argument("--boxes", type=str, default="", metavar="OUT.geojson",
                     help="with --vector: also write every object's minimum-area rectangle (objects.convex_hulls + oriented_boxes on the traced "
                          "outlines, not the simplified ones) with its angle, width, height, rectangularity and solidity")
@@ -61,6 +65,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.boxes and not args.vector:
         parser.error("--boxes needs --vector")
+    if args.topology and not (args.vector and args.simplify is not None):
+        parser.error("--topology needs --vector and --simplify")
     assert torch.cuda.is_available(), "the engine needs a GPU (no CPU fallback)"
     dev = torch.device("cuda:0")
     a, b, label = synth.make_pairs_u8(1, args.size, args.size, args.seed)          # uint8 [1,H,W,3] x 2, uint8 [1,H,W] in {0,1}
@@ -112,8 +118,16 @@ def main(argv=None):
                   f"median rectangularity {float(np.median(shape['rectangularity'][outer])) if outer.any() else float('nan'):.3f}, "
                   f"median solidity {float(np.median(shape['solidity'][outer])) if outer.any() else float('nan'):.3f}")
         if args.simplify is not None:
-            rings = objects.simplify_rings(rings, tolerance=args.simplify)
-            print(f"simplified at {args.simplify} px (Douglas-Peucker on the device): {traced} vertices before, {int(rings.vertices.shape[0])} after")
+            if args.topology:
+                plain = objects.simplify_rings(rings, tolerance=args.simplify)
+                safe = objects.simplify_rings_safe(rings, tolerance=args.simplify)
+                rings = safe.rings
+                print(f"simplified at {args.simplify} px with the topology repaired: {traced} vertices before, {int(rings.vertices.shape[0])} after, "
+                      f"{safe.restored} of them restored in {safe.rounds} rounds, {safe.conflicts} conflicting edges left; plain Douglas-Peucker "
+                      f"keeps {int(plain.vertices.shape[0])} vertices and leaves {objects.ring_conflicts(plain).count} conflicting edges")
+            else:
+                rings = objects.simplify_rings(rings, tolerance=args.simplify)
+                print(f"simplified at {args.simplify} px (Douglas-Peucker on the device): {traced} vertices before, {int(rings.vertices.shape[0])} after")
             # what the tolerance cost in pixels: the polygons rasterized again, with the mask they came from as overlay
             from stcd_amd.metrics import scores_from_cm
             cm = objects.rasterize_rings(rings, clean.shape, overlay=(clean != 0).to(torch.uint8)).cm.cpu().numpy()      # 0 / 1: an overlay byte of 255 is ignored

@@ -588,7 +588,7 @@ int stcd_rings_write(const int32_t* labels, int height, int width, int connectiv
  *      The result keeps the ring count and order, every ring a subsequence of its input in travel order with the first vertex still
  *      first; q == 0 drops only vertices that lie on the segment between their kept neighbours (none on a traced ring).  Topology
  *      is NOT protected: a simplified hole may touch or cross its exterior and two objects' polygons may overlap by up to the
- *      tolerance.
+ *      tolerance; stcd_rings_safe_begin / _round / _write below repair that and stcd_rings_conflicts reports it.
  *      Every ring iterates the levels of step 3 inside one kernel (a wavefront per ring up to 64 vertices, a block per longer
  *      ring, its state in LDS up to 2048 vertices and in the scratch buffer above): no launch and no host read per level, no
  *      thread walks a chain.  Two phases with one host read between them, as for the rings; the scratch buffer carries the state.
@@ -610,6 +610,80 @@ int stcd_rings_simplify_count(const int32_t* vertices, const int64_t* offsets, i
 int stcd_rings_simplify_write(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t q, int64_t n_out,
                               int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, void* scratch, int64_t scratch_bytes,
                               void* hip_stream);
+
+/* ---- topology of ring sets: which edges conflict, and Douglas-Peucker with its topology repaired; rings in the layout above
+ *      (vertices int32 [V,2] = (y, x) in [0, 16384], offsets int64 [R+1]), on the device, with exact integer arithmetic.
+ *      tests/topology_spec.py states every output.  Edge k of ring r with n vertices runs from P[k] to P[(k+1) % n] and has the
+ *      global index offsets[r] + k.  orient(a, b, c) = (b.y - a.y)(c.x - a.x) - (b.x - a.x)(c.y - a.y), below 2^30 in magnitude.
+ *      CONFLICT of two distinct edges (a, b), (c, d), of one ring or of two:
+ *        1. a zero-length edge conflicts with nothing.
+ *        2. all four orientations 0 (collinear): iff their overlap along the axis in which a and b differ has positive length.
+ *        3. otherwise no endpoint value may be common to both (a != c, a != d, b != c, b != d) and the closed segments must share a
+ *           point: both orientation sign products negative, or one orientation 0 and that point in the other edge's bounding box.
+ *      So proper crossings, a vertex inside another edge, collinear overlaps and spikes conflict; contact at a vertex of both does
+ *      not (consecutive edges, pinch corners), and the rings of stcd_rings_write have no conflict.  Known limit: a crossing exactly
+ *      through a vertex that both rings share is not seen.
+ *      POCKET HIT: a current edge from kept vertex i to the next kept vertex j (j = n for the edge that closes the ring; vertex 0 is
+ *      always kept) with j - i >= 2 has the pocket P[i], ..., P[j % n], a closed polygon; the edge is hit iff the first vertex p of
+ *      any OTHER ring lies on one of the pocket's sides (orientation 0 and within the side's bounding box) or inside: the sides
+ *      (u, v), taken with u.y < v.y, with u.y <= p.y < v.y (the half-open row rule of stcd_rings_raster) and
+ *      (v.x - u.x)(p.y - u.y) > (p.x - u.x)(v.y - u.y) are odd in number.
+ *      TOPOLOGY-SAFE SIMPLIFICATION at q:
+ *        1. round 0 is stcd_rings_simplify_count (rules 1 to 5 there): a keep mask over the input vertices.
+ *        2. a round flags every current edge that conflicts with another current edge or whose pocket is hit.
+ *        3. every flagged edge with dropped vertices restores the vertex of largest key (rule 1 of the simplification) against
+ *           (P[i], P[j % n]) among i+1 .. j-1, lowest index on ties: the one Douglas-Peucker would split at next.  All at once.
+ *        4. every ring whose mask changed: kept area2 0 or of another sign than the input's -> all of its vertices are kept.
+ *        5. repeat from 2 until a round restores nothing.  Masks only grow, so this ends; at the end a flagged edge is an input
+ *           edge, so conflict-free input gives a conflict-free result in which every ring winds round every other ring's first
+ *           vertex as often, mod 2, as in the input.  Input that conflicts already still ends; what is left is counted.
+ *      Candidate pairs come from a uniform grid of cell x cell pixels, cell a power of two from 8 to 256 (0: 16): every edge is
+ *      entered into the cells its segment passes through (a walk over the cell rows it spans with exact floor / ceiling columns per
+ *      row, not the cells of its bounding box) by count, prefix sum and fill; one block per non-empty cell stages the cell's edges
+ *      in LDS in tiles of 256 and every lane tests its own edge against the tile and sets its own flag with a plain byte store (no
+ *      atomics, no pair list; a pair that shares several cells is tested in each).  No output depends on cell.  The first vertices
+ *      of all rings lie in the same grid; a wavefront per current edge with dropped vertices takes the box of its chain, the points
+ *      in the grid rows of that box and runs on-or-inside with its lanes striding over the chain, and another one the arg-max of
+ *      the restore.  No thread walks a ring.  No entry allocates, synchronises or copies to the host; all run on hip_stream.
+ *      counts: int64 [8] on the device = (status, current edges, grid entries, vertices restored by this call, conflicting edges,
+ *      pocket hits, 0, 0); the last two of the named ones are -1 where the status is set.  Status word: 0, or bits 1: a coordinate
+ *      outside [0, 16384], 2: a ring reached its round cap in round 0 (a bug, never a property of the input), 4: offsets that do not
+ *      start at 0, do not ascend or do not end at n_vertices, 8: n_edges / n_out is not the device's own count, 16: the grid has more
+ *      entries than max_entries (counts[2] says how many; nothing was flagged or restored).  With a status set the kernels that
+ *      follow do nothing.  Bits 8 and 16 are those of one call, the others stay. ---- */
+/* Bytes of the scratch buffer of the entries below (8-byte aligned): 64 + 26 per vertex + 24 per ring + 8 per cell of the grid
+ * ((16384 / cell + 1)^2 of them) + the scan's 8 per 4096 of the larger of the two + stcd_rings_simplify_scratch_bytes; 0 for arguments
+ * they refuse. */
+int64_t stcd_rings_topo_scratch_bytes(int64_t n_rings, int64_t n_vertices, int cell);
+/* flags uint8 [n_vertices]: 1 where the edge that starts at that vertex conflicts with any other edge of the ring set, else 0;
+ * counts as above (current edges = n_vertices).  entries: int32 [max_entries], the grid's (cell, edge) entries; 4 * n_vertices + 4096
+ * is enough for traced rings.  Refused before any launch: null pointers, negative counts or counts of 2^31 and above, a cell that is
+ * not 0 or a power of two from 8 to 256, max_entries outside [0, 2^31), misaligned pointers (8 bytes, entries 4), a scratch buffer
+ * that is too small.  n_vertices == 0 launches the validation and the counts alone.  Otherwise 11 kernel launches and 3 memsets whatever
+ * the data: validation, the ring of every vertex, the edges, the grid (count, 3 of the scan, fill), the pairs, the tally, the counts. */
+int stcd_rings_conflicts(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int cell, uint8_t* flags,
+                         int64_t* counts, int32_t* entries, int64_t max_entries, void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* Round 0 of the safe simplification: stcd_rings_simplify_count on a part of the scratch buffer, then the ring of every vertex, the
+ * input areas and the grid of first vertices.  counts[1] is the number of kept vertices, which is the number of current edges.
+ * Refused before any launch: as above, and q outside [0, 2^31).  The launches of stcd_rings_simplify_count, then 10 kernel launches, 4
+ * memsets and one device-to-device copy of 8 bytes per ring. */
+int stcd_rings_safe_begin(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int64_t q, int cell,
+                          int64_t* counts, void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* One round after stcd_rings_safe_begin on the same rings, cell and scratch: the detection pass (rule 2) over the n_edges current
+ * edges and, with restore != 0, rules 3 and 4.  n_edges is counts[1] of the begin entry plus every counts[3] since (bit 8 if not).
+ * counts[3] == 0 ends the loop; counts[4] is then the number of conflicting edges of the result.  With restore == 0 nothing changes:
+ * the pass a round cap ends with.  After bit 16 the same call is repeated with max_entries >= counts[2].  Refused before any launch:
+ * as stcd_rings_conflicts, and n_edges outside [0, n_vertices].  15 kernel launches and 3 memsets per round whatever the data, 3 launches
+ * more with restore != 0. */
+int stcd_rings_safe_round(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int cell, int64_t n_edges,
+                          int restore, int64_t* counts, int32_t* entries, int64_t max_entries, void* scratch, int64_t scratch_bytes,
+                          void* hip_stream);
+/* After a round that restored nothing (or ran with restore == 0), with its n_edges as n_out: out_vertices int32 [n_out,2],
+ * out_offsets int64 [R+1], out_area2 int64 [R] of the kept vertices.  Refused before any launch: as the begin entry, n_out outside
+ * [0, n_vertices], null or misaligned outputs.  An n_out that is not the device's own is found there: nothing is written, bit 8. */
+int stcd_rings_safe_write(const int32_t* vertices, const int64_t* offsets, int64_t n_rings, int64_t n_vertices, int cell, int64_t n_out,
+                          int32_t* out_vertices, int64_t* out_offsets, int64_t* out_area2, int64_t* counts, void* scratch,
+                          int64_t scratch_bytes, void* hip_stream);
 
 /* ---- convex hulls and oriented boxes: rings in the layout above (vertices int32 [V,2] = (y, x) in [0, 16384], offsets int64 [R+1]),
  *      on the device, with exact integer arithmetic.  tests/hull_spec.py states every output.

@@ -174,6 +174,11 @@ _PROTOS = {
     "stcd_rings_simplify_scratch_bytes": (_i64, [_i64, _i64]),
     "stcd_rings_simplify_count": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
     "stcd_rings_simplify_write": (_i, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_rings_topo_scratch_bytes": (_i64, [_i64, _i64, _i]),
+    "stcd_rings_conflicts": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "stcd_rings_safe_begin": (_i, [_vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _i64, _vp]),
+    "stcd_rings_safe_round": (_i, [_vp, _vp, _i64, _i64, _i, _i64, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "stcd_rings_safe_write": (_i, [_vp, _vp, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_rings_hull_scratch_bytes": (_i64, [_i64, _i64]),
     "stcd_rings_hull_count": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     "stcd_rings_hull_write": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),

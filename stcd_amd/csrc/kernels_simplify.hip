@@ -390,6 +390,14 @@ inline bool sm_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a -
 inline bool sm_sizes_ok(int64_t R, int64_t V) { return R >= 0 && V >= 0 && R < ((int64_t)1 << 31) && V < ((int64_t)1 << 31); }
 
 }  // namespace
+
+// for kernels_topo.hip, whose repair loop goes on from the count phase's state: where the keep bytes, the areas and the status word lie
+void sm_state_of(void* scratch, int64_t n_rings, int64_t n_vertices, uint8_t** keep, long long** area, int** status) {
+    const SmScratch L = sm_layout(n_rings, n_vertices);
+    *keep = (uint8_t*)scratch + L.keep;
+    *area = (long long*)((char*)scratch + L.area);
+    *status = &((SmHeader*)scratch)->status;
+}
 }  // namespace stcd
 
 using namespace stcd;

@@ -9,7 +9,10 @@ stcd_amd/csrc/kernels_objects.hip behind ``stcd_objects_label``, ``stcd_objects_
 ``object_rings`` goes on from numbered objects to vector data: the boundary rings of every object with their holes, on the device
 (stcd_amd/csrc/kernels_rings.hip behind ``stcd_rings_count`` and ``stcd_rings_write``; tests/rings_spec.py is the specification),
 ``simplify_rings`` thins them with Douglas-Peucker, still on the device (stcd_amd/csrc/kernels_simplify.hip behind
-``stcd_rings_simplify_count`` and ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification), and
+``stcd_rings_simplify_count`` and ``stcd_rings_simplify_write``; tests/simplify_spec.py is the specification),
+``simplify_rings_safe`` does the same and then restores vertices until no two edges conflict and no object has jumped into another's
+polygon, and ``ring_conflicts`` says which edges of any ring set conflict (stcd_amd/csrc/kernels_topo.hip behind
+``stcd_rings_conflicts`` and ``stcd_rings_safe_begin`` / ``_round`` / ``_write``; tests/topology_spec.py is the specification), and
 ``rings_to_geojson`` writes either as polygons on the host.  ``convex_hulls`` and ``oriented_boxes`` give every ring its convex hull and
 its minimum-area rectangle, on the device (stcd_amd/csrc/kernels_hull.hip behind ``stcd_rings_hull_count``, ``stcd_rings_hull_write`` and
 ``stcd_rings_boxes``; tests/hull_spec.py is the specification); ``box_shape`` and ``boxes_to_geojson`` read them on the host.  ``rasterize_rings`` goes the other way, from rings to a mask on the
@@ -39,6 +42,9 @@ BOX_WAVE_MAX = 64     # the longest hull one wavefront boxes (BX_WAVE_MAX of ker
 BOX_LDS_MAX = 1024     # the longest hull the block holds in LDS (BX_LDS_MAX); above it the vertices are read from global memory
 RASTER_SPAN_MAX = 32     # the longest clipped row span of an edge one lane rasterizes alone (RS_SPAN_MAX of kernels_raster.hip); a wavefront strides over longer ones
 RASTER_ROW_CHUNK = 1024     # columns of a row a wavefront scans per step with a carried sum (RS_ROW_CHUNK)
+TOPO_TILE = 256     # the edges of one grid cell staged in LDS at a time (TP_TILE of kernels_topo.hip); a fuller cell loops over tile pairs
+TOPO_CELL = 16     # the default side, in pixels, of the grid cells candidate pairs come from (TP_CELL_DEFAULT)
+TOPO_CELLS = (0, 8, 16, 32, 64, 128, 256)     # what ``cell`` may be; 0 stands for TOPO_CELL
 
 _SCRATCH = {}         # (device, bytes) -> scratch tensor: one allocation per scene size, not per call
 
@@ -60,6 +66,18 @@ class Rings(NamedTuple):
     object: torch.Tensor                # int32 [count] on the device: the label of the ring's object
     area2: torch.Tensor                 # int64 [count] on the device: twice the signed area, > 0 outer ring, < 0 hole
     count: int
+
+
+class RingConflicts(NamedTuple):
+    flags: torch.Tensor                 # uint8 [V] on the device: 1 where the edge that starts at this vertex conflicts with another edge
+    count: object                       # the number of flagged edges: an int, or an int64 tensor on the device (check=False)
+
+
+class SafeRings(NamedTuple):
+    rings: Rings
+    rounds: int                         # rounds that restored something
+    restored: int                       # vertices kept beyond plain Douglas-Peucker's
+    conflicts: int                      # conflicting edges of ``rings``: 0 for conflict-free input without a round cap
 
 
 class OrientedBoxes(NamedTuple):
@@ -292,7 +310,8 @@ def simplify_rings(rings: Rings, tolerance: float = 1.5) -> Rings:
     ``tolerance`` is in pixels; 0 returns the rings of ``object_rings`` bit for bit.
 
     Douglas-Peucker does not protect topology: a simplified hole may touch or cross its exterior, and the polygons of two objects
-    may overlap by up to the tolerance.  Orthogonalising building outlines is out of scope.
+    may overlap by up to the tolerance.  ``simplify_rings_safe`` repairs that, and ``ring_conflicts`` reports it.  Orthogonalising
+    building outlines is out of scope.
 
     One host read, of the new vertex count and a status word (16 bytes), between the two phases."""
     q = simplify_q(tolerance)
@@ -323,6 +342,149 @@ def simplify_rings(rings: Rings, tolerance: float = 1.5) -> Rings:
     return Rings(out_vertices, out_offsets, obj.clone(), out_area2, R)
 
 
+_TOPO_STATUS = ("bit 1: a coordinate outside [0, 16384], bit 4: offsets that do not ascend from 0 to the vertex count; bit 2: a ring reached "
+                "its round cap, bit 8: a vertex count that is not the device's own, bit 16: the grid's entry capacity, all three bugs in "
+                "the kernels or the wrapper, not properties of the rings")
+
+
+def _check_cell(cell) -> int:
+    if cell not in TOPO_CELLS:
+        raise StcdError(f"cell must be 0 or one of {TOPO_CELLS[1:]}, got {cell!r}")
+    return int(cell)
+
+
+def _topo_buffers(dev, R: int, V: int, cell: int):
+    nbytes = int(_lib.lib().stcd_rings_topo_scratch_bytes(R, V, cell))
+    key = (str(dev), "topo", nbytes)
+    scratch = _SCRATCH.get(key)
+    if scratch is None:
+        scratch = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return scratch
+
+
+def _topo_entries(dev, n: int) -> torch.Tensor:
+    """The (cell, edge) entries of the grid: a buffer of its own, so that it can grow while the scratch buffer holds a state."""
+    key = (str(dev), "topo_entries")
+    t = _SCRATCH.get(key)
+    if t is None or t.numel() < n:
+        t = _SCRATCH[key] = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    return t
+
+
+def ring_conflicts(rings: Rings, cell: int = 0, check: bool = True) -> RingConflicts:
+    """Which edges of ``rings`` (any ``Rings`` with int32 ``(y, x)`` vertices in ``[0, 16384]``: traced, simplified, hulls, foreign)
+    conflict with another edge, of the same ring or of another, on the device: ``flags`` is uint8 ``[V]``, 1 where the edge from
+    vertex ``k`` of its ring to vertex ``k + 1`` (the last one back to the first) does, ``count`` their number (include/stcd_hip.h,
+    ``stcd_rings_conflicts``; tests/topology_spec.py is the specification and the device equals it to the bit).  Proper crossings, a
+    vertex inside another edge, collinear overlaps and spikes conflict; two edges that meet at a vertex of both do not, so the rings
+    of ``object_rings`` have none.  Known limit: a crossing exactly through a vertex that both rings share is not seen.
+
+    Candidate pairs come from a uniform grid of ``cell`` x ``cell`` pixels (a power of two from 8 to 256, 0 for the default of
+    ``TOPO_CELL``); the result does not depend on it.  ``check=True`` reads the counts afterwards (one copy of 64 bytes), repeats the
+    call once with the exact capacity if the grid held more entries than the default allows, and raises ``StcdError`` on a status;
+    ``count`` is an int.  ``check=False`` reads nothing back: ``count`` is an int64 tensor on the device, -1 where a status was set
+    (the flags are then not valid)."""
+    cell = _check_cell(cell)
+    vertices, offsets, obj, R, V = _check_rings(rings)
+    dev = vertices.device
+    with torch.cuda.device(dev):
+        flags = torch.zeros(V, dtype=torch.uint8, device=dev)
+        if R == 0 or V == 0:
+            return RingConflicts(flags, 0 if check else torch.zeros((), dtype=torch.int64, device=dev))
+        scratch = _topo_buffers(dev, R, V, cell)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+        cap = 4 * V + 4096
+        for attempt in range(2):
+            entries = _topo_entries(dev, cap)
+            _lib.check(_lib.lib().stcd_rings_conflicts(_ptr(vertices), _ptr(offsets), R, V, cell, _ptr(flags), _ptr(counts), _ptr(entries), cap,
+                                                       _ptr(scratch), scratch.numel(), _stream(dev)))
+            if not check:
+                return RingConflicts(flags, counts[4])
+            c = [int(v) for v in counts.cpu().numpy()]
+            if c[0] != 16 or attempt == 1:
+                break
+            cap = c[2]
+        if c[0]:
+            raise StcdError(f"ring_conflicts: status {c[0]} ({_TOPO_STATUS})")
+    return RingConflicts(flags, c[4])
+
+
+def simplify_rings_safe(rings: Rings, tolerance: float = 1.5, max_rounds: Optional[int] = None, cell: int = 0) -> SafeRings:
+    """``simplify_rings`` with its topology repaired, on the device: ``SafeRings(rings, rounds, restored, conflicts)``.  Round 0 is
+    ``simplify_rings`` itself.  Then, round by round, every current edge that conflicts with another one (``ring_conflicts``' rule) or
+    whose pocket is hit -- the closed polygon of the vertices it dropped holds the first vertex of another ring, on its boundary or
+    inside -- gets back the dropped vertex Douglas-Peucker would split at next; a ring whose kept area then is 0 or has changed its
+    sign gets back all of them; the loop ends with the round that restores nothing (include/stcd_hip.h, ``stcd_rings_safe_begin`` /
+    ``_round`` / ``_write``; tests/topology_spec.py is the specification and the device equals it to the bit).  On conflict-free input
+    (every ``object_rings`` result) the result has no conflicting edge, and every ring winds round every other ring's first vertex as
+    often, mod 2, as in the input: no hole leaves its exterior and no object ends up inside another's polygon.  Where plain
+    Douglas-Peucker has no flagged edge the result equals ``simplify_rings`` bit for bit, after round 0 and one detection pass.
+
+    ``rings`` is a ``Rings`` (same count, object and ring order, every ring a subsequence of its input with the first vertex still
+    first, ``area2`` recomputed); ``rounds`` counts the rounds that restored something, ``restored`` the vertices kept beyond plain
+    Douglas-Peucker's, ``conflicts`` the conflicting edges of the result: 0 unless the input conflicts already (foreign rings: the loop
+    still ends) or ``max_rounds`` was reached, after which one more detection pass is made and what stands is returned.  ``cell`` is
+    the grid cell of ``ring_conflicts``; the result does not depend on it.  Tolerance 0 returns the input.  Known limit: a crossing
+    exactly through a vertex that both rings share is not seen.
+
+    One host read of 64 bytes after round 0 and one per round: the status, the number of restored vertices, which decides whether
+    another round follows and sizes it, and the grid's entry count, which sizes its buffer.  Nothing else is copied to the host."""
+    q = simplify_q(tolerance)
+    cell = _check_cell(cell)
+    if max_rounds is not None:
+        max_rounds = int(max_rounds)
+        if max_rounds < 0:
+            raise StcdError(f"max_rounds must be >= 0 or None, got {max_rounds}")
+    vertices, offsets, obj, R, V = _check_rings(rings)
+    dev = vertices.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        if R == 0 or V == 0:
+            return SafeRings(Rings(vertices.clone(), offsets.clone(), obj.clone(), rings.area2.clone(), R), 0, 0, 0)
+        if q == 0:
+            return SafeRings(Rings(vertices.clone(), offsets.clone(), obj.clone(), rings.area2.clone(), R), 0, 0,
+                             ring_conflicts(rings, cell).count)
+        scratch = _topo_buffers(dev, R, V, cell)
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+
+        def read(what):
+            c = [int(v) for v in counts.cpu().numpy()]
+            if c[0] & ~16:
+                raise StcdError(f"simplify_rings_safe: {what} reports status {c[0]} ({_TOPO_STATUS})")
+            return c
+
+        _lib.check(L.stcd_rings_safe_begin(_ptr(vertices), _ptr(offsets), R, V, q, cell, _ptr(counts), _ptr(scratch), scratch.numel(), _stream(dev)))
+        E0 = E = read("round 0")[1]
+        cap = 4 * E + 4096
+        rounds = 0
+        while True:
+            restore = max_rounds is None or rounds < max_rounds
+            for attempt in range(2):
+                entries = _topo_entries(dev, cap)
+                _lib.check(L.stcd_rings_safe_round(_ptr(vertices), _ptr(offsets), R, V, cell, E, 1 if restore else 0, _ptr(counts), _ptr(entries), cap,
+                                                   _ptr(scratch), scratch.numel(), _stream(dev)))
+                c = read(f"round {rounds + 1}")
+                if not c[0]:
+                    break
+                if attempt == 1:
+                    raise StcdError(f"simplify_rings_safe: round {rounds + 1} reports status {c[0]} ({_TOPO_STATUS})")
+                cap = c[2]                                      # the grid held more entries than the buffer: nothing was restored
+            conflicts = c[4]
+            if not restore or c[3] == 0:
+                break
+            E += c[3]
+            cap = max(cap, c[2] + 4 * c[3] + 4096)
+            rounds += 1
+            if rounds > V:
+                raise StcdError("simplify_rings_safe: more rounds than vertices; this is a bug in the kernels, not a property of the rings")
+        out_vertices = torch.empty((E, 2), dtype=torch.int32, device=dev)
+        out_offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        out_area2 = torch.empty(R, dtype=torch.int64, device=dev)
+        _lib.check(L.stcd_rings_safe_write(_ptr(vertices), _ptr(offsets), R, V, cell, E, _ptr(out_vertices), _ptr(out_offsets), _ptr(out_area2),
+                                           _ptr(counts), _ptr(scratch), scratch.numel(), _stream(dev)))
+    return SafeRings(Rings(out_vertices, out_offsets, obj.clone(), out_area2, R), rounds, E - E0, conflicts)
+
+
 def convex_hulls(rings: Rings) -> Rings:
     """The convex hull of every ring of ``rings`` (``object_rings``' result, or any ``Rings`` with int32 ``(y, x)`` vertices in
     ``[0, 16384]``), on the device: a new ``Rings`` with the same ``count``, ``object`` and ring order, every ring the subsequence
@@ -334,7 +496,8 @@ def convex_hulls(rings: Rings) -> Rings:
     shrink.  A ring of 0, 1 or 2 distinct points, or all on one line, gives 0, 1 or 2 vertices and ``area2`` 0.  ``rings_to_geojson``,
     ``rasterize_rings`` and ``oriented_boxes`` take the result unchanged.
 
-    A ring that crosses itself (a foreign ring of ``geojson_to_rings``, possibly a ring of ``simplify_rings``) or repeats a hull
+    A ring that crosses itself (a foreign ring of ``geojson_to_rings``, possibly a ring of ``simplify_rings``, never one of
+    ``simplify_rings_safe`` on traced rings) or repeats a hull
     vertex still gives a subsequence that holds its leftmost and rightmost vertex, but which others it holds is unspecified and it
     need not be a convex polygon in travel order: take the hull of the traced rings first, which costs nothing extra.
 
