@@ -7,6 +7,7 @@ The scene is synthetic (stcd_amd.synth); with ``--load_path`` the weights of a t
 scores are those of a randomly initialised network and only show the plumbing.
 
     python examples/predict_scene_synth.py --size 1024 --tile 256 --stride 128 --window hann --tta d4
+    python examples/predict_scene_synth.py --touching 40 --split 8 --vector buildings.geojson --boxes boxes.geojson
 """
 import argparse
 import os
@@ -50,6 +51,14 @@ parser.add_argument("--boundary", type=float, default=None, metavar="T",
                     help="also print boundary precision, recall and F1 at T pixels and the Hausdorff distance of the prediction against the "
                          "label (distance.boundary_scores); with --vector ... --simplify the same scores of the simplified polygons' raster "
                          "against the mask they came from")
+parser.add_argument("--split", type=float, default=None, metavar="R",
+                    help="with --vector: split objects that touch before they are labelled (objects.split_objects): the mask is eroded by "
+                         "a disc of R pixels to cores, every pixel goes to its nearest core and a cut is made where two owners meet, so "
+                         "that --vector and --boxes write one polygon and one rectangle per building")
+parser.add_argument("--min_core", type=int, default=0, metavar="A", help="with --split: cores of fewer than A pixels are dropped")
+parser.add_argument("--touching", type=int, default=0, metavar="N",
+                    help="with --vector: vectorise a synthetic mask of N rectangles that touch their neighbours instead of the prediction "
+                         "(an untrained network predicts no buildings): what --split is for")
 parser.add_argument("--vector_label", type=str, default="", metavar="IN.geojson",
                     help="read the label from GeoJSON polygons in pixel coordinates (objects.geojson_to_rings + rasterize_rings) instead of the synthetic one")
 
@@ -61,10 +70,27 @@ def print_boundary(what, scores, tolerance):
           f"({scores.n_pred} / {scores.n_label} boundary pixels); Hausdorff distance {hd}")
 
 
+def touching_rectangles(size, n, dev):
+    """uint8 [size,size] on the device: n rectangles in rows, each overlapping the next by a few pixels at a corner."""
+    m = np.zeros((size, size), np.uint8)
+    h, w, y, x = 40, 56, 8, 8
+    for k in range(n):
+        if x + w > size - 8:
+            y, x = y + h + 42, 8
+        if y + h + 30 > size:
+            break
+        dy = 30 * (k % 2)                                       # every second one lower: they share 10 rows
+        m[y + dy:y + dy + h, x:x + w] = 255
+        x += w - 5                                              # the next one starts 5 columns inside this one
+    return torch.from_numpy(m).to(dev)
+
+
 def main(argv=None):
     args = parser.parse_args(argv)
     if args.boxes and not args.vector:
         parser.error("--boxes needs --vector")
+    if (args.split is not None or args.touching) and not args.vector:
+        parser.error("--split and --touching need --vector")
     if args.topology and not (args.vector and args.simplify is not None):
         parser.error("--topology needs --vector and --simplify")
     assert torch.cuda.is_available(), "the engine needs a GPU (no CPU fallback)"
@@ -103,7 +129,15 @@ def main(argv=None):
     if args.vector:
         # the mask as vector data: small objects and small holes removed, the rest numbered, outlined and written as polygons
         from stcd_amd import objects
-        clean = objects.filter_objects(res.mask.contiguous(), args.min_area, args.max_hole)
+        source = touching_rectangles(args.size, args.touching, dev) if args.touching else res.mask.contiguous()
+        clean = objects.filter_objects(source, args.min_area, args.max_hole)
+        if args.split is not None:
+            # neighbours that touch are one component: cut them apart where the nearest cores change
+            before = objects.label_components(clean).count
+            split = objects.split_objects(clean, args.split, min_core_area=args.min_core)
+            clean = split.mask
+            print(f"split at {args.split} px: {split.n_cores} cores, {split.cut_pixels} pixels cut, {split.orphan_pixels} orphan pixels; "
+                  f"{before} objects before, {objects.label_components(clean).count} after")
         comp = objects.label_components(clean)
         rings = objects.object_rings(comp)
         traced = int(rings.vertices.shape[0])

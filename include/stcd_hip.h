@@ -833,6 +833,49 @@ int stcd_mask_buffer(const uint8_t* mask, int height, int width, int seeds, int 
 int stcd_boundary_match(const uint8_t* pred, const uint8_t* label, int height, int width, const int32_t* q, int n_q, int64_t* counts,
                         void* scratch, int64_t scratch_bytes, void* hip_stream);
 
+/* ---- nearest-seed (feature) transform: the distance transform above with the seed it found, what
+ *      scipy.ndimage.distance_transform_edt(return_indices=True) gives as a linear index, and what is read off it: Voronoi growth of
+ *      a label plane (skimage.segmentation.expand_labels) and the distance-transform split of merged objects.
+ *      tests/nearest_spec.py states every output; all quantities are integers.  Seeds, modes and the ignore plane are stcd_edt's.
+ *        - index[i][j] = y * width + x of the seed (y, x) that minimises (i - y)^2 + (j - x)^2; among equal distances the smallest
+ *          column x wins, then the smallest row y.  A seed's nearest seed is itself.  With no seed in the frame every index is -1
+ *          (and d2 NO_SEED).  height * width <= 2^28, so the index fits int32.  d2, where asked for, is stcd_edt's to the bit.
+ *        - gather: out[p] = values[index[p]] where d2[p] <= q, else 0.  With mask = (labels != 0), values = labels and q =
+ *          floor(distance^2) that is expand_labels(labels, distance) under the tie rule above; q = 0 returns the labels.
+ *        - split (stcd_objects_split_cut), from mask M, its components L0 (`labels`), the components Lc of a core mask
+ *          (`core_labels`: M eroded by a disc, small cores dropped) and index, the nearest-seed transform of the core mask, mode 1:
+ *          owner[p] = Lc[index[p]] if p is set in M, index[p] >= 0 and L0[index[p]] == L0[p], else 0.  A set pixel with owner 0 is
+ *          an ORPHAN: its nearest core belongs to another component, or there is no core.  A set pixel p is CUT (out byte 0) iff
+ *          owner[p] != 0 and one of its neighbours right, down-left, down, down-right inside the frame has a non-zero owner other
+ *          than owner[p]; every other set pixel becomes mask_value, every unset pixel 0.  Of two 8-adjacent pixels with different
+ *          owners the earlier in raster order is cut, so a component of out (4- or 8-connected) holds two owners only where
+ *          orphans join them.  Orphans never cut and are never cut.
+ *      The tie rule is the one the kernels imply: the row pass takes the leftmost argmin column, and along a column the seed above
+ *      wins a tie with the seed below.  The column pass's third launch, k_edt_col_near, writes g with bit 15 set where the column's
+ *      nearer seed is strictly below (g <= 16383 leaves the bit free; 0xFFFF stays "no seed"), so the scratch buffer is that of
+ *      stcd_edt; the row pass strips the bit into a side line of LDS (a byte per four columns) as it loads the row, searches the
+ *      argmins as before and rebuilds the seed row of column arg[j] in its epilogue.  Four launches per transform, no atomics. ---- */
+/* Bytes of the scratch buffer of the two entries below (16-byte aligned): those of stcd_edt_scratch_bytes. */
+int64_t stcd_edt_nearest_scratch_bytes(int height, int width);
+/* index: int32 [height,width] on the device; d2: NULL, or int32 [height,width].  Refused before any HIP call: null pointers (d2 and
+ * ignore aside), a shape outside [1, 16384], seeds outside 0..2, an ignore plane with seeds 0 or 1, index / d2 not 4-byte or scratch
+ * not 16-byte aligned, a scratch buffer that is too small.  16-byte stores when width % 4 == 0 and index (and d2) are 16-byte
+ * aligned. */
+int stcd_edt_nearest(const uint8_t* mask, const uint8_t* ignore, int height, int width, int seeds, int32_t* d2, int32_t* index,
+                     void* scratch, int64_t scratch_bytes, void* hip_stream);
+/* out: int32 [height,width] on the device = values[index] where d2 <= q, else 0; values: int32 [height,width]; q >= 0.  Neither
+ * index nor d2 is written.  Refused before any HIP call: null pointers, a shape outside [1, 16384], seeds outside 0..2, q < 0,
+ * values / out not 4-byte or scratch not 16-byte aligned, a scratch buffer that is too small, out overlapping mask or values. */
+int stcd_edt_gather(const uint8_t* mask, int height, int width, int seeds, int q, const int32_t* values, int32_t* out, void* scratch,
+                    int64_t scratch_bytes, void* hip_stream);
+/* One pass, one launch: out uint8 [height,width] as defined above; owner: NULL, or int32 [height,width]; counts: int64 [2] on the
+ * device = (cut pixels, orphan pixels), cleared by the entry itself (one hipMemsetAsync), reduced per wave and block before one
+ * 64-bit integer atomic per block and counter.  labels, core_labels, index: int32 [height,width]; an index outside [-1, height *
+ * width) counts as -1.  Refused before any HIP call: null pointers (owner aside), a shape outside [1, 16384], mask_value outside
+ * [1, 255], int32 planes not 4-byte or counts not 8-byte aligned, out overlapping mask.  Needs no scratch buffer. */
+int stcd_objects_split_cut(const uint8_t* mask, const int32_t* labels, const int32_t* core_labels, const int32_t* index, int height,
+                           int width, int mask_value, uint8_t* out, int32_t* owner, int64_t* counts, void* hip_stream);
+
 /* ---- per-op entry points (NHWC, activation dtype per `dtype`); used by the parity tests.
  *      Geometry is the engine's generic "tap list" convolution: see DESIGN.md section 3. ---- */
 typedef struct stcd_conv_geom {

@@ -189,6 +189,10 @@ _PROTOS = {
     "stcd_edt": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "stcd_mask_buffer": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp]),
     "stcd_boundary_match": (_i, [_vp, _vp, _i, _i, C.POINTER(C.c_int32), _i, _vp, _vp, _i64, _vp]),
+    "stcd_edt_nearest_scratch_bytes": (_i64, [_i, _i]),
+    "stcd_edt_nearest": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_edt_gather": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "stcd_objects_split_cut": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "stcd_op_conv": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_conv_fused": (_i, [C.POINTER(ConvGeom), C.POINTER(ConvFused), _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "stcd_op_wgrad": (_i, [_i, _i, C.POINTER(ConvGeom), _vp, _vp, _vp, _vp, _i64, _vp]),

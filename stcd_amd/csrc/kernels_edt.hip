@@ -30,6 +30,15 @@
 //                    Epilogue, a template parameter: EDT_EPI_D2 stores the int32 plane, EDT_EPI_MASK the threshold as bytes,
 //                    EDT_EPI_MATCH accumulates n, max d2 and within[t] at the boundary pixels of the other mask (evaluated by
 //                    edt_seed4 in place), reduced per wave and block before one integer atomic per block and counter.
+//
+// The nearest-seed transform (stcd_edt_nearest, stcd_edt_gather) keeps the seed the minimum came from.  Its third launch is
+// k_edt_col_near: k_edt_col_dist's body with bit 15 of g set where the column's nearer seed is strictly below the row (a tie goes
+// to the seed above, the smaller row; g <= 16383 leaves the bit free and EDT_NONE stays EDT_NONE), so no second plane is written
+// and the scratch buffer is unchanged.  k_edt_row<EDT_EPI_INDEX / _GATHER> strips that bit while it loads the row into LDS, into a
+// side line of a byte per four columns (4 KiB at 16384: 68 KiB per block, still two blocks per CU of 160 KiB), so h and the argmin
+// search are exactly those of the other epilogues; the epilogue rebuilds the seed row of column arg[j] as i - h or i + h and
+// writes the linear index (and d2), or values[index] under the threshold.  Leftmost argmin column, then the upper seed: the
+// smallest column wins a tie, then the smallest row.
 #include <algorithm>
 
 #include "common.h"
@@ -45,9 +54,10 @@ namespace stcd {
 #define EDT_NONE 0xFFFFu                       // g: the column has no seed; table: no seed row
 #define EDT_NO_SEED (1 << 30)                  // NO_SEED
 #define EDT_MAX_Q 8
+#define EDT_BELOW 0x8000u                      // g of k_edt_col_near: the nearer seed of the column is below the row
 
 enum { EDT_SEED_UNSET = 0, EDT_SEED_SET = 1, EDT_SEED_BOUNDARY = 2 };
-enum { EDT_EPI_D2 = 0, EDT_EPI_MASK = 1, EDT_EPI_MATCH = 2 };
+enum { EDT_EPI_D2 = 0, EDT_EPI_MASK = 1, EDT_EPI_MATCH = 2, EDT_EPI_INDEX = 3, EDT_EPI_GATHER = 4 };
 
 struct EdtSrc {                                // a mask and how to read seeds off it
     const uint8_t* mask;
@@ -57,12 +67,14 @@ struct EdtSrc {                                // a mask and how to read seeds o
 };
 
 struct EdtEpi {
-    int32_t* d2;                               // EDT_EPI_D2
+    int32_t* d2;                               // EDT_EPI_D2; EDT_EPI_INDEX: may be nullptr
+    int32_t* index;                            // EDT_EPI_INDEX
+    const int32_t* values; int32_t* gathered;  // EDT_EPI_GATHER, with q
     uint8_t* out; int q, keep_above, mask_value;      // EDT_EPI_MASK
     EdtSrc own;                                // EDT_EPI_MATCH: the mask whose boundary pixels are measured
     unsigned long long* counts;                // (n, max_d2, within[0..nq-1]) of this side
     int nq; int qs[EDT_MAX_Q];
-    int vec;                                   // 16-byte (d2) / 4-byte (out) stores: W % 4 == 0 and the pointer aligned
+    int vec;                                   // 16-byte (d2, index, gathered) / 4-byte (out) stores: W % 4 == 0 and the pointers aligned
 };
 
 // bytes j0 .. j0 + 3 of row i, byte k in bits 8k; a pixel outside the frame reads 0.  vec: see EdtSrc (then j0 + 3 < W)
@@ -202,9 +214,9 @@ k_edt_col_carry(int W, int Wp, int chunks, uint32_t* tab) {
     }
 }
 
-// g: uint16 [H][Wp]
-__global__ void __launch_bounds__(EDT_THREADS)
-k_edt_col_dist(EdtSrc s, int Wp, const uint32_t* __restrict__ tab, uint16_t* __restrict__ g) {
+// g: uint16 [H][Wp]; BELOW: with EDT_BELOW where the nearer seed is strictly below row i
+template <bool BELOW>
+__device__ __forceinline__ void edt_col_dist(const EdtSrc& s, int Wp, const uint32_t* __restrict__ tab, uint16_t* __restrict__ g) {
     const int j0 = (blockIdx.x * EDT_THREADS + threadIdx.x) * EDT_LANE_COLS, c = blockIdx.y;
     if (j0 >= s.W) return;
     uint64_t bits[EDT_LANE_COLS];
@@ -225,10 +237,16 @@ k_edt_col_dist(EdtSrc s, int Wp, const uint32_t* __restrict__ tab, uint16_t* __r
             if (hi) dn = (uint32_t)(__ffsll((long long)hi) - 1);
             else if (below != EDT_NONE) dn = below - (uint32_t)i;
             d[k] = min(up, dn);                                        // at most 16383, or EDT_NONE
+            if constexpr (BELOW) d[k] |= dn < up ? EDT_BELOW : 0u;     // dn < up: dn is a distance
         }
         *reinterpret_cast<uint2*>(g + (int64_t)i * Wp + j0) = make_uint2(d[0] | (d[1] << 16), d[2] | (d[3] << 16));    // 8-byte aligned
     }
 }
+
+__global__ void __launch_bounds__(EDT_THREADS)
+k_edt_col_dist(EdtSrc s, int Wp, const uint32_t* __restrict__ tab, uint16_t* __restrict__ g) { edt_col_dist<false>(s, Wp, tab, g); }
+__global__ void __launch_bounds__(EDT_THREADS)
+k_edt_col_near(EdtSrc s, int Wp, const uint32_t* __restrict__ tab, uint16_t* __restrict__ g) { edt_col_dist<true>(s, Wp, tab, g); }
 
 // ------------------------------------------------------------------------------------------------ the row pass
 __device__ __forceinline__ unsigned long long edt_key(const uint16_t* __restrict__ h, int j, int k) {     // (cost, k): the minimum is the leftmost argmin
@@ -236,6 +254,12 @@ __device__ __forceinline__ unsigned long long edt_key(const uint16_t* __restrict
     const uint32_t h2 = hv == EDT_NONE ? (uint32_t)EDT_NO_SEED : hv * hv;
     const int d = j - k;
     return ((unsigned long long)((uint32_t)(d * d) + h2) << 32) | (uint32_t)k;
+}
+// two g values of k_edt_col_near in one word: the EDT_BELOW bits (bit 0: the low half) are taken out of w
+__device__ __forceinline__ uint32_t edt_strip2(uint32_t& w) {
+    const uint32_t lo = (w & 0xFFFFu) != EDT_NONE ? w & EDT_BELOW : 0u, hi = (w >> 16) != EDT_NONE ? w & (EDT_BELOW << 16) : 0u;
+    w &= ~(lo | hi);
+    return (lo >> 15) | (hi >> 30);
 }
 __device__ __forceinline__ unsigned long long edt_wave_min(unsigned long long v) {
 #pragma unroll
@@ -264,9 +288,18 @@ k_edt_row(const uint16_t* __restrict__ g, int H, int W, int Wp, EdtEpi ep) {
     __shared__ unsigned part[4][2 + EDT_MAX_Q];
     uint16_t* __restrict__ h = edt_lds;                                // [Wp]
     uint16_t* __restrict__ arg = edt_lds + Wp;                         // [Wp]: arg[j] = k*(j)
+    constexpr bool NEAR = EPI == EDT_EPI_INDEX || EPI == EDT_EPI_GATHER;      // g is k_edt_col_near's
+    uint8_t* __restrict__ below = reinterpret_cast<uint8_t*>(edt_lds + 2 * Wp);       // NEAR: [Wp / 4], bit k: the seed of column 4 b + k is below row i
     const int i = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const uint16_t* __restrict__ grow = g + (int64_t)i * Wp;
-    for (int j = tid * 4; j < Wp; j += EDT_THREADS * 4) *reinterpret_cast<uint2*>(h + j) = *reinterpret_cast<const uint2*>(grow + j);
+    for (int j = tid * 4; j < Wp; j += EDT_THREADS * 4) {
+        uint2 w = *reinterpret_cast<const uint2*>(grow + j);
+        if constexpr (NEAR) {
+            const uint32_t b01 = edt_strip2(w.x), b23 = edt_strip2(w.y);
+            below[j >> 2] = (uint8_t)(b01 | (b23 << 2));
+        }
+        *reinterpret_cast<uint2*>(h + j) = w;
+    }
     __syncthreads();
 
     int L = 1;
@@ -334,6 +367,34 @@ k_edt_row(const uint16_t* __restrict__ g, int H, int W, int Wp, EdtEpi ep) {
             if (ep.vec) *reinterpret_cast<uint4*>(ep.d2 + base + j0) = make_uint4(v[0], v[1], v[2], v[3]);
             else
                 for (int k = 0; k < n; ++k) ep.d2[base + j0 + k] = (int32_t)v[k];
+        } else if constexpr (NEAR) {
+            int32_t at[EDT_LANE_COLS];                                 // the linear index of the nearest seed, -1: the frame has none
+#pragma unroll
+            for (int k = 0; k < EDT_LANE_COLS; ++k) {
+                at[k] = -1;
+                if (k < n) {
+                    const int a = arg[j0 + k];
+                    const int hv = h[a];
+                    if (hv != (int)EDT_NONE) at[k] = (((below[a >> 2] >> (a & 3)) & 1) ? i + hv : i - hv) * W + a;
+                }
+            }
+            if constexpr (EPI == EDT_EPI_INDEX) {
+                if (ep.vec) {
+                    *reinterpret_cast<int4*>(ep.index + base + j0) = make_int4(at[0], at[1], at[2], at[3]);
+                    if (ep.d2) *reinterpret_cast<uint4*>(ep.d2 + base + j0) = make_uint4(v[0], v[1], v[2], v[3]);
+                } else {
+                    for (int k = 0; k < n; ++k) ep.index[base + j0 + k] = at[k];
+                    if (ep.d2)
+                        for (int k = 0; k < n; ++k) ep.d2[base + j0 + k] = (int32_t)v[k];
+                }
+            } else {
+                int32_t o[EDT_LANE_COLS];
+#pragma unroll
+                for (int k = 0; k < EDT_LANE_COLS; ++k) o[k] = k < n && v[k] <= (uint32_t)ep.q ? ep.values[at[k]] : 0;      // q < NO_SEED: at[k] >= 0
+                if (ep.vec) *reinterpret_cast<int4*>(ep.gathered + base + j0) = make_int4(o[0], o[1], o[2], o[3]);
+                else
+                    for (int k = 0; k < n; ++k) ep.gathered[base + j0 + k] = o[k];
+            }
         } else if constexpr (EPI == EDT_EPI_MASK) {
             uint32_t o = 0;
 #pragma unroll
@@ -403,14 +464,17 @@ hipError_t edt_run(const EdtSrc& src, const EdtEpi& ep, void* scratch, hipStream
     const dim3 cgrid((unsigned)((Wp / EDT_LANE_COLS + EDT_THREADS - 1) / EDT_THREADS), (unsigned)chunks);
     k_edt_col_seeds<<<cgrid, EDT_THREADS, 0, s>>>(src, Wp, tab);
     k_edt_col_carry<<<(unsigned)((W + EDT_THREADS - 1) / EDT_THREADS), EDT_THREADS, 0, s>>>(W, Wp, chunks, tab);
-    k_edt_col_dist<<<cgrid, EDT_THREADS, 0, s>>>(src, Wp, tab, g);
+    constexpr bool NEAR = EPI == EDT_EPI_INDEX || EPI == EDT_EPI_GATHER;      // the side line of LDS: a byte per four columns
+    if constexpr (NEAR) k_edt_col_near<<<cgrid, EDT_THREADS, 0, s>>>(src, Wp, tab, g);
+    else k_edt_col_dist<<<cgrid, EDT_THREADS, 0, s>>>(src, Wp, tab, g);
     static bool attr_set = false;                                      // per instantiation: the row of 16384 needs 64 KiB beside the static LDS
     if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_edt_row<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * EDT_DIM_MAX);
+        const hipError_t e = hipFuncSetAttribute((const void*)k_edt_row<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 4 * EDT_DIM_MAX + (NEAR ? EDT_DIM_MAX / 4 : 0));
         if (e != hipSuccess) return e;
         attr_set = true;
     }
-    k_edt_row<EPI><<<(unsigned)H, EDT_THREADS, (size_t)4 * Wp, s>>>(g, H, W, Wp, ep);
+    k_edt_row<EPI><<<(unsigned)H, EDT_THREADS, (size_t)4 * Wp + (NEAR ? Wp / 4 : 0), s>>>(g, H, W, Wp, ep);
     return hipGetLastError();
 }
 
@@ -479,6 +543,41 @@ int stcd_boundary_match(const uint8_t* pred, const uint8_t* label, int height, i
     STCD_HIP(edt_run<EDT_EPI_MATCH>(bl, ep, scratch, s));
     ep.own = bl; ep.counts = (unsigned long long*)counts + stride;     // side 1: the reverse
     STCD_HIP(edt_run<EDT_EPI_MATCH>(bp, ep, scratch, s));
+    return 0;
+}
+
+int64_t stcd_edt_nearest_scratch_bytes(int height, int width) { return stcd_edt_scratch_bytes(height, width); }
+
+int stcd_edt_nearest(const uint8_t* mask, const uint8_t* ignore, int height, int width, int seeds, int32_t* d2, int32_t* index, void* scratch,
+                     int64_t scratch_bytes, void* hip_stream) {
+    STCD_CHECK(mask && index && scratch, "null pointer argument");
+    STCD_CHECK(edt_shape_ok(height, width), "height and width must be in [1, 16384]");
+    STCD_CHECK(seeds >= EDT_SEED_UNSET && seeds <= EDT_SEED_BOUNDARY, "seeds must be 0 (unset), 1 (set) or 2 (boundary)");
+    STCD_CHECK(!ignore || seeds == EDT_SEED_BOUNDARY, "an ignore plane is read by seeds == 2 (boundary) alone");
+    STCD_CHECK(edt_aligned(index, 4) && edt_aligned(d2, 4) && edt_aligned(scratch, 16), "index and d2 must be 4-byte and scratch 16-byte aligned");
+    STCD_CHECK(scratch_bytes >= edt_bytes(height, width), "scratch too small (stcd_edt_nearest_scratch_bytes)");
+    EdtEpi ep = {};
+    ep.d2 = d2; ep.index = index;
+    ep.vec = width % 4 == 0 && edt_aligned(index, 16) && edt_aligned(d2, 16);
+    STCD_HIP(edt_run<EDT_EPI_INDEX>(edt_src(mask, ignore, height, width, seeds), ep, scratch, (hipStream_t)hip_stream));
+    return 0;
+}
+
+int stcd_edt_gather(const uint8_t* mask, int height, int width, int seeds, int q, const int32_t* values, int32_t* out, void* scratch,
+                    int64_t scratch_bytes, void* hip_stream) {
+    STCD_CHECK(mask && values && out && scratch, "null pointer argument");
+    STCD_CHECK(edt_shape_ok(height, width), "height and width must be in [1, 16384]");
+    STCD_CHECK(seeds >= EDT_SEED_UNSET && seeds <= EDT_SEED_BOUNDARY, "seeds must be 0 (unset), 1 (set) or 2 (boundary)");
+    STCD_CHECK(q >= 0, "q must be >= 0");
+    const int64_t px = (int64_t)height * width;
+    STCD_CHECK(!edt_overlap(mask, px, out, 4 * px), "out must not overlap mask");
+    STCD_CHECK(!edt_overlap(values, 4 * px, out, 4 * px), "out must not overlap values");
+    STCD_CHECK(edt_aligned(values, 4) && edt_aligned(out, 4) && edt_aligned(scratch, 16), "values and out must be 4-byte and scratch 16-byte aligned");
+    STCD_CHECK(scratch_bytes >= edt_bytes(height, width), "scratch too small (stcd_edt_nearest_scratch_bytes)");
+    EdtEpi ep = {};
+    ep.values = values; ep.gathered = out; ep.q = q < EDT_NO_SEED ? q : EDT_NO_SEED - 1;       // "no seed" is within no q
+    ep.vec = width % 4 == 0 && edt_aligned(out, 16);
+    STCD_HIP(edt_run<EDT_EPI_GATHER>(edt_src(mask, nullptr, height, width, seeds), ep, scratch, (hipStream_t)hip_stream));
     return 0;
 }
 

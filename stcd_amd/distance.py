@@ -8,7 +8,11 @@ them in numpy and the tests ask for equality.
 
 A pixel is set iff its byte is non-zero; pixel (i, j) is a lattice point and ``d2`` the squared distance to the nearest seed inside
 the frame, ``NO_SEED`` where the frame holds none.  A transform is four launches whatever the data (three for the column pass, one
-row pass whose epilogue writes the plane, the threshold or the match counts)."""
+row pass whose epilogue writes the plane, the threshold or the match counts).
+
+``nearest_seed`` is the same transform keeping WHICH seed is nearest (the feature transform, ``stcd_edt_nearest``) and
+``expand_labels`` Voronoi growth of a label plane read off it (``stcd_edt_gather``); tests/nearest_spec.py states both, ties included:
+the smallest column wins, then the smallest row.  ``objects.split_objects`` builds the split of touching objects on them."""
 from __future__ import annotations
 
 import ctypes as C
@@ -130,6 +134,64 @@ def buffer_mask(mask: torch.Tensor, radius, op: str = "dilate", mask_value: int 
             _lib.check(_lib.lib().stcd_mask_buffer(_ptr(src), H, W, seeds, q, 1 - seeds, mask_value, _ptr(out), _ptr(scratch), scratch.numel(),
                                                    _stream(dev)))
             src = out
+    return out
+
+
+def _nearest_scratch_for(device, height: int, width: int) -> torch.Tensor:
+    nbytes = int(_lib.lib().stcd_edt_nearest_scratch_bytes(int(height), int(width)))
+    key = (str(device), nbytes)                                 # the size is stcd_edt's: one buffer serves both
+    t = _SCRATCH.get(key)
+    if t is None:
+        t = _SCRATCH[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return t
+
+
+def nearest_seed(mask: torch.Tensor, to: str = "set", ignore: Optional[torch.Tensor] = None, return_distance: bool = False):
+    """int32 ``[H,W]`` on the device: for every pixel the linear index ``y * W + x`` of the nearest seed of ``mask`` inside the
+    frame, the feature transform (``scipy.ndimage.distance_transform_edt(return_indices=True)`` as one plane; include/stcd_hip.h,
+    ``stcd_edt_nearest``; tests/nearest_spec.py is the specification and the device equals it to the bit).  Seeds, ``to`` and
+    ``ignore`` are ``squared_distance``'s.  Among seeds at the same distance the one in the smallest column wins, then the one in the
+    smallest row; a seed's nearest seed is itself; -1 everywhere when there is no seed.  ``index // W`` and ``index % W`` are the
+    seed's row and column.  With ``return_distance=True`` the result is ``(index, d2)``, ``d2`` being ``squared_distance``'s plane
+    to the bit, out of the same four launches.  Nothing synchronises."""
+    H, W = _check_frame(mask)
+    if to not in _SEEDS:
+        raise StcdError(f"to must be 'unset', 'set' or 'boundary', got {to!r}")
+    dev = mask.device
+    if ignore is not None:
+        if to != "boundary":
+            raise StcdError("an ignore plane is read with to='boundary' alone")
+        _check_mask(ignore, "ignore", (H, W), dev)
+    with torch.cuda.device(dev):
+        index = torch.empty((H, W), dtype=torch.int32, device=dev)
+        d2 = torch.empty((H, W), dtype=torch.int32, device=dev) if return_distance else None
+        scratch = _nearest_scratch_for(dev, H, W)
+        _lib.check(_lib.lib().stcd_edt_nearest(_ptr(mask), _ptr(ignore), H, W, _SEEDS[to], _ptr(d2), _ptr(index), _ptr(scratch), scratch.numel(),
+                                               _stream(dev)))
+    return (index, d2) if return_distance else index
+
+
+def expand_labels(labels, distance) -> torch.Tensor:
+    """A new int32 ``[H,W]`` label plane on the device: every label of ``labels`` (a ``Components`` of ``objects.label_components``,
+    or a contiguous int32 ``[H,W]`` tensor on the GPU, 0 the background) grown by ``distance`` pixels without running into another
+    label, ``skimage.segmentation.expand_labels``: a background pixel within ``distance`` (``buffer_q(distance)`` in squared
+    distance) of a labelled pixel takes the label of the nearest one, under ``nearest_seed``'s tie rule; the other pixels keep what
+    they hold (include/stcd_hip.h, ``stcd_edt_gather``).  Distance 0 returns a copy of the labels.  One elementwise pass forms the
+    seed bytes, then one transform whose epilogue gathers; nothing synchronises."""
+    plane = getattr(labels, "labels", labels)
+    if not torch.is_tensor(plane) or plane.dtype != torch.int32 or plane.dim() != 2 or not plane.is_cuda or not plane.is_contiguous():
+        raise StcdError("labels must be a Components or a contiguous int32 [H,W] tensor on the GPU")
+    H, W = (int(v) for v in plane.shape)
+    if not (1 <= H <= DIM_MAX and 1 <= W <= DIM_MAX):
+        raise StcdError(f"labels must be [H,W] with 1 <= H, W <= {DIM_MAX}, got {(H, W)}")
+    q = buffer_q(distance)
+    dev = plane.device
+    with torch.cuda.device(dev):
+        seeds = (plane != 0).to(torch.uint8)
+        out = torch.empty((H, W), dtype=torch.int32, device=dev)
+        scratch = _nearest_scratch_for(dev, H, W)
+        _lib.check(_lib.lib().stcd_edt_gather(_ptr(seeds), H, W, _SEEDS["set"], q, _ptr(plane), _ptr(out), _ptr(scratch), scratch.numel(),
+                                              _stream(dev)))
     return out
 
 

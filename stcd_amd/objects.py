@@ -18,6 +18,10 @@ its minimum-area rectangle, on the device (stcd_amd/csrc/kernels_hull.hip behind
 ``stcd_rings_boxes``; tests/hull_spec.py is the specification); ``box_shape`` and ``boxes_to_geojson`` read them on the host.  ``rasterize_rings`` goes the other way, from rings to a mask on the
 device (stcd_amd/csrc/kernels_raster.hip behind ``stcd_rings_raster``; tests/raster_spec.py is the specification), with the
 confusion counts against an overlay in the same pass, and ``geojson_to_rings`` reads polygons back on the host.
+
+``split_objects`` comes before all of that where one component holds several buildings: the distance-transform split, on the device
+(``distance.buffer_mask``, ``label_components`` and ``distance.nearest_seed``, then one pass of stcd_amd/csrc/kernels_split.hip behind
+``stcd_objects_split_cut``; tests/nearest_spec.py is the specification).
 """
 from __future__ import annotations
 
@@ -91,6 +95,14 @@ class OrientedBoxes(NamedTuple):
 class Raster(NamedTuple):
     mask: torch.Tensor                  # uint8 [H,W] on the device
     cm: Optional[torch.Tensor]          # int64 [2,2] on the device, cm[label, pred], None without an overlay
+
+
+class SplitObjects(NamedTuple):
+    mask: torch.Tensor                  # uint8 [H,W] on the device: the mask with its cut pixels cleared
+    owner: torch.Tensor                 # int32 [H,W] on the device: the core (1..n_cores) a set pixel belongs to, 0 for unset pixels and orphans
+    n_cores: int
+    cut_pixels: object                  # an int, or an int64 scalar tensor on the device (check=False)
+    orphan_pixels: object               # set pixels with owner 0, likewise
 
 
 class ObjectScores(NamedTuple):
@@ -208,6 +220,61 @@ def filter_objects(mask: torch.Tensor, min_area: int = 0, max_hole: int = 0, con
         if check:
             _raise_if_status(int(scratch[-4:].cpu().numpy().view(np.int32)[0]), "filter_objects")
     return out
+
+
+def split_objects(mask: torch.Tensor, radius, min_core_area: int = 0, connectivity: int = 8, mask_value: int = 255,
+                  check: bool = True) -> SplitObjects:
+    """The distance-transform split of objects that touch: ``mask`` with a cut of one to two pixels where two buildings that one
+    connected component merges meet, on the device (include/stcd_hip.h, ``stcd_objects_split_cut``; tests/nearest_spec.py is the
+    specification and the device equals it to the bit).
+
+    1. The cores are ``distance.buffer_mask(mask, radius, "erode")``, the pixels farther than ``radius`` from every unset pixel;
+       with ``min_core_area > 0`` cores of fewer pixels are dropped (``filter_objects(core, min_area=min_core_area)``).
+    2. The cores and the mask are labelled (``label_components``, ``connectivity``): ``Lc`` with ``n_cores``, and ``L0``.
+    3. ``index = distance.nearest_seed(core, "set")``.
+    4. The owner of a set pixel ``p`` is ``Lc[index[p]]`` if ``L0[index[p]] == L0[p]``, else 0: an orphan, whose nearest core
+       lies in another component or whose component has no core.  Unset pixels have owner 0.
+    5. A set pixel with a non-zero owner is cut if its right, down-left, down or down-right neighbour has another non-zero owner.
+       Orphans never cut and are never cut: a thin arm of one building that reaches towards another's core stays attached.
+
+    Returns ``SplitObjects(mask, owner, n_cores, cut_pixels, orphan_pixels)``: ``mask`` holds ``mask_value`` where a set pixel
+    was not cut.  Of two 8-adjacent pixels with different owners the earlier in raster order is cut, so a component of it (4- or
+    8-connected) holds two owners only where orphan pixels join them, and ``label_components``, ``object_rings``,
+    ``oriented_boxes`` and ``match_objects`` see one object per core.  Limits: a cut costs area; a single building with a neck
+    narrower than ``2 * radius`` is split (``min_core_area`` is the guard); an orphan region that touches two owners keeps them
+    joined.  With ``n_cores == 0`` the transform is skipped and ``mask`` is the input as 0 / ``mask_value``, every set pixel an
+    orphan.
+
+    Two host reads, the 8 bytes each of the two ``label_components`` calls (count and status word); ``check=True`` adds one, of
+    the two counts (16 bytes).  With ``check=False`` ``cut_pixels`` and ``orphan_pixels`` are int64 scalar tensors on the device."""
+    from . import distance                                      # distance does not import this module
+    H, W = distance._check_frame(mask)
+    connectivity = _check_connectivity(connectivity)
+    min_core_area = int(min_core_area)
+    if min_core_area < 0:
+        raise StcdError(f"min_core_area must be >= 0, got {min_core_area}")
+    if isinstance(mask_value, bool) or not isinstance(mask_value, int) or not 1 <= mask_value <= 255:
+        raise StcdError(f"mask_value must be an integer in [1, 255], got {mask_value!r}")
+    dev = mask.device
+    with torch.cuda.device(dev):
+        core = distance.buffer_mask(mask, radius, "erode")
+        if min_core_area > 1:
+            core = filter_objects(core, min_area=min_core_area, connectivity=connectivity, check=False)
+        cores = label_components(core, connectivity)
+        whole = label_components(mask, connectivity)
+        if cores.count:
+            index = distance.nearest_seed(core, "set")
+        else:
+            index = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+        out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        owner = torch.empty((H, W), dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        _lib.check(_lib.lib().stcd_objects_split_cut(_ptr(mask), _ptr(whole.labels), _ptr(cores.labels), _ptr(index), H, W, mask_value, _ptr(out),
+                                                     _ptr(owner), _ptr(counts), _stream(dev)))
+        if not check:
+            return SplitObjects(out, owner, cores.count, counts[0], counts[1])
+        cut, orphan = (int(v) for v in counts.cpu().numpy())
+    return SplitObjects(out, owner, cores.count, cut, orphan)
 
 
 def _check_components(components):
